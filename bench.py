@@ -16,13 +16,17 @@ and checked against the digests stored there.  (LPBOX_BENCH_SHARD=relabel, or a 
 LPs with bids and items relabelled by a rank-seeded permutation.)
 Config 3: step = one ADMM_bqp_unconstrained_legacy solve; config 5: step = init + 100 ADMM iterations of the sharded instance.
 
-Launch:  python bench.py [--config C] [--gpus N] [--steps K] [--warmup W]
+Launch:  python bench.py [--config C] [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
          python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 With --gpus N > 1 and no WORLD_SIZE in the environment bench.py starts its N ranks itself: N fresh child processes (one per GPU,
 RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set), started BEFORE the parent has made any GPU call; the parent only relays rank 0's line.
 
-Without --config (what the driver runs) the headline line is config 2 and, on one GPU, short passes of configs 4, 3 and 5 follow
-OUTSIDE the headline's timed region; each lands under detail.configs.<c> as a complete line of its own (value, roofline, cpu_baseline).
+A plain run does only what its line needs: set-up, W warm-up steps, K timed steps, the line (config 2 unless --config says otherwise).
+--full adds everything else the benchmark measures, each OUTSIDE the headline's timed region: the CPU oracle baselines (cpu_baseline,
+objective_vs_eigen_order_oracle), the opt-in side modes (direct x-update of config 2, comm-lean PCG and the 8-rank model of
+config 5) and, without --config on one GPU, short passes of configs 4, 3 and 5 under detail.configs.<c>, each a complete line of its own.
+--dump-outputs DIR writes what the timed path computed in its last step as DIR/<name>.npy (float64; ranks r > 0 add _rank<r>), at most
+64 MB in all: an array that does not fit is replaced by a fixed, seeded sample of its elements and <name>_sample_index.npy.
 """
 import argparse
 import glob
@@ -210,6 +214,29 @@ def pmc_traffic(kernel_tag, instances):
     return None, None
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out_dir, rank, arrays):
+    """--dump-outputs: each array as out_dir/<name>[_rank<r>].npy in float64.  When they exceed DUMP_LIMIT_BYTES together, the largest
+    are replaced, largest first, by a sample of their elements at indices drawn by RandomState(0) (sorted, saved beside them as
+    <name>_sample_index.npy), so the same run always dumps the same elements."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.asarray(v, np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name in sorted(arrays, key=lambda k: -arrays[k].nbytes):
+        if total <= DUMP_LIMIT_BYTES:
+            break
+        a = arrays[name].ravel()
+        keep = max(1, (DUMP_LIMIT_BYTES - (total - a.nbytes)) // 2 // a.itemsize)     # sample + its index, both f64
+        idx = np.sort(np.random.RandomState(0).choice(a.size, min(keep, a.size), replace=False))
+        arrays[name], arrays[name + "_sample_index"] = a[idx], idx.astype(np.float64)
+        total += 2 * idx.nbytes - a.nbytes
+    suffix = "" if rank == 0 else "_rank%d" % rank
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
+
+
 def dist_setup(args):
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -269,12 +296,16 @@ def main(argv=None):
     ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", type=int, default=None, choices=(2, 3, 4, 5),
-                    help="default: config 2 as the headline + short passes of 4, 3, 5 under detail.configs (one GPU)")
+                    help="default: config 2 as the headline (with --full: + short passes of 4, 3, 5 under detail.configs, one GPU)")
     ap.add_argument("--batch", type=int, default=256, help="instances per GPU (configs 2 and 4)")
     ap.add_argument("--cpu-sample", type=int, default=None, help="instances solved by ONE CPU thread for cpu_baseline (0 = skip)")
     ap.add_argument("--cpu-pool", type=int, default=None, help="instances solved by the all-cores CPU pass")
     ap.add_argument("--variables", type=float, default=1e6, help="variables of the config 5 instance")
-    ap.add_argument("--no-extra-configs", action="store_true", help="default run: headline only, no detail.configs")
+    ap.add_argument("--no-extra-configs", action="store_true", help="with --full: headline only, no detail.configs")
+    ap.add_argument("--full", action="store_true",
+                    help="also CPU baselines, side modes and (without --config) configs 4, 3, 5, all outside the timed region")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed path's results of its last step as DIR/<name>.npy")
     args = ap.parse_args(argv)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(args, argv)
@@ -282,7 +313,7 @@ def main(argv=None):
     if os.environ.get("LPBOX_BENCH_FAIL_RANK") == str(rank) and STUB:           # test hook (tests/test_bench_launch.py): a rank that dies at start
         raise SystemExit(3)
     headline = args.config or 2
-    extras = [] if (args.config is not None or world > 1 or args.no_extra_configs or STUB) else [4, 3, 5]
+    extras = [] if (not args.full or args.config is not None or world > 1 or args.no_extra_configs or STUB) else [4, 3, 5]
 
     def args_for(c, nested):
         a = argparse.Namespace(**vars(args))
@@ -291,11 +322,12 @@ def main(argv=None):
             a.steps = {2: 5, 4: 2, 3: 5, 5: 3}[c] if not nested else {4: 2, 3: 3, 5: 2}[c]
         if nested:
             a.warmup = 1
+            a.dump_outputs = None
         return a
 
     # CPU legs of the LP configs first: their process pools fork, which must happen before this process initialises the GPU
     cpu = {}
-    if world == 1 and rank == 0:
+    if args.full and world == 1 and rank == 0:
         for c in [headline] + extras:
             if c in (2, 4):
                 cpu[c] = cpu_leg_lp(args_for(c, c != headline), nested=c != headline)
@@ -456,11 +488,15 @@ def run_lp_batch(args, ctx, cpu_leg=None):
     k_ms, k_launches = batch.kernel_time()
     objs = np.array([-batch.cal_obj(i) for i in range(B)])
     infeasible = int(sum(batch.check_infeasible_l2f(i) > 0 for i in range(B)))
+    if args.dump_outputs:
+        xs = [batch.get_x_sol(i) for i in range(B)]
+        dump_outputs(args.dump_outputs, rank, {"x_sol": np.concatenate(xs), "x_sol_n": [len(x) for x in xs], "objective": objs,
+                                               "outer_iters": outer, "pcg_iters": pcg, "stop_reason": [batch.stop(i)[0] for i in range(B)]})
 
     # Outside the timed region, config 2 only: the opt-in direct x-update (lpbox_set_x_update; NOT the reference's PCG, so it is reported
     # beside the headline, never as `value`) on the same batch
     direct = None
-    if not c4 and world == 1 and not STUB:
+    if args.full and not c4 and world == 1 and not STUB:
         try:
             batch.set_x_update("direct")
             batch.solve_init(); batch.solve_iter(0, MAX_ITERS)          # warm
@@ -581,6 +617,9 @@ def run_seg(args, ctx, cpu_leg=None):
     dt = time.perf_counter() - t0
     o, p = s.counters()
     ms, nl = s.kernel_time()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, {"x_sol": s.get_x_sol(), "energy": [energy], "objective": [s.get_obj()],
+                                               "outer_iters": [o], "pcg_iters": [p]})
     n, nnz = P["n"], len(P["colidx"])
     mA = 12 * nnz + 4 * (n + 1)
     bytes_solve = o * (3 * mA + 256 * n) + p * (mA + 104 * n)     # B_iter = 3 m_A + 8*32 n + K (m_A + 8*13 n)
@@ -604,7 +643,7 @@ def run_seg(args, ctx, cpu_leg=None):
                              "note": "chain-level: algorithmic bytes of a whole solve / stream time of its launches (HIP events on the "
                                      "solver's stream); the 34 MB working set is L2/MALL resident, per-kernel stats in profiles/"},
                 "detail": {"outer_iters": o, "pcg_per_outer": p / o, "energy": energy, "us_per_iteration": 1e6 * chain_s / o}}
-        if world == 1 and (args.cpu_sample is None or args.cpu_sample > 0):
+        if args.full and world == 1 and (args.cpu_sample is None or args.cpu_sample > 0):
             from oracle import oracle as O
             so = O.SegOracle(0, gray.size, 0)
             so.set_problem(P)
@@ -691,23 +730,28 @@ def run_big(args, ctx, cpu_leg=None):
     sync()
     dt = time.perf_counter() - t0
     t_max = allred(dt, "MAX")
-    # the opt-in comm-lean PCG beside it (every rank: it has its own exchanges); reported under detail, never as `value`
-    gl = BigLp(P, rank=rank, world=world, device=local_rank, use_torch_stream=True, pcg_mode="lean")
-    gl.solve_init(); gl.solve_iter(0, window)
-    sync()
-    cl0, ll0 = gl.scalar("collectives"), gl.scalar("launches")
-    t0 = time.perf_counter()
-    lean_steps = max(1, min(args.steps, 5))
-    for _ in range(lean_steps):
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, {"x": g.local_x(), "x_sol": g.local_x_sol(), "objective": [g.cal_Obj()],
+                                               "outer_iters": [g.scalar("outer_total")], "pcg_iters": [g.scalar("pcg_total")]})
+    # --full: the opt-in comm-lean PCG beside it (every rank: it has its own exchanges); reported under detail, never as `value`
+    lean = None
+    if args.full:
+        gl = BigLp(P, rank=rank, world=world, device=local_rank, use_torch_stream=True, pcg_mode="lean")
         gl.solve_init(); gl.solve_iter(0, window)
-    sync()
-    lean_t = allred(time.perf_counter() - t0, "MAX") / (lean_steps * window)
-    lean = {"ms_per_iteration": 1e3 * lean_t, "iterations_per_s": 1.0 / lean_t, "pcg_per_outer": gl.scalar("pcg_total") / max(gl.scalar("outer_total"), 1),
-            "launches_per_iteration": (gl.scalar("launches") - ll0) / (lean_steps * max(gl.scalar("outer_total"), 1)),
-            "exchanges_per_outer_iteration": (gl.scalar("collectives") - cl0) / (lean_steps * max(gl.scalar("outer_total"), 1)),
-            "note": "opt-in pcg_mode='lean': p.Mp = dI (p.p) + r4Et (q.q) -- not the reference's arithmetic, outside the parity claim "
-                    "(bit-exact against its own oracle mirror, tests/test_big_gpu_parity.py)"}
-    gl.close()
+        sync()
+        cl0, ll0 = gl.scalar("collectives"), gl.scalar("launches")
+        t0 = time.perf_counter()
+        lean_steps = max(1, min(args.steps, 5))
+        for _ in range(lean_steps):
+            gl.solve_init(); gl.solve_iter(0, window)
+        sync()
+        lean_t = allred(time.perf_counter() - t0, "MAX") / (lean_steps * window)
+        lean = {"ms_per_iteration": 1e3 * lean_t, "iterations_per_s": 1.0 / lean_t, "pcg_per_outer": gl.scalar("pcg_total") / max(gl.scalar("outer_total"), 1),
+                "launches_per_iteration": (gl.scalar("launches") - ll0) / (lean_steps * max(gl.scalar("outer_total"), 1)),
+                "exchanges_per_outer_iteration": (gl.scalar("collectives") - cl0) / (lean_steps * max(gl.scalar("outer_total"), 1)),
+                "note": "opt-in pcg_mode='lean': p.Mp = dI (p.p) + r4Et (q.q) -- not the reference's arithmetic, outside the parity claim "
+                        "(bit-exact against its own oracle mirror, tests/test_big_gpu_parity.py)"}
+        gl.close()
     line = None
     if rank == 0:
         o, p = g.scalar("outer_total"), g.scalar("pcg_total")        # of the last step
@@ -735,10 +779,11 @@ def run_big(args, ctx, cpu_leg=None):
                 "detail": {"pcg_per_outer": K, "ms_per_iteration": 1e3 * s_iter, "backend": backend if world > 1 else None}}
         line["detail"]["launches_per_iteration"] = launches_per_iter
         line["detail"]["folded_reductions"] = bool(g.scalar("folded_reductions"))
-        line["detail"]["comm_lean_pcg"] = lean
-        if world == 1:
+        if lean is not None:
+            line["detail"]["comm_lean_pcg"] = lean
+        if args.full and world == 1:
             line["detail"]["model_8_ranks"] = model_8_ranks(args, n, l, K, s_iter, local_rank)
-        if world == 1 and (args.cpu_sample is None or args.cpu_sample > 0):
+        if args.full and world == 1 and (args.cpu_sample is None or args.cpu_sample > 0):
             from oracle import oracle as O
             s = O.LpOracle(0)
             s.set_problem(P["n"], P["l"], P["colptr"], P["rowidx"], P["b"])

@@ -3,6 +3,8 @@ launch path -- child processes, process group, barriers, the max-over-ranks timi
 no GPU.  It computes nothing; its counters are a fixed function of the instance so the line's totals can be checked."""
 import time
 
+import numpy as np
+
 
 class StubBatch:
     def __init__(self, instances, device=None):
@@ -30,6 +32,9 @@ class StubBatch:
 
     def counters(self, idx=0):
         return 100 + self.insts[idx]["nnz"] % 7, 1500
+
+    def get_x_sol(self, idx=0):
+        return np.full(self.insts[idx]["n"], 0.5)
 
     def cal_obj(self, idx=0):
         return -1.0 - idx

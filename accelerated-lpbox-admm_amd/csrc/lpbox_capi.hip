@@ -99,6 +99,7 @@ struct lpbox_solver {
     bool colsplit = false;
     bool identity_rows = true;   // row storage index == row id (bank-aware placement off)
     bool direct = false;          // opt-in direct x-update (lpbox_set_x_update)
+    int order = LPBOX_ORDER_DEFAULT;   // opt-in reference summation order (lpbox_set_order): own kernels, identity layout
     int HL = 0, HLD = 0;
     size_t lds = 0, lds_direct = 0;
     bool log_on = false; int log_rows = 0; DevBuf<double> logbuf; int log_cap = 0;   // lpbox_set_log: records of the last plain call
@@ -174,8 +175,9 @@ int finalize(lpbox_t *h) {
     // 4-slot variant keeps the vectors the PCG loop never reads out of registers); beyond 2048 positions 4 wavefronts x 8 slots.
     // LPBOX_LP_THREADS overrides (tuning only).
     const int big = std::max(nmax, lmax);
+    const bool ref = h->order == LPBOX_ORDER_REFERENCE;
     int T = 512;                          // 8 waves with short lists beat 4 waves with long ones also at n = 2000 (512 x 4, register-lean variant)
-    if (const char *e = getenv("LPBOX_LP_THREADS")) { int v = atoi(e); if (v == 256 || v == 512 || v == 1024) T = v; }
+    if (const char *e = getenv("LPBOX_LP_THREADS")) { int v = atoi(e); if (!ref && (v == 256 || v == 512 || v == 1024)) T = v; }
     const int max_ept = T == 256 ? 8 : (T == 1024 ? 2 : 4);
     int EPT = 1;
     while (EPT < max_ept && (long)T * EPT < big) EPT *= 2;
@@ -186,7 +188,9 @@ int finalize(lpbox_t *h) {
     h->T = T; h->EPT = EPT;
     h->NS = T * EPT;                       // storage positions / row-task slots per instance
     h->LS = (lmax + 31) & ~31; h->ZS = (zmax + 7) & ~7;     // LS: a whole number of 32-row bank classes
-    h->lds = lp_window_lds_bytes(T, h->NS, h->LS, h->ZS);
+    h->lds = ref ? lp_ref_lds_bytes(h->NS, h->LS, h->ZS) : lp_window_lds_bytes(T, h->NS, h->LS, h->ZS);
+    if (ref && !lp_ref_supported(T, EPT))
+        return fail(LPBOX_E_TOOLARGE, "reference order: instance with max(n,l)=%d exceeds the on-chip kernel (%d threads x %d slots)", big, T, EPT);
     if (h->lds > 160 * 1024) return fail(LPBOX_E_TOOLARGE, "instance needs %zu B of LDS (> 160 KiB per CU)", h->lds);
 
     if (!h->stream) HIPCHK(hipStreamCreate(&h->stream));
@@ -228,6 +232,34 @@ int finalize(lpbox_t *h) {
     const bool noconflict = getenv("LPBOX_LP_NOCONFLICT") != nullptr || !(ba ? atoi(ba) != 0 : h->EPT >= 4);
     for (size_t i = 0; i < B; i++) {
         LpInstance &I = h->inst[i];
+        if (ref) {
+            // reference order (lp_ref_window_kernel): variable j at position j, row i at row slot i, one lane per row, whole columns;
+            // rs_ptr / rs_col = CSR of E (columns ascending), cs_ptr / cs_row = CSC (rows ascending)
+            I.cpos.resize(I.n); I.cperm.resize(I.n);
+            for (int j = 0; j < I.n; j++) { I.cpos[j] = j; I.cperm[j] = j; }
+            I.rowG.assign(I.l, 1);
+            I.col_own.resize(I.n);
+            for (int j = 0; j < I.n; j++) I.col_own[j] = I.colptr[j + 1] - I.colptr[j];
+            I.col_help.assign((size_t)4 * I.n, 0);
+            I.help_of_pos.clear();
+            for (size_t p = 0; p <= NS; p++) {
+                const int jj = std::min((int)p, I.n), rr = std::min((int)p, I.l);
+                h_cs_ptr[i * (NS + 1) + p] = I.colptr[jj];
+                h_rs_ptr[i * (NS + 1) + p] = I.rowptr[rr];
+                h_hs_ptr[i * (NS + 1) + p] = I.nnz;
+            }
+            for (int k = 0; k < I.nnz; k++) { h_cs_row[i * ZS + k] = (uint16_t)I.rowidx[k]; h_rs_col[i * ZS + k] = (uint16_t)I.colidx[k]; }
+            for (int j = 0; j < I.n; j++) {
+                h_b[i * NS + j] = I.b[j];
+                h_live[i * NS + j] = 1;
+                h_cmeta[i * NS + j] = (uint16_t)I.col_own[j];
+            }
+            for (int r = 0; r < I.l; r++) { h_rid[i * NS + r] = (uint16_t)r; h_rgl[i * NS + r] = (uint16_t)r; h_f[i * LS + r] = I.f_org[r]; }
+            h_isc[i * NI_COUNT + NI_N] = I.n; h_isc[i * NI_COUNT + NI_L] = I.l; h_isc[i * NI_COUNT + NI_NNZ] = I.nnz;
+            h_isc[i * NI_COUNT + NI_ACTIVE] = 1;
+            h_c1[i] = std::pow((double)I.n, 1.0 / 2);     // std::pow(n, 1.0/p), p = projection_lp = 2 (LPcpp:427,503)
+            continue;
+        }
         // ---- rows: G lanes share a row so that no lane walks more than ~L entries; lane g takes entries g, g+G, ... ----
         I.rowG.assign(I.l, 1);
         if (!nosplit) {
@@ -538,7 +570,8 @@ int run_window(lpbox_t *h, int iter_start, int iter_end, int l2f, bool log = fal
     HIPCHK(hipEventRecord(h->ev0, h->stream));
     LpBatchDev bd = h->dev();
     if (log) { bd.logbuf = h->logbuf.p; bd.log_cap = h->log_cap; }
-    HIPCHK(lp_launch_window(bd, h->T, h->EPT, h->direct ? h->lds_direct : h->lds, iter_start, iter_end, l2f, h->stream, h->direct, log));
+    if (h->order == LPBOX_ORDER_REFERENCE) HIPCHK(lp_ref_launch_window(bd, h->EPT, h->lds, iter_start, iter_end, l2f, h->stream));
+    else HIPCHK(lp_launch_window(bd, h->T, h->EPT, h->direct ? h->lds_direct : h->lds, iter_start, iter_end, l2f, h->stream, h->direct, log));
     HIPCHK(hipEventRecord(h->ev1, h->stream));
     int rc = refresh_scalars(h);     // synchronises the stream
     if (rc) return rc;
@@ -735,7 +768,8 @@ int lpbox_init(lpbox_t *h) {
     }
     h->xi_valid = false;
     HIPCHK(hipMemsetAsync(h->ctl.p, 0, (size_t)h->B * 4 * sizeof(int), h->stream));
-    HIPCHK(lp_launch_init(h->dev(), h->T, h->EPT, h->f_org.p, h->c1_init.p, h->live_init.p, h->stream));
+    if (h->order == LPBOX_ORDER_REFERENCE) HIPCHK(lp_ref_launch_init(h->dev(), h->lds, h->f_org.p, h->c1_init.p, h->live_init.p, h->stream));
+    else HIPCHK(lp_launch_init(h->dev(), h->T, h->EPT, h->f_org.p, h->c1_init.p, h->live_init.p, h->stream));
     rc = refresh_scalars(h);
     if (rc) return rc;
     h->inited = true;
@@ -887,6 +921,7 @@ int lpbox_set_x_update(lpbox_t *h, int mode) {
     if (!valid_handle(h)) return fail(LPBOX_E_BADHANDLE, "bad handle");
     if (mode != LPBOX_XUPDATE_PCG && mode != LPBOX_XUPDATE_DIRECT) return fail(LPBOX_E_BADARG, "x-update mode %d", mode);
     if (mode == LPBOX_XUPDATE_PCG) { h->direct = false; return LPBOX_OK; }
+    if (h->order == LPBOX_ORDER_REFERENCE) return fail(LPBOX_E_UNSUPPORTED, "the direct x-update has no reference-order variant (lpbox_set_order)");
     int rc = finalize(h);              // the geometry decides whether the dense inverse fits
     if (rc) return rc;
     rc = use_device(h);
@@ -954,8 +989,22 @@ int lpbox_set_record(lpbox_t *h, int on) {
 int lpbox_set_log(lpbox_t *h, int on) {
     if (!valid_handle(h)) return fail(LPBOX_E_BADHANDLE, "bad handle");
     if (h->seg) return fail(LPBOX_E_UNSUPPORTED, "the segmentation solver of the reference writes no iteration log (SEGh:225)");
+    if (on && h->order == LPBOX_ORDER_REFERENCE) return fail(LPBOX_E_UNSUPPORTED, "the iteration log has no reference-order variant (lpbox_set_order)");
     h->log_on = on != 0;
     if (!h->log_on) h->log_rows = 0;
+    return LPBOX_OK;
+}
+
+// Summation order of the on-chip kernels.  The layout is built when the problem is uploaded, so the order is
+// chosen before that.
+int lpbox_set_order(lpbox_t *h, int mode) {
+    if (valid_handle(h) && h->seg) return fail(LPBOX_E_STATE, "this entry point belongs to the LP flavour");
+    if (!valid_handle(h)) return fail(LPBOX_E_BADHANDLE, "bad handle");
+    if (mode != LPBOX_ORDER_DEFAULT && mode != LPBOX_ORDER_REFERENCE) return fail(LPBOX_E_BADARG, "summation order %d", mode);
+    if (mode == LPBOX_ORDER_REFERENCE && h->direct) return fail(LPBOX_E_UNSUPPORTED, "the direct x-update has no reference-order variant");
+    if (mode == LPBOX_ORDER_REFERENCE && h->log_on) return fail(LPBOX_E_UNSUPPORTED, "the iteration log has no reference-order variant");
+    if (h->finalized) return fail(LPBOX_E_STATE, "problem already uploaded; choose the summation order before lpbox_init");
+    h->order = mode;
     return LPBOX_OK;
 }
 

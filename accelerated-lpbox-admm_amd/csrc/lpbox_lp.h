@@ -88,5 +88,11 @@ hipError_t lp_launch_window(const LpBatchDev &bd, int T, int EPT, size_t lds, in
                             hipStream_t s, bool direct = false, bool log = false);
 bool lp_log_supported(int T, int EPT);         // geometries the logging variant is compiled for (the default ones: 512 threads)
 bool lp_direct_supported(int T, int EPT);      // geometries the DIRECT variant is compiled for
+// opt-in reference-order kernels (lpbox_lp_ref_kernels.hip, lpbox_set_order): identity layout, 512 threads, EPT = 1, 2 or 4
+size_t lp_ref_lds_bytes(int NS, int LS, int ZS);
+bool lp_ref_supported(int T, int EPT);
+hipError_t lp_ref_launch_init(const LpBatchDev &bd, size_t lds, const double *f_org, const double *c1_init, const uint8_t *live_init,
+                              hipStream_t s);
+hipError_t lp_ref_launch_window(const LpBatchDev &bd, int EPT, size_t lds, int iter_start, int iter_end, int mode, hipStream_t s);
 hipError_t lp_launch_pack_xiters(const LpBatchDev &bd, const int *live_pos, const int *rows, int ws, double *out,
                                  long out_stride, hipStream_t s);

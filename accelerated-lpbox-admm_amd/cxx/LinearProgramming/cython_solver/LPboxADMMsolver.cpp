@@ -39,6 +39,7 @@ struct LPboxADMMsolver::State {
     int org_n = 0, l = 0;
     std::vector<double> xiters, xsol, xfinal, x_prev;
     bool does_log = false;
+    int order = LPBOX_ORDER_DEFAULT;  // summation order of the on-chip kernels (set_order); kept across new problems
     ~State() { if (big) lpbox_big_destroy(big); if (h) lpbox_destroy(h); }
     std::string data_root() const {
         if (!root.empty()) return root;
@@ -50,6 +51,7 @@ struct LPboxADMMsolver::State {
         if (h) { lpbox_destroy(h); h = nullptr; }
         h = lpbox_create(LPBOX_FLAVOUR_LP, 1, print_info);
         if (!h) lpbox_throw("lpbox_create");
+        if (order != LPBOX_ORDER_DEFAULT) lpbox_ok(lpbox_set_order(h, order), "lpbox_set_order");
         x_prev.clear();
     }
     double scalar(const char *name) {
@@ -95,6 +97,13 @@ inline void LPboxADMMsolver::set_fix_threshold(double t) { s_->fix_threshold = t
 inline void LPboxADMMsolver::set_consistency(int c) { s_->consistency = c; }
 inline void LPboxADMMsolver::set_data_root(const std::string &root) { s_->root = root; }
 inline bool LPboxADMMsolver::on_large_path() const { return s_->big != nullptr; }
+// the opt-in reference summation order; an instance beyond the on-chip kernel then throws at ADMM_lp_iters_init
+// instead of moving to the large-instance path, which sums in an order of its own
+inline void LPboxADMMsolver::set_order(int mode) {
+    if (!s_->h) s_->fresh();
+    lpbox_ok(lpbox_set_order(s_->h, mode), "lpbox_set_order");
+    s_->order = mode;
+}
 inline int LPboxADMMsolver::get_org_n() { return s_->org_n; }
 
 inline void LPboxADMMsolver::readFile(int i, int k, int j) {
@@ -117,10 +126,10 @@ inline int LPboxADMMsolver::ADMM_lp_iters_init() {
         lpbox_ok(lpbox_get_problem_lp(s.h, 0, &n, &l, &nnz, nullptr, nullptr, nullptr, nullptr), "lpbox_get_problem_lp");
         s.org_n = n; s.l = l;
         bool fits = std::max(n, l) <= LPBOX_ONCHIP_MAX;
-        if (fits) {
+        if (fits || s.order == LPBOX_ORDER_REFERENCE) {
             const int rc = lpbox_init(s.h);
             if (rc >= 0) return rc;
-            if (rc != LPBOX_E_TOOLARGE) lpbox_throw("lpbox_init");
+            if (rc != LPBOX_E_TOOLARGE || s.order == LPBOX_ORDER_REFERENCE) lpbox_throw("lpbox_init");
         }
         // does not fit one CU: the same algorithm on the large-instance path, one rank
         std::vector<int> colptr((size_t)n + 1), rowidx((size_t)std::max(nnz, 1));

@@ -52,6 +52,7 @@ public:
     bool on_large_path() const;
     long long outer_iterations();                             // lpbox_get_counters
     int stop_reason(int *plain_iter_plus1 = nullptr);         // lpbox_get_stop: 0 none, 1 y1_y2, 2 obj_std, 3 PCG alpha < 0, 4 all fixed
+    void set_order(int mode);                                 // lpbox_set_order: LPBOX_ORDER_DEFAULT / LPBOX_ORDER_REFERENCE, before ADMM_lp_iters_init
 
 private:
     struct State;

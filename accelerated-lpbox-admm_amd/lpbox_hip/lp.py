@@ -33,6 +33,8 @@ class LpBatch:
     LPcpp:2520) and optionally f (default ones, LPcpp:2522).
     """
 
+    order = "default"        # summation order of the kernels (set_order)
+
     def __init__(self, instances=None, print_info=0, device=None, batch=None):
         self._L = _lib.load()
         if device is not None:
@@ -120,6 +122,17 @@ class LpBatch:
         if mode not in ("pcg", "direct"):
             raise ValueError("x-update mode must be 'pcg' or 'direct'")
         check(self._L.lpbox_set_x_update(self._h, 1 if mode == "direct" else 0), "lpbox_set_x_update")
+
+    def set_order(self, mode="default"):
+        """Summation order of the kernels, chosen before solve_init.  "default" is the tuned layout (bit-exact against the oracle in the
+        kernels' own association).  "reference" is an opt-in that sums every dot product / norm in the order of the reference's Eigen
+        path and every sparse product row by row / column by column in ascending index order: the reference's
+        iterates and binary solutions, except that the std stop test takes sqrt where the reference calls pow(v, 1/2).  Not combinable
+        with the direct x-update or the iteration log; max(n, l) <= 2048 (solve_init raises otherwise)."""
+        if mode not in ("default", "reference"):
+            raise ValueError("summation order must be 'default' or 'reference'")
+        check(self._L.lpbox_set_order(self._h, 1 if mode == "reference" else 0), "lpbox_set_order")
+        self.order = mode
 
     def direct_rows(self, idx=0):
         """Row split of the direct x-update (lpbox_get_direct_rows): dense index per row of E, -1 = closed-form row."""
@@ -390,7 +403,16 @@ class PyLPboxADMMsolver:
         if not isinstance(self._b, LpBatch):
             self._b.close()
             self._b = LpBatch(batch=1, print_info=self.print_info)
+            if self.order != "default":
+                self._b.set_order(self.order)
         return self._b
+
+    order = "default"
+
+    # not in the pyx: the opt-in reference summation order (LpBatch.set_order), chosen before solve_init
+    def set_order(self, mode="default"):
+        self._small().set_order(mode)
+        self.order = mode
 
     # LP pyx:16-17
     def read_File(self, i, k, j):
@@ -411,6 +433,12 @@ class PyLPboxADMMsolver:
         if isinstance(self._b, LpBatch):
             P = self._b.get_problem(0)
             fits = max(P["n"], P["l"]) <= ONCHIP_MAX
+            if self.order == "reference":                  # the large-instance path sums in its own order: refuse rather than switch
+                if not fits:
+                    err = LpboxError("reference summation order: max(n, l) = %d exceeds the on-chip kernel's %d" % (max(P["n"], P["l"]), ONCHIP_MAX))
+                    err.code = E_TOOLARGE
+                    raise err
+                return self._b.solve_init()
             if fits:
                 try:
                     return self._b.solve_init()

@@ -103,6 +103,17 @@ int lpbox_set_record(lpbox_t *h, int on);
 #define LPBOX_XUPDATE_PCG 0
 #define LPBOX_XUPDATE_DIRECT 1
 int lpbox_set_x_update(lpbox_t *h, int mode);
+/* LP flavour, OPT-IN: the summation order of the on-chip kernels.  LPBOX_ORDER_DEFAULT (default) = the tuned layout, bit-exact against the
+ * oracle run in the kernels' own association.  LPBOX_ORDER_REFERENCE = every dot product / norm over the live variables in the order of
+ * Eigen 3.3.8's SSE2 redux, every row of E v and column of E^T w summed sequentially in ascending index order:
+ * the same iterates, binary solution and iteration counts as the reference's Eigen path, except that the std stop test takes sqrt where
+ * the reference calls pow(v, 1/2).  Only before the problem is uploaded (LPBOX_E_STATE after lpbox_init / lpbox_get_config / ...);
+ * LPBOX_E_UNSUPPORTED together with the direct x-update or the iteration log (either call order).  An instance beyond the on-chip
+ * limit makes lpbox_init fail with LPBOX_E_TOOLARGE.  lpbox_get_layout / _row_split / _col_split then report the identity layout,
+ * one lane per row and whole columns. */
+#define LPBOX_ORDER_DEFAULT 0
+#define LPBOX_ORDER_REFERENCE 1
+int lpbox_set_order(lpbox_t *h, int mode);
 /* The row split of the direct mode for instance idx (the order of its arithmetic; tests hand it to the oracle's mirror): gidx_of_row[l] =
  * dense index of the row among the rows solved through the on-chip inverse, -1 for a row handled in closed form (its columns meet no
  * other such row).  Returns the number of dense rows. */

@@ -150,7 +150,7 @@ __global__ void __launch_bounds__(T) gen_k_prep(GenDev d, int in, int out, int d
                 if ((it + 1) % P.rho_change_step == 0) {                                                     // :1753-1770
                     s->prev_rho1 = s->rho1; s->prev_rho2 = s->rho2;
                     s->rho1 = P.learning_fact * s->rho1; s->rho2 = P.learning_fact * s->rho2;
-                    if (d.eq) { s->prev_rho3 = s->rho3; s->rho3 = P.learning_fact * s->rho3; }
+                    if (d.eq && d.ineq) { s->prev_rho3 = s->rho3; s->rho3 = P.learning_fact * s->rho3; }   // update_rho3: type 3 only (:1906, :2045)
                     if (d.ineq) { s->prev_rho4 = s->rho4; s->rho4 = P.learning_fact * s->rho4; }
                     const double g = s->gamma_val * P.gamma_factor;
                     s->gamma_val = g < 1.0 ? 1.0 : g;
@@ -224,7 +224,7 @@ __global__ void __launch_bounds__(T) gen_k_y(GenDev d, int in, int out) {
             if (refresh) {
                 d.tmval[d.adiag[j]] += inc;                                      // :1623
                 if (type != 0) pd += inc;                                        // :1626
-                if (d.eq) pd += s3 * d.Csq[j];                                   // :1641
+                if (d.eq && d.ineq) pd += s3 * d.Csq[j];                         // :1629-1632, update_rho3 only
                 if (d.ineq) pd += s4 * d.Esq[j];                                 // :1646
                 d.pdiag[j] = pd;
             }
@@ -237,7 +237,7 @@ __global__ void __launch_bounds__(T) gen_k_y(GenDev d, int in, int out) {
         }
     if (refresh) {                                                                // the scaled transposes (:1643, :1648)
         const long stride = (long)gridDim.x * T;
-        if (d.eq) for (long k = (long)blockIdx.x * T + threadIdx.x; k < d.Cnnz; k += stride) d.Cc_sv[k] = P.learning_fact * d.Cc_sv[k];
+        if (d.eq && d.ineq) for (long k = (long)blockIdx.x * T + threadIdx.x; k < d.Cnnz; k += stride) d.Cc_sv[k] = P.learning_fact * d.Cc_sv[k];
         if (d.ineq) for (long k = (long)blockIdx.x * T + threadIdx.x; k < d.Ennz; k += stride) d.Ec_sv[k] = P.learning_fact * d.Ec_sv[k];
     }
     if (d.ineq && blockIdx.x < d.Gl)

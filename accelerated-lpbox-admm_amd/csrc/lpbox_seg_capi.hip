@@ -703,7 +703,7 @@ int segc_debug_scalar(SegSolver *s, const char *name, double *out) {
     struct { const char *n; double v; } tab[] = {
         {"rho1", h.rho1}, {"gamma", h.gamma_val}, {"cur_obj", h.cur_obj}, {"std_obj", h.std_obj}, {"cvg1", h.cvg1}, {"cvg2", h.cvg2},
         {"obj_val", h.obj_val}, {"best_bin_obj", h.best_bin_obj}, {"c", s->c}, {"last_pcg", (double)h.last_pcg}, {"iter", (double)h.iter},
-        {"matrix_as_diagonals", s->dia ? 1.0 : 0.0},
+        {"matrix_as_diagonals", s->dia ? 1.0 : 0.0}, {"ell_width", (double)s->ell_w},
     };
     for (auto &e : tab) if (!strcmp(e.n, name)) { *out = e.v; return LPBOX_OK; }
     return lpbox_fail(LPBOX_E_BADARG, "unknown scalar '%s'", name);

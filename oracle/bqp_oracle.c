@@ -353,7 +353,7 @@ int bqpo_solve(bqpo_t *o) {                    /* ADMM_bqp SEGcpp:1384-1832 */
             for (int i = 0; i < n; i++)
                 for (int k = o->tm.ptr[i]; k < o->tm.ptr[i + 1]; k++) if (o->tm.idx[k] == i) o->tm.val[k] += inc;
             if (o->type != 0) for (int i = 0; i < n; i++) o->pdiag[i] += inc;
-            if (eq) {
+            if (eq && ineq) {                                                            /* update_rho3: type 3 only (:1906, :2045) */
                 for (int i = 0; i < n; i++) o->pdiag[i] += rcr * prev_rho3 * o->Csq[i];
                 for (int k = 0; k < o->r3Ct.nnz; k++) o->r3Ct.val[k] = o->learning_fact * o->r3Ct.val[k];
             }
@@ -412,7 +412,7 @@ int bqpo_solve(bqpo_t *o) {                    /* ADMM_bqp SEGcpp:1384-1832 */
         if ((iter + 1) % o->rho_change_step == 0) {                                      /* :1753-1770 */
             prev_rho1 = rho1; prev_rho2 = rho2;
             rho1 = o->learning_fact * rho1; rho2 = o->learning_fact * rho2;
-            if (eq) { prev_rho3 = rho3; rho3 = o->learning_fact * rho3; }
+            if (eq && ineq) { prev_rho3 = rho3; rho3 = o->learning_fact * rho3; }
             if (ineq) { prev_rho4 = rho4; rho4 = o->learning_fact * rho4; }
             const double g = o->gamma_val * o->gamma_factor;
             o->gamma_val = g < 1.0 ? 1.0 : g;

@@ -227,3 +227,160 @@ def oracle_iters_fix(o, i, j, x_prev=None, consistency=5, fix_threshold=1e-3, mi
             ret = 1
             break
     return ret, prev
+
+
+# ------------------------------------------------------------------------------------------------
+# Comparisons with the independent numpy restatement (oracle/bqp_numpy.py) and the problems they run on.
+# ------------------------------------------------------------------------------------------------
+BQP_VECS = ("x", "y1", "y2", "z1", "z2", "best_sol", "z3", "z4", "y3")
+BQP_SCALARS = ("rho1", "rho3", "rho4", "gamma", "std_obj", "cvg1", "cvg2", "best_bin_obj", "obj_val", "cur_obj")
+
+
+def spread_bound(e, g):
+    """Tolerance B against the restatement: 10 x the oracle's own Eigen-order vs GPU-order spread, plus 1e-12 max(1, |v|)."""
+    e, g = np.atleast_1d(np.asarray(e, float)), np.atleast_1d(np.asarray(g, float))
+    return 10 * np.abs(e - g).max(initial=0.0) + 1e-12 * max(1.0, np.abs(e).max(initial=0.0))
+
+
+def assert_within_bound(got, ref, e, g, tag):
+    got, ref = np.atleast_1d(np.asarray(got, float)), np.atleast_1d(np.asarray(ref, float))
+    assert got.shape == ref.shape, f"{tag}: shape {got.shape} vs {ref.shape}"
+    d = np.abs(got - ref).max(initial=0.0)
+    B = spread_bound(e, g)
+    assert d <= B, f"{tag}: |got - restatement| = {d:.3e} > B = {B:.3e}"
+
+
+def common_prefix(*traces):
+    k = min(len(t) for t in traces)
+    for i in range(k):
+        if len({int(t[i]) for t in traces}) != 1:
+            return i
+    return k
+
+
+def bqp_params(ptype, K, rho_change_step=3):
+    """The type's preset hyper-parameters (bqp_numpy.PRESETS) cut to K iterations, with a shorter rho schedule so that a short
+    prefix holds rho / gamma updates."""
+    from oracle.bqp_numpy import PRESETS
+    p = list(PRESETS[ptype])
+    p[4], p[5] = rho_change_step, K
+    return p
+
+
+def _csr_dense(M):
+    rp, ci, va = [0], [], []
+    for i in range(M.shape[0]):
+        nz = np.nonzero(M[i])[0]
+        ci += list(nz); va += list(M[i, nz])
+        rp.append(len(ci))
+    return np.array(rp, np.int32), np.array(ci, np.int32), np.array(va, np.float64)
+
+
+def _constraint_rows(rows, n, rs, skip_col):
+    """rows x n with row lengths 1, 2, 3, ... mod 4 (row 0 empty), non-unit values of both signs, column `skip_col` empty."""
+    M = np.zeros((rows, n))
+    cols = np.array([j for j in range(n) if j != skip_col]) if n > 1 else np.arange(n)
+    for i in range(rows):
+        if i == 0 and rows > 1:
+            continue
+        k = min(len(cols), 1 + (i % 7))
+        pick = rs.choice(cols, k, replace=False)
+        M[i, pick] = rs.uniform(0.3, 1.7, k) * np.where(rs.rand(k) < 0.25, -1.0, 1.0)
+    return M
+
+
+def bqp_problem(n, m=0, l=0, seed=0, offdiag=True, indefinite=False):
+    """A generic constrained BQP for lpbox_hip.bqp / BqpOracle / NumpyBqp: A symmetric with every diagonal stored (off-diagonals of
+    both signs, or none), C (m x n) and E (l x n) with an empty row and an empty column once they have more than one row, d = C xb
+    and f = E xb + slack for a binary xb (feasible), x0 inside the box.  indefinite: A's diagonal made negative enough that
+    2A + (rho1 + rho2) I is indefinite at the starting rho of the eq / both presets."""
+    rs = np.random.RandomState(seed)
+    A = np.zeros((n, n))
+    if offdiag and n > 1:
+        for _ in range(2 * n):
+            i, j = rs.randint(n), rs.randint(n)
+            if i != j:
+                v = rs.uniform(-1, 1)
+                A[i, j] += v; A[j, i] += v
+    dg = np.abs(A).sum(axis=1) + rs.uniform(0.5, 2.0, n)
+    if indefinite:
+        dg = dg.copy()
+        dg[: max(1, n // 8)] = -np.abs(A[: max(1, n // 8)]).sum(axis=1) - 40.0
+    A[np.arange(n), np.arange(n)] = dg
+    xb = (rs.rand(n) < 0.4).astype(float)
+    P = dict(n=n, A=_csr_dense(A), b=rs.uniform(-2, 1, n), x0=rs.uniform(0.2, 0.8, n))
+    skip = n - 1
+    if m:
+        Cm = _constraint_rows(m, n, rs, skip)
+        P["C"], P["d"] = _csr_dense(Cm), Cm @ xb
+    if l:
+        Em = _constraint_rows(l, n, rs, skip)
+        P["E"], P["f"] = _csr_dense(Em), Em @ xb + rs.uniform(0.0, 1.0, l)
+    # a zero diagonal must still be stored (lpbox_bqp_set_problem): _csr_dense keeps only nonzeros, so put it back
+    from lpbox_hip.bqp import with_diagonal
+    P["A"] = with_diagonal(*P["A"], n)
+    return P
+
+
+def laplacian_seg_problem(n, width, seed=0):
+    """A segmentation-flavour problem P (for PyLPboxADMMsolver.set_problem / SegOracle / NumpySeg) that is no image: A = D - W, a
+    weighted graph Laplacian with non-integer weights (so 2A + rho I is positive definite), built on a chain (rows of 3 entries) plus
+    hub rows whose extra neighbours are disjoint: the longest row holds exactly `width` entries (width >= 4), every other row at
+    most 4.  b: non-integer costs of both signs."""
+    rs = np.random.RandomState(seed)
+    W = {}
+    for i in range(n - 1):
+        W[(i, i + 1)] = rs.uniform(0.2, 1.5)
+    hubs = max(1, min(4, n // (2 * width)))
+    pool = list(rs.permutation([i for i in range(n) if i % (n // hubs) != 0]))
+    for h in range(hubs):
+        hub = h * (n // hubs)
+        have = {hub - 1, hub + 1} & set(range(n))
+        extra = width - 1 - len(have)
+        for j in [pool.pop() for _ in range(extra)]:
+            W[(min(hub, j), max(hub, j))] = W.get((min(hub, j), max(hub, j)), 0.0) + rs.uniform(0.2, 1.5)
+    rows = [dict() for _ in range(n)]
+    for (i, j), w in W.items():
+        rows[i][j] = rows[i].get(j, 0.0) - w
+        rows[j][i] = rows[j].get(i, 0.0) - w
+    rp, ci, va = [0], [], []
+    for i in range(n):
+        rows[i][i] = -sum(rows[i].values())
+        for j in sorted(rows[i]):
+            ci.append(j); va.append(rows[i][j])
+        rp.append(len(ci))
+    return dict(n=n, rowptr=np.array(rp, np.int32), colidx=np.array(ci, np.int32), vals=np.array(va), b=rs.uniform(-3, 3, n).round(3),
+                c=0.0, rows=1, cols=n)
+
+
+def banded_seg_problem(n, seed=0, fourth_offset=False):
+    """Offsets +-1, +-2, +-3 with small integer weights (the shape lpbox_seg holds as diagonals, rows of at most 7 entries); with
+    fourth_offset, one more symmetric pair (0, n-1): a fourth distinct offset on each side, so the matrix must stay in ELL."""
+    rs = np.random.RandomState(seed)
+    M = {}
+    for i in range(n):
+        for o in (1, 2, 3):
+            if i + o < n:
+                M[(i, i + o)] = float(rs.randint(0, 6))
+    if fourth_offset:
+        M[(0, n - 1)] = 2.0
+    rows = [dict() for _ in range(n)]
+    for (i, j), w in M.items():
+        rows[i][j] = -w
+        rows[j][i] = -w
+    rp, ci, va = [0], [], []
+    for i in range(n):
+        rows[i][i] = -sum(rows[i].values())
+        for j in sorted(rows[i]):
+            ci.append(j); va.append(rows[i][j])
+        rp.append(len(ci))
+    return dict(n=n, rowptr=np.array(rp, np.int32), colidx=np.array(ci, np.int32), vals=np.array(va),
+                b=rs.randint(-40, 40, n).astype(float), c=0.0, rows=1, cols=n)
+
+
+def synthetic_gray(rows, cols, seed=0):
+    """A blocky grayscale image with noise (uint8), fast at any size."""
+    rs = np.random.RandomState(seed)
+    coarse = rs.rand(rows // 24 + 2, cols // 24 + 2)
+    img = np.kron(coarse, np.ones((24, 24)))[:rows, :cols] * 200 + 55 * rs.rand(rows, cols)
+    return np.floor(img).astype(np.uint8)

@@ -56,6 +56,7 @@ struct LpInstance {
     int n = 0, l = 0, nnz = 0;
     std::vector<int> colptr, rowidx;   // CSC of E, as read (LPcpp:2416-2444)
     std::vector<int> rowptr, colidx;   // CSR of the same matrix
+    std::vector<double> vals, vals_csr; // stored values in CSC / CSR entry order; empty = every entry is 1.0 (a unit instance)
     std::vector<int> cpos, cperm;      // storage layout: variable j sits at position cpos[j]; cperm[pos] = j
     std::vector<int> rowG;             // lanes that share the sum of row r (1,2,4,8)
     std::vector<int> col_own;          // entries of column j summed by its own lane (= its length unless the column is split)
@@ -100,6 +101,8 @@ struct lpbox_solver {
     bool identity_rows = true;   // row storage index == row id (bank-aware placement off)
     bool direct = false;          // opt-in direct x-update (lpbox_set_x_update)
     int order = LPBOX_ORDER_DEFAULT;   // opt-in reference summation order (lpbox_set_order): own kernels, identity layout
+    bool valued = false, vals_in_lds = false;   // reference order only: some instance stores a value other than 1.0
+    DevBuf<double> vr, vc, r4v;        // ... then the values in CSR / CSC entry order and the entries of rho4_E_transpose, ZS per instance
     int HL = 0, HLD = 0;
     size_t lds = 0, lds_direct = 0;
     bool log_on = false; int log_rows = 0; DevBuf<double> logbuf; int log_cap = 0;   // lpbox_set_log: records of the last plain call
@@ -132,6 +135,11 @@ struct lpbox_solver {
         d.ctl = ctl.p; d.dctl = dctl.p; d.xhist = xhist.p; d.ws_cap = ws_cap; d.logbuf = nullptr; d.log_cap = 0; d.stamps = stamps.p; d.stamp_wave = getenv("LPBOX_STAMP_WAVE") ? atoi(getenv("LPBOX_STAMP_WAVE")) : 0;
         d.H = direct ? Hinv.p : nullptr; d.HL = direct ? HL : 0; d.HLD = direct ? HLD : 0; d.rdir = rdir.p; d.dng = dng.p;
         return d;
+    }
+    LpRefVals ref_vals() const {
+        LpRefVals v;
+        v.vr = valued ? vr.p : nullptr; v.vc = valued ? vc.p : nullptr; v.r4v = valued ? r4v.p : nullptr; v.in_lds = vals_in_lds ? 1 : 0;
+        return v;
     }
 };
 
@@ -188,9 +196,21 @@ int finalize(lpbox_t *h) {
     h->T = T; h->EPT = EPT;
     h->NS = T * EPT;                       // storage positions / row-task slots per instance
     h->LS = (lmax + 31) & ~31; h->ZS = (zmax + 7) & ~7;     // LS: a whole number of 32-row bank classes
+    h->valued = false;
+    for (auto &I : h->inst) h->valued = h->valued || !I.vals.empty();
+    if (h->valued && !ref) return fail(LPBOX_E_UNSUPPORTED, "E has stored values != 1; only the reference order carries them (lpbox_set_order)");
     h->lds = ref ? lp_ref_lds_bytes(h->NS, h->LS, h->ZS) : lp_window_lds_bytes(T, h->NS, h->LS, h->ZS);
     if (ref && !lp_ref_supported(T, EPT))
         return fail(LPBOX_E_TOOLARGE, "reference order: instance with max(n,l)=%d exceeds the on-chip kernel (%d threads x %d slots)", big, T, EPT);
+    h->vals_in_lds = false;
+    if (h->valued) {
+        // the values (CSR order, CSC order) and rho4_E_transpose sit in LDS where they fit next to the index sets, else in global memory;
+        // LPBOX_LP_REF_VALS=global / =lds overrides (tuning and tests only; lds fails below when it does not fit)
+        const size_t with_vals = lp_ref_lds_bytes(h->NS, h->LS, h->ZS, true);
+        const char *e = getenv("LPBOX_LP_REF_VALS");
+        h->vals_in_lds = e ? !strcmp(e, "lds") : with_vals <= 160 * 1024;
+        if (h->vals_in_lds) h->lds = with_vals;
+    }
     if (h->lds > 160 * 1024) return fail(LPBOX_E_TOOLARGE, "instance needs %zu B of LDS (> 160 KiB per CU)", h->lds);
 
     if (!h->stream) HIPCHK(hipStreamCreate(&h->stream));
@@ -206,6 +226,20 @@ int finalize(lpbox_t *h) {
     HIPCHK(h->dsc.alloc(B * ND_COUNT)); HIPCHK(h->isc.alloc(B * NI_COUNT)); HIPCHK(h->hist.alloc(B * LP_HIST));
     HIPCHK(h->ctl.alloc(B * 4)); HIPCHK(h->dctl.alloc(B)); HIPCHK(h->c1_init.alloc(B));
     HIPCHK(h->left_idx.alloc(B * NS)); HIPCHK(h->xi_rows.alloc(B));
+    if (h->valued) {
+        HIPCHK(h->vr.alloc(B * ZS)); HIPCHK(h->vc.alloc(B * ZS)); HIPCHK(h->r4v.alloc(B * ZS));
+        std::vector<double> h_vr(B * ZS, 0.0), h_vc(B * ZS, 0.0);
+        for (size_t i = 0; i < B; i++) {
+            const LpInstance &I = h->inst[i];
+            for (int k = 0; k < I.nnz; k++) {
+                h_vr[i * ZS + k] = I.vals.empty() ? 1.0 : I.vals_csr[k];
+                h_vc[i * ZS + k] = I.vals.empty() ? 1.0 : I.vals[k];
+            }
+        }
+        HIPCHK(hipMemcpy(h->vr.p, h_vr.data(), h_vr.size() * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(h->vc.p, h_vc.data(), h_vc.size() * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(hipMemset(h->r4v.p, 0, B * ZS * sizeof(double)));
+    }
 #ifdef LPBOX_STAMPS
     HIPCHK(h->stamps.alloc(B * 16)); HIPCHK(hipMemset(h->stamps.p, 0, B * 16 * sizeof(unsigned long long)));
 #endif
@@ -570,7 +604,7 @@ int run_window(lpbox_t *h, int iter_start, int iter_end, int l2f, bool log = fal
     HIPCHK(hipEventRecord(h->ev0, h->stream));
     LpBatchDev bd = h->dev();
     if (log) { bd.logbuf = h->logbuf.p; bd.log_cap = h->log_cap; }
-    if (h->order == LPBOX_ORDER_REFERENCE) HIPCHK(lp_ref_launch_window(bd, h->EPT, h->lds, iter_start, iter_end, l2f, h->stream));
+    if (h->order == LPBOX_ORDER_REFERENCE) HIPCHK(lp_ref_launch_window(bd, h->ref_vals(), h->EPT, h->lds, iter_start, iter_end, l2f, h->stream));
     else HIPCHK(lp_launch_window(bd, h->T, h->EPT, h->direct ? h->lds_direct : h->lds, iter_start, iter_end, l2f, h->stream, h->direct, log));
     HIPCHK(hipEventRecord(h->ev1, h->stream));
     int rc = refresh_scalars(h);     // synchronises the stream
@@ -589,17 +623,25 @@ int set_instance(lpbox_t *h, int idx, int n, int l, int nnz, const int *colptr, 
     if (n == l) return fail(LPBOX_E_UNSUPPORTED, "n == l: the reference's aliased sparse product is ill-defined here (LPcpp:103-107,150)");
     if (colptr[0] != 0 || colptr[n] != nnz) return fail(LPBOX_E_BADARG, "colptr does not span nnz");
     // validate everything BEFORE touching the instance (a rejected call leaves it as it was) and before reading rowidx / vals through colptr
+    bool valued = false;
     for (int j = 0; j < n; j++) {
         if (colptr[j] < 0 || colptr[j + 1] < colptr[j] || colptr[j + 1] > nnz) return fail(LPBOX_E_BADARG, "colptr not monotone inside [0, nnz]");
         for (int k = colptr[j]; k < colptr[j + 1]; k++) {
             if (rowidx[k] < 0 || rowidx[k] >= l) return fail(LPBOX_E_BADARG, "row index out of range");
             if (k > colptr[j] && rowidx[k] <= rowidx[k - 1]) return fail(LPBOX_E_BADARG, "row indices must ascend inside a column");
-            if (vals && vals[k] != 1.0)
-                return fail(LPBOX_E_UNSUPPORTED, "E has a stored value %g != 1; the LP kernels hold E implicitly as a 0/1 pattern", vals[k]);
+            if (vals && !std::isfinite(vals[k])) return fail(LPBOX_E_BADARG, "E has a non-finite stored value (column %d, row %d)", j, rowidx[k]);
+            if (vals && vals[k] != 1.0) {
+                if (h->order != LPBOX_ORDER_REFERENCE)
+                    return fail(LPBOX_E_UNSUPPORTED, "E has a stored value %g != 1; the default-order LP kernels hold E implicitly as a 0/1 pattern "
+                                "(call lpbox_set_order(LPBOX_ORDER_REFERENCE) first: the reference-order kernels carry stored values)", vals[k]);
+                valued = true;
+            }
         }
     }
     LpInstance &I = h->inst[idx];
     I.n = n; I.l = l; I.nnz = nnz;
+    if (valued) I.vals.assign(vals, vals + nnz); else I.vals.clear();     // all ones = a unit instance
+    I.vals_csr.assign(valued ? nnz : 0, 0.0);
     I.colptr.assign(colptr, colptr + n + 1);
     I.rowidx.assign(rowidx, rowidx + nnz);
     // CSR of E: rows in ascending column order (the order Eigen's column-major product accumulates a row in)
@@ -609,7 +651,11 @@ int set_instance(lpbox_t *h, int idx, int n, int l, int nnz, const int *colptr, 
     I.colidx.assign(nnz, 0);
     std::vector<int> cur(I.rowptr.begin(), I.rowptr.end() - 1);
     for (int j = 0; j < n; j++)
-        for (int k = colptr[j]; k < colptr[j + 1]; k++) I.colidx[cur[rowidx[k]]++] = j;
+        for (int k = colptr[j]; k < colptr[j + 1]; k++) {
+            const int at = cur[rowidx[k]]++;
+            I.colidx[at] = j;
+            if (valued) I.vals_csr[at] = vals[k];
+        }
     I.b.assign(b, b + n);
     if (f) I.f_org.assign(f, f + l); else I.f_org.assign(l, 1.0);
     I.left_idx.resize(n);
@@ -682,6 +728,7 @@ void lpbox_destroy(lpbox_t *h) {
     h->rs_col.release(); h->cs_row.release(); h->rid.release(); h->rmeta.release(); h->rgl.release(); h->live_init.release();
     h->x.release(); h->z1.release(); h->z2.release(); h->b.release(); h->pd.release(); h->z4.release(); h->f.release();
     h->f_org.release(); h->dsc.release(); h->hist.release(); h->dctl.release(); h->c1_init.release(); h->xhist.release();
+    h->vr.release(); h->vc.release(); h->r4v.release();
     h->xi_out.release(); h->live.release(); h->newfix.release(); h->stamps.release(); h->logbuf.release(); h->Hinv.release(); h->rdir.release(); h->dng.release();
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -768,7 +815,7 @@ int lpbox_init(lpbox_t *h) {
     }
     h->xi_valid = false;
     HIPCHK(hipMemsetAsync(h->ctl.p, 0, (size_t)h->B * 4 * sizeof(int), h->stream));
-    if (h->order == LPBOX_ORDER_REFERENCE) HIPCHK(lp_ref_launch_init(h->dev(), h->lds, h->f_org.p, h->c1_init.p, h->live_init.p, h->stream));
+    if (h->order == LPBOX_ORDER_REFERENCE) HIPCHK(lp_ref_launch_init(h->dev(), h->ref_vals(), h->lds, h->f_org.p, h->c1_init.p, h->live_init.p, h->stream));
     else HIPCHK(lp_launch_init(h->dev(), h->T, h->EPT, h->f_org.p, h->c1_init.p, h->live_init.p, h->stream));
     rc = refresh_scalars(h);
     if (rc) return rc;
@@ -1001,6 +1048,10 @@ int lpbox_set_order(lpbox_t *h, int mode) {
     if (valid_handle(h) && h->seg) return fail(LPBOX_E_STATE, "this entry point belongs to the LP flavour");
     if (!valid_handle(h)) return fail(LPBOX_E_BADHANDLE, "bad handle");
     if (mode != LPBOX_ORDER_DEFAULT && mode != LPBOX_ORDER_REFERENCE) return fail(LPBOX_E_BADARG, "summation order %d", mode);
+    if (mode == LPBOX_ORDER_DEFAULT)
+        for (size_t i = 0; i < h->inst.size(); i++)
+            if (!h->inst[i].vals.empty())
+                return fail(LPBOX_E_UNSUPPORTED, "instance %zu stores values != 1; only the reference order carries them", i);
     if (mode == LPBOX_ORDER_REFERENCE && h->direct) return fail(LPBOX_E_UNSUPPORTED, "the direct x-update has no reference-order variant");
     if (mode == LPBOX_ORDER_REFERENCE && h->log_on) return fail(LPBOX_E_UNSUPPORTED, "the iteration log has no reference-order variant");
     if (h->finalized) return fail(LPBOX_E_STATE, "problem already uploaded; choose the summation order before lpbox_init");
@@ -1256,6 +1307,19 @@ int lpbox_get_problem_lp(lpbox_t *h, int idx, int *n, int *l, int *nnz, int *col
     return LPBOX_OK;
 }
 
+int lpbox_get_problem_lp_vals(lpbox_t *h, int idx, double *vals) {
+    if (valid_handle(h) && h->seg) return fail(LPBOX_E_STATE, "this entry point belongs to the LP flavour");
+    int rc = check_idx(h, idx);
+    if (rc) return rc;
+    const LpInstance &I = h->inst[idx];
+    if (!I.set) return fail(LPBOX_E_STATE, "instance %d has no problem (call read_File / set_problem first)", idx);
+    if (vals) {
+        if (I.vals.empty()) std::fill(vals, vals + I.nnz, 1.0);
+        else std::copy(I.vals.begin(), I.vals.end(), vals);
+    }
+    return I.nnz;
+}
+
 int lpbox_check_infeasible_lpbox(lpbox_t *h, int idx) {                     // LPcpp:1577-1591: rows of the CURRENT E with (E x)_i > 1
     int rc = check_idx(h, idx);
     if (rc) return rc;
@@ -1270,7 +1334,8 @@ int lpbox_check_infeasible_lpbox(lpbox_t *h, int idx) {                     // L
     int inf = 0;
     for (int r = 0; r < I.l; r++) {
         double s = 0.0;
-        for (int k = I.rowptr[r]; k < I.rowptr[r + 1]; k++) if (live[I.colidx[k]]) s += 1.0 * x[I.colidx[k]];
+        // mat_mul_vec on the compacted E: res_i += val * (1.0 * x_j) over the live columns, ascending, from 0
+        for (int k = I.rowptr[r]; k < I.rowptr[r + 1]; k++) if (live[I.colidx[k]]) s += (I.vals.empty() ? 1.0 : I.vals_csr[k]) * (1.0 * x[I.colidx[k]]);
         if (!(s <= 1.0)) inf++;
     }
     return inf;
@@ -1287,7 +1352,7 @@ int lpbox_check_infeasible_l2f(lpbox_t *h, int idx) {                       // L
     int inf = 0;
     for (int r = 0; r < I.l; r++) {
         double s = 0.0;
-        for (int k = I.rowptr[r]; k < I.rowptr[r + 1]; k++) s += 1.0 * sol[I.colidx[k]];
+        for (int k = I.rowptr[r]; k < I.rowptr[r + 1]; k++) s += (I.vals.empty() ? 1.0 : I.vals_csr[k]) * (1.0 * sol[I.colidx[k]]);
         if (!(s <= 1.0)) inf++;
     }
     return inf;
@@ -1394,6 +1459,12 @@ int lpbox_debug_get_vec(lpbox_t *h, int idx, const char *name, double *out, int 
     else if (!strcmp(name, "pd")) pool = h->pd.p;
     else if (!strcmp(name, "z4")) { pool = h->z4.p; stride = h->LS; len = I.l; by_var = false; }
     else if (!strcmp(name, "f")) { pool = h->f.p; stride = h->LS; len = I.l; by_var = false; }
+    else if (!strcmp(name, "r4v")) {     // valued reference-order batches: the entries of rho4_E_transpose, CSC entry order
+        if (!h->valued) return fail(LPBOX_E_BADARG, "no stored values in this batch");
+        if (I.nnz > cap) return fail(LPBOX_E_BADARG, "buffer too small");
+        HIPCHK(hipMemcpy(out, h->r4v.p + (size_t)idx * h->ZS, sizeof(double) * (size_t)I.nnz, hipMemcpyDeviceToHost));
+        return I.nnz;
+    }
     else if (!strcmp(name, "live")) {
         std::vector<uint8_t> live;
         if ((rc = fetch_live(h, idx, live))) return rc;

@@ -89,10 +89,19 @@ hipError_t lp_launch_window(const LpBatchDev &bd, int T, int EPT, size_t lds, in
 bool lp_log_supported(int T, int EPT);         // geometries the logging variant is compiled for (the default ones: 512 threads)
 bool lp_direct_supported(int T, int EPT);      // geometries the DIRECT variant is compiled for
 // opt-in reference-order kernels (lpbox_lp_ref_kernels.hip, lpbox_set_order): identity layout, 512 threads, EPT = 1, 2 or 4
-size_t lp_ref_lds_bytes(int NS, int LS, int ZS);
+// Stored values of E for the VALUED variants of those kernels (a batch with at least one value other than 1.0),
+// ZS doubles per instance like rs_col / cs_row.  vr = nullptr selects the unit kernels, which never read this struct.
+struct LpRefVals {
+    const double *vr;       // values in CSR order (entry k of rs_col)
+    const double *vc;       // values in CSC order (entry k of cs_row)
+    double *r4v;            // the entries of rho4_E_transpose in CSC order, kept from launch to launch (what ND_R4ET is to the unit kernels)
+    int in_lds;             // 1: the three arrays are staged in LDS behind the RefLds carve-up, 0: read from / written to global memory
+};
+size_t lp_ref_lds_bytes(int NS, int LS, int ZS, bool vals_in_lds = false);
 bool lp_ref_supported(int T, int EPT);
-hipError_t lp_ref_launch_init(const LpBatchDev &bd, size_t lds, const double *f_org, const double *c1_init, const uint8_t *live_init,
+hipError_t lp_ref_launch_init(const LpBatchDev &bd, const LpRefVals &vv, size_t lds, const double *f_org, const double *c1_init, const uint8_t *live_init,
                               hipStream_t s);
-hipError_t lp_ref_launch_window(const LpBatchDev &bd, int EPT, size_t lds, int iter_start, int iter_end, int mode, hipStream_t s);
+hipError_t lp_ref_launch_window(const LpBatchDev &bd, const LpRefVals &vv, int EPT, size_t lds, int iter_start, int iter_end, int mode,
+                                hipStream_t s);
 hipError_t lp_launch_pack_xiters(const LpBatchDev &bd, const int *live_pos, const int *rows, int ws, double *out,
                                  long out_stride, hipStream_t s);

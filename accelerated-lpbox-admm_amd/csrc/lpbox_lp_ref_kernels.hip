@@ -12,6 +12,10 @@
 // to an LDS staging buffer at the live rank of each variable (a block prefix sum over the live mask, rebuilt at launch and after a fix);
 // then four lanes of wave 0 walk the four chains of the redux.  Independent reductions ride on different lane groups of that wave at
 // the same time (up to NSTG of them), so they cost one walk.
+// VALUED variants (a batch in which some instance stores a value other than 1.0): every entry of a row / column sum
+// is val * v, rounded, then added; rho4_E_transpose is an array r4v with one entry per stored entry (CSC order), set to rho4 * val and
+// scaled in place by learning_fact exactly as the reference does, kept in global memory between launches.  The values sit in LDS behind
+// the carve-up below (VLDS) or stay in global memory.  The unit variants are the code as it was and never touch the values.
 // Built with -ffp-contract=off like the rest of the library.  The one known deviation from the reference: the std stop test takes
 // sqrt where the reference calls pow(v, 1/2) (glibc pow is not correctly rounded; the oracle counts the disagreements).
 #include "lpbox_lp.h"
@@ -104,10 +108,46 @@ __device__ __forceinline__ double seq_gather(const uint16_t *idx, int b, int e, 
     return acc;
 }
 
+// the same with stored values: acc = ((+0.0 + val[b] * src[idx[b]]) + val[b + 1] * src[idx[b + 1]]) + ..., every product rounded first
+template <int STRIDE>
+__device__ __forceinline__ double seq_gather_val(const uint16_t *idx, const double *val, int b, int e, const double *src) {
+    double acc = 0.0;
+    int k = b;
+    for (; k + 4 <= e; k += 4) {
+        const double p0 = val[k] * src[STRIDE * idx[k]], p1 = val[k + 1] * src[STRIDE * idx[k + 1]];
+        const double p2 = val[k + 2] * src[STRIDE * idx[k + 2]], p3 = val[k + 3] * src[STRIDE * idx[k + 3]];
+        acc = acc + p0; acc = acc + p1; acc = acc + p2; acc = acc + p3;
+    }
+    for (; k < e; k++) acc = acc + val[k] * src[STRIDE * idx[k]];
+    return acc;
+}
+
+// VALUED kernels: rho4_E_transpose = rho4 * E_transpose (LPcpp:2293) and rho4_E_transpose *= learning_fact (:864), entry by entry.  A thread
+// keeps the entries of its own columns j = s * RT + tid (cs_ptr[j] .. cs_ptr[j + 1] of the CSC order), the only ones it ever reads, so no
+// barrier orders these writes.  (Free functions: a lambda in the window kernel would perturb the code of the unit variants.)
+template <int EPT>
+__device__ __forceinline__ void r4v_set(double *r4v, const double *vc, const int *cs_ptr, int n, double rho4) {
+#pragma unroll
+    for (int s = 0; s < EPT; s++) {
+        const int j = s * RT + (int)threadIdx.x;
+        if (j < n) for (int k = cs_ptr[j]; k < cs_ptr[j + 1]; k++) r4v[k] = rho4 * vc[k];
+    }
+}
+template <int EPT>
+__device__ __forceinline__ void r4v_scale(double *r4v, const int *cs_ptr, int n, double fct) {
+#pragma unroll
+    for (int s = 0; s < EPT; s++) {
+        const int j = s * RT + (int)threadIdx.x;
+        if (j < n) for (int k = cs_ptr[j]; k < cs_ptr[j + 1]; k++) r4v[k] = fct * r4v[k];
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // ADMM_lp_iters_init (LPcpp:489-763): lp_init_kernel with best_bin_obj = b.dot(x0) in Eigen's order
 // ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(RT) lp_ref_init_kernel(LpBatchDev bd, const double *f_org, const double *c1_init, const uint8_t *live_init) {
+template <bool VALUED>
+__global__ void __launch_bounds__(RT) lp_ref_init_kernel(LpBatchDev bd, const double *f_org, const double *c1_init, const uint8_t *live_init,
+                                                         LpRefVals vv) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const RefLds L(bd.NS, bd.LS, bd.ZS);
     double *stage = (double *)(smem + L.stage), *res = (double *)(smem + L.res);
@@ -125,6 +165,8 @@ __global__ void __launch_bounds__(RT) lp_ref_init_kernel(LpBatchDev bd, const do
         if (pos < n) stage[pos] = bd.b[on + pos] * 1.0;   // products of b.dot(x0), :727
     }
     for (int i = tid; i < l; i += RT) { bd.z4[ol + i] = 0.0; bd.f[ol + i] = f_org[ol + i]; }   // :650
+    if constexpr (VALUED)                                // rho4_E_transpose is built by the first iteration (what ND_R4ET = 0 says below)
+        for (int k = tid; k < isc[NI_NNZ]; k += RT) vv.r4v[(size_t)inst * bd.ZS + k] = 0.0;
     double bb[1];
     eigen_reduce<1>(stage, bd.NS, n, res, bb);
     if (tid == 0) {
@@ -153,8 +195,8 @@ __global__ void __launch_bounds__(RT) lp_ref_init_kernel(LpBatchDev bd, const do
 // ADMM_lp_iters_l2f (LPcpp:1098-1574, bit 0 set); bit 1 keeps x after every iteration in xhist.  Same phases, same expressions and the
 // same saved state as lp_window_kernel; only the sums are associated differently.
 // ------------------------------------------------------------------------------------------------
-template <int EPT>
-__global__ void __launch_bounds__(RT) lp_ref_window_kernel(LpBatchDev bd, int iter_start, int iter_end, int mode) {
+template <int EPT, bool VALUED, bool VLDS>
+__global__ void __launch_bounds__(RT) lp_ref_window_kernel(LpBatchDev bd, int iter_start, int iter_end, int mode, LpRefVals vv) {
     const int l2f = mode & 1, rec = mode & 2;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int inst = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -173,6 +215,13 @@ __global__ void __launch_bounds__(RT) lp_ref_window_kernel(LpBatchDev bd, int it
     uint16_t *s_rank = (uint16_t *)(smem + L.rank);
     uint8_t *s_flag = (uint8_t *)(smem + L.flag);
     int *s_wsum = (int *)(smem + L.wsum);
+    // VALUED: the values in CSR and CSC entry order and rho4_E_transpose (CSC entry order), in LDS behind the carve-up or in global memory
+    const double *vr = nullptr, *vc = nullptr;
+    double *r4v = nullptr;
+    if constexpr (VALUED) {
+        if constexpr (VLDS) { double *sv = (double *)(smem + L.total); vr = sv; vc = sv + bd.ZS; r4v = sv + 2 * (size_t)bd.ZS; }
+        else { vr = vv.vr + oz; vc = vv.vc + oz; r4v = vv.r4v + oz; }
+    }
 
     // ---- stage the index sets of E into LDS ----
     {
@@ -180,6 +229,12 @@ __global__ void __launch_bounds__(RT) lp_ref_window_kernel(LpBatchDev bd, int it
         for (int i = tid; i <= l; i += RT) s_rs_ptr[i] = gp[i];
         for (int j = tid; j <= n; j += RT) s_cs_ptr[j] = gc[j];
         for (int k = tid; k < nnz; k += RT) { s_rs_col[k] = bd.rs_col[oz + k]; s_cs_row[k] = bd.cs_row[oz + k]; }
+        if constexpr (VALUED && VLDS) {
+            double *sv = (double *)(smem + L.total);
+            for (int k = tid; k < nnz; k += RT) {
+                sv[k] = vv.vr[oz + k]; sv[bd.ZS + k] = vv.vc[oz + k]; sv[2 * (size_t)bd.ZS + k] = vv.r4v[oz + k];
+            }
+        }
     }
 
     // ---- per-thread state: variables j = s * RT + tid, rows i = s * RT + tid ----
@@ -215,7 +270,15 @@ __global__ void __launch_bounds__(RT) lp_ref_window_kernel(LpBatchDev bd, int it
     int ret = 0, stop = LP_STOP_NONE;
 
     __syncthreads();   // index sets staged
-
+    if constexpr (VALUED) {                                       // Esq_diag_j = sum of val^2 down column j, rows ascending, from +0.0 (:2378-2390)
+#pragma unroll
+        for (int s = 0; s < EPT; s++) {
+            const int j = s * RT + tid;
+            double e = 0.0;
+            if (j < n) for (int k = s_cs_ptr[j]; k < s_cs_ptr[j + 1]; k++) e += vc[k] * vc[k];
+            esq[s] = e;
+        }
+    }
     // out[s] = rank of this thread's variable of slot s among the flagged ones (ascending index); returns how many are flagged.
     // Thread t counts the flags of positions t*EPT .. t*EPT+EPT-1, a wave scan and the wave totals give every position its rank.
     auto rank_build = [&](const bool (&fl)[EPT], int (&out)[EPT]) {
@@ -247,15 +310,18 @@ __global__ void __launch_bounds__(RT) lp_ref_window_kernel(LpBatchDev bd, int it
 #pragma unroll
         for (int s = 0; s < EPT; s++) {
             const int i = s * RT + tid;
-            out[s] = rv[s] ? seq_gather<1>(s_rs_col, s_rs_ptr[i], s_rs_ptr[i + 1], gx) : 0.0;
+            if constexpr (VALUED) out[s] = rv[s] ? seq_gather_val<1>(s_rs_col, vr, s_rs_ptr[i], s_rs_ptr[i + 1], gx) : 0.0;
+            else out[s] = rv[s] ? seq_gather<1>(s_rs_col, s_rs_ptr[i], s_rs_ptr[i + 1], gx) : 0.0;
         }
     };
-    // (E^T gl[.][c])_j for this thread's variables; gl must have been published
+    // (E^T gl[.][c])_j for this thread's variables; gl must have been published.  VALUED: c = 0 multiplies by the entries of
+    // rho4_E_transpose (r4v), c = 1 by those of E_transpose (vc)
     auto cols_sum = [&](int c, double (&out)[EPT]) {
 #pragma unroll
         for (int s = 0; s < EPT; s++) {
             const int j = s * RT + tid;
-            out[s] = j < n ? seq_gather<2>(s_cs_row, s_cs_ptr[j], s_cs_ptr[j + 1], gl + c) : 0.0;
+            if constexpr (VALUED) out[s] = j < n ? seq_gather_val<2>(s_cs_row, c == 0 ? r4v : vc, s_cs_ptr[j], s_cs_ptr[j + 1], gl + c) : 0.0;
+            else out[s] = j < n ? seq_gather<2>(s_cs_row, s_cs_ptr[j], s_cs_ptr[j + 1], gl + c) : 0.0;
         }
     };
     auto publish_x = [&](const double (&v)[EPT]) {
@@ -299,6 +365,7 @@ __global__ void __launch_bounds__(RT) lp_ref_window_kernel(LpBatchDev bd, int it
 #pragma unroll
             for (int s = 0; s < EPT; s++) { double v = dI; v += rho4 * esq[s]; pd[s] = v; }
             r4Et = rho4;
+            if constexpr (VALUED) r4v_set<EPT>(r4v, vc, s_cs_ptr, n, rho4);
             expr_ready = 1;
             fixed_now = true;
         }
@@ -344,6 +411,7 @@ __global__ void __launch_bounds__(RT) lp_ref_window_kernel(LpBatchDev bd, int it
 #pragma unroll
                 for (int s = 0; s < EPT; s++) { double v = dI; v += rho4 * esq[s]; pd[s] = v; }
                 r4Et = rho4;
+                if constexpr (VALUED) r4v_set<EPT>(r4v, vc, s_cs_ptr, n, rho4);
                 expr_ready = 1;
             }
             if (it != 0 && rhoUpdated) {
@@ -353,14 +421,17 @@ __global__ void __launch_bounds__(RT) lp_ref_window_kernel(LpBatchDev bd, int it
 #pragma unroll
                 for (int s = 0; s < EPT; s++) { double v = pd[s]; v += inc; v += inc4 * esq[s]; pd[s] = v; }
                 r4Et = learning_fact * r4Et;                      // rho4_E_transpose *= learning_fact (:864)
+                if constexpr (VALUED) r4v_scale<EPT>(r4v, s_cs_ptr, n, learning_fact);
             }
             const double r4 = r4Et;
             // ---------------- rhs (:872-878): (rho4 E^T)(f - y3) and E^T z4; every entry of the scaled product adds (rho4 * 1.0) * w_i,
-            // the same value for every column of row i, so the row publishes r4 * w_i once ----------------
+            // the same value for every column of row i, so the row publishes r4 * w_i once.  VALUED: the row publishes w_i itself and
+            // every entry multiplies it by its own r4v ----------------
 #pragma unroll
             for (int s = 0; s < EPT; s++) {
                 const int i = s * RT + tid;
-                if (rv[s]) { gl[2 * i] = r4 * (f[s] - y3[s]); gl[2 * i + 1] = z4[s]; }
+                if constexpr (VALUED) { if (rv[s]) { gl[2 * i] = f[s] - y3[s]; gl[2 * i + 1] = z4[s]; } }
+                else { if (rv[s]) { gl[2 * i] = r4 * (f[s] - y3[s]); gl[2 * i + 1] = z4[s]; } }
             }
             __syncthreads();
             double rhs[EPT];
@@ -391,7 +462,7 @@ __global__ void __launch_bounds__(RT) lp_ref_window_kernel(LpBatchDev bd, int it
                 double q[EPT];
                 rows_sum(q);
 #pragma unroll
-                for (int s = 0; s < EPT; s++) if (rv[s]) gl[2 * (s * RT + tid)] = r4 * q[s];
+                for (int s = 0; s < EPT; s++) if (rv[s]) gl[2 * (s * RT + tid)] = VALUED ? q[s] : r4 * q[s];
             }
             __syncthreads();
             cols_sum(0, tcol);
@@ -425,7 +496,7 @@ __global__ void __launch_bounds__(RT) lp_ref_window_kernel(LpBatchDev bd, int it
                             double q[EPT];
                             rows_sum(q);
 #pragma unroll
-                            for (int s = 0; s < EPT; s++) if (rv[s]) gl[2 * (s * RT + tid)] = r4 * q[s];
+                            for (int s = 0; s < EPT; s++) if (rv[s]) gl[2 * (s * RT + tid)] = VALUED ? q[s] : r4 * q[s];
                         }
                         __syncthreads();
                         cols_sum(0, tcol);
@@ -562,6 +633,10 @@ __global__ void __launch_bounds__(RT) lp_ref_window_kernel(LpBatchDev bd, int it
     }
 
     // ---- write the state back ----
+    if constexpr (VALUED && VLDS) {
+        __syncthreads();                                          // every thread's entries of r4v
+        for (int k = tid; k < nnz; k += RT) vv.r4v[oz + k] = r4v[k];
+    }
 #pragma unroll
     for (int s = 0; s < EPT; s++) {
         const int j = s * RT + tid;
@@ -593,30 +668,42 @@ __global__ void __launch_bounds__(RT) lp_ref_window_kernel(LpBatchDev bd, int it
 // ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
-size_t lp_ref_lds_bytes(int NS, int LS, int ZS) { return RefLds(NS, LS, ZS).total; }
+size_t lp_ref_lds_bytes(int NS, int LS, int ZS, bool vals_in_lds) {
+    return RefLds(NS, LS, ZS).total + (vals_in_lds ? 3 * sizeof(double) * (size_t)ZS : 0);
+}
 
 bool lp_ref_supported(int T, int EPT) { return T == RT && (EPT == 1 || EPT == 2 || EPT == 4); }
 
-hipError_t lp_ref_launch_init(const LpBatchDev &bd, size_t lds, const double *f_org, const double *c1_init, const uint8_t *live_init,
-                              hipStream_t s) {
-    hipError_t e = hipFuncSetAttribute((const void *)lp_ref_init_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+hipError_t lp_ref_launch_init(const LpBatchDev &bd, const LpRefVals &vv, size_t lds, const double *f_org, const double *c1_init,
+                              const uint8_t *live_init, hipStream_t s) {
+    auto kfn = vv.vr ? lp_ref_init_kernel<true> : lp_ref_init_kernel<false>;
+    hipError_t e = hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(lp_ref_init_kernel, dim3(bd.B), dim3(RT), lds, s, bd, f_org, c1_init, live_init);
+    hipLaunchKernelGGL(kfn, dim3(bd.B), dim3(RT), lds, s, bd, f_org, c1_init, live_init, vv);
     return hipGetLastError();
 }
 
-hipError_t lp_ref_launch_window(const LpBatchDev &bd, int EPT, size_t lds, int iter_start, int iter_end, int mode, hipStream_t s) {
-#define CALL_REF(EE)                                                                                           \
+// vv.vr == nullptr: the unit kernels; else the VALUED ones with the values in LDS (vv.in_lds) or in global memory
+hipError_t lp_ref_launch_window(const LpBatchDev &bd, const LpRefVals &vv, int EPT, size_t lds, int iter_start, int iter_end, int mode,
+                                hipStream_t s) {
+#define CALL_REF(EE, VA, VL)                                                                                   \
     {                                                                                                          \
-        auto kfn = lp_ref_window_kernel<EE>;                                                                   \
+        auto kfn = lp_ref_window_kernel<EE, VA, VL>;                                                           \
         hipError_t e = hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
         if (e != hipSuccess) return e;                                                                         \
-        hipLaunchKernelGGL(kfn, dim3(bd.B), dim3(RT), lds, s, bd, iter_start, iter_end, mode);                 \
+        hipLaunchKernelGGL(kfn, dim3(bd.B), dim3(RT), lds, s, bd, iter_start, iter_end, mode, vv);             \
     }
-    if (EPT == 1) CALL_REF(1)
-    else if (EPT == 2) CALL_REF(2)
-    else if (EPT == 4) CALL_REF(4)
+#define PICK_REF(EE)                                                                                           \
+    {                                                                                                          \
+        if (!vv.vr) CALL_REF(EE, false, false)                                                                 \
+        else if (vv.in_lds) CALL_REF(EE, true, true)                                                           \
+        else CALL_REF(EE, true, false)                                                                         \
+    }
+    if (EPT == 1) PICK_REF(1)
+    else if (EPT == 2) PICK_REF(2)
+    else if (EPT == 4) PICK_REF(4)
     else return hipErrorInvalidConfiguration;
+#undef PICK_REF
 #undef CALL_REF
     return hipGetLastError();
 }

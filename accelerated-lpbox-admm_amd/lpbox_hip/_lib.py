@@ -32,6 +32,7 @@ SYMBOLS = {
     "lpbox_read_file": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_int]),
     "lpbox_get_problem_lp": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p]),
+    "lpbox_get_problem_lp_vals": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "lpbox_init": (C.c_int, [C.c_void_p]),
     "lpbox_iterate": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "lpbox_iterate_l2f": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p]),

@@ -29,13 +29,14 @@ def _as_int(v, name):
 class LpBatch:
     """B independent LP instances solved together on one GPU (extension; no reference counterpart).
 
-    instances: iterable of dicts with keys n, l, colptr, rowidx (CSC of E, 0/1 pattern), b (already negated,
-    LPcpp:2520) and optionally f (default ones, LPcpp:2522).
+    instances: iterable of dicts with keys n, l, colptr, rowidx (CSC of E), b (already negated, LPcpp:2520) and optionally
+    f (default ones, LPcpp:2522) and vals (the stored values of E in the order of rowidx; default ones = a 0/1 pattern).
+    order: the summation order, set before the instances ("reference" is the one that accepts vals other than 1, see set_order).
     """
 
     order = "default"        # summation order of the kernels (set_order)
 
-    def __init__(self, instances=None, print_info=0, device=None, batch=None):
+    def __init__(self, instances=None, print_info=0, device=None, batch=None, order=None):
         self._L = _lib.load()
         if device is not None:
             check(self._L.lpbox_set_device(int(device)), "lpbox_set_device")
@@ -46,9 +47,11 @@ class LpBatch:
         if not h:
             check(-2, "lpbox_create")
         self._h = C.c_void_p(h)
+        if order is not None:
+            self.set_order(order)
         if instances is not None:
             for i, I in enumerate(instances):
-                self.set_problem(i, I["n"], I["l"], I["colptr"], I["rowidx"], I["b"], I.get("f"))
+                self.set_problem(i, I["n"], I["l"], I["colptr"], I["rowidx"], I["b"], I.get("f"), I.get("vals"))
 
     def close(self):
         if getattr(self, "_h", None):
@@ -85,14 +88,20 @@ class LpBatch:
         check(self._L.lpbox_read_file(self._h, idx, r, int(i), int(k), int(j)), "lpbox_read_file")
 
     def get_problem(self, idx=0):
-        """The instance as set_problem / read_file left it in the handle: dict(n, l, colptr, rowidx, b, f)."""
+        """The instance as set_problem / read_file left it in the handle: dict(n, l, colptr, rowidx, b, f), plus vals (the stored values
+        in the order of rowidx) when some value is not 1."""
         n, l, nnz = C.c_int(), C.c_int(), C.c_int()
         check(self._L.lpbox_get_problem_lp(self._h, idx, C.byref(n), C.byref(l), C.byref(nnz), None, None, None, None), "lpbox_get_problem_lp")
         colptr, rowidx = np.zeros(n.value + 1, np.int32), np.zeros(max(nnz.value, 1), np.int32)
         b, f = np.zeros(n.value), np.zeros(l.value)
         check(self._L.lpbox_get_problem_lp(self._h, idx, None, None, None, colptr.ctypes.data_as(C.c_void_p), rowidx.ctypes.data_as(C.c_void_p),
                                            b.ctypes.data_as(C.c_void_p), f.ctypes.data_as(C.c_void_p)), "lpbox_get_problem_lp")
-        return dict(n=n.value, l=l.value, colptr=colptr, rowidx=rowidx[:nnz.value], b=b, f=f)
+        P = dict(n=n.value, l=l.value, colptr=colptr, rowidx=rowidx[:nnz.value], b=b, f=f)
+        vals = np.ones(max(nnz.value, 1))
+        check(self._L.lpbox_get_problem_lp_vals(self._h, idx, vals.ctypes.data_as(C.c_void_p)), "lpbox_get_problem_lp_vals")
+        if np.any(vals[:nnz.value] != 1.0):
+            P["vals"] = vals[:nnz.value]
+        return P
 
     # ---- solver ----
     def solve_init(self):
@@ -128,7 +137,8 @@ class LpBatch:
         kernels' own association).  "reference" is an opt-in that sums every dot product / norm in the order of the reference's Eigen
         path and every sparse product row by row / column by column in ascending index order: the reference's
         iterates and binary solutions, except that the std stop test takes sqrt where the reference calls pow(v, 1/2).  Not combinable
-        with the direct x-update or the iteration log; max(n, l) <= 2048 (solve_init raises otherwise)."""
+        with the direct x-update or the iteration log; max(n, l) <= 2048 (solve_init raises otherwise).  It is also the order that
+        accepts stored values of E other than 1 (set_problem(vals=...), valued instance files): set it first."""
         if mode not in ("default", "reference"):
             raise ValueError("summation order must be 'default' or 'reference'")
         check(self._L.lpbox_set_order(self._h, 1 if mode == "reference" else 0), "lpbox_set_order")
@@ -270,6 +280,8 @@ class LpBatch:
 
     def debug_vec(self, name, idx=0):
         cap = max(self.get_org_n(idx), self.get_l(idx))
+        if name == "r4v":        # one value per stored entry of E
+            cap = max(cap, check(self._L.lpbox_get_problem_lp_vals(self._h, idx, None), "lpbox_get_problem_lp_vals"))
         out = np.zeros(cap, np.float64)
         k = check(self._L.lpbox_debug_get_vec(self._h, idx, name.encode(), out, cap), "lpbox_debug_get_vec")
         return out[:k].copy()
@@ -424,8 +436,8 @@ class PyLPboxADMMsolver:
         return None
 
     # extension: hand the problem over in memory instead of through the instance files
-    def set_problem(self, n, l, colptr, rowidx, b, f=None):
-        self._small().set_problem(0, n, l, colptr, rowidx, b, f)
+    def set_problem(self, n, l, colptr, rowidx, b, f=None, vals=None):
+        self._small().set_problem(0, n, l, colptr, rowidx, b, f, vals)
 
     # LP pyx:19-20
     def solve_init(self):

@@ -54,8 +54,12 @@ void     lpbox_destroy(lpbox_t *h);
 
 /* ---- problem input (instance index idx in [0,batch)) ------------------------------------------ */
 /* What readFile leaves in the object (LPcpp:2446-2545): E (l x n) column-major, row indices ascending in a
- * column, all stored values must be 1.0 (vals == NULL means all ones; anything else -> LPBOX_E_UNSUPPORTED),
- * b ALREADY NEGATED (LPcpp:2520), f (NULL means all ones, LPcpp:2522). */
+ * column, vals = the stored values in the same order (NULL means all ones), b ALREADY NEGATED (LPcpp:2520), f (NULL means all
+ * ones, LPcpp:2522).  A handle in the default summation order holds E as a 0/1 pattern: a stored value other than 1.0 ->
+ * LPBOX_E_UNSUPPORTED.  After lpbox_set_order(h, LPBOX_ORDER_REFERENCE) any finite value is accepted (negative, zero and tiny ones
+ * included: an explicit zero stays a stored entry, as in the reference's readSparseMat, LPcpp:2416-2444); a non-finite value ->
+ * LPBOX_E_BADARG.  The same holds for the two file readers below, which negate the values for k == 2 and sum duplicate triplets as
+ * the reference does.  Values that are all exactly 1.0 make a unit instance. */
 int lpbox_set_problem_lp(lpbox_t *h, int idx, int n, int l, int nnz, const int *colptr, const int *rowidx,
                          const double *vals, const double *b, const double *f);
 /* LP pxd:9 `void readFile(int,int,int)` (LPcpp:2446-2545) with the two paths explicit; k as in the reference. */
@@ -68,6 +72,9 @@ int lpbox_read_file(lpbox_t *h, int idx, const char *root, int i, int k, int j);
  * always, arrays where the pointer is not NULL (colptr n+1, rowidx nnz, b n, f l).  Used by the Python class to hand an instance
  * that exceeds the on-chip kernel (max(n, l) > 2048) over to the large-instance path. */
 int lpbox_get_problem_lp(lpbox_t *h, int idx, int *n, int *l, int *nnz, int *colptr, int *rowidx, double *b, double *f);
+/* The stored values of E of that instance, in the order of rowidx (column-major); ones for a unit instance.  Returns nnz; vals == NULL
+ * only queries the count. */
+int lpbox_get_problem_lp_vals(lpbox_t *h, int idx, double *vals);
 
 /* ---- solver (whole batch per call) ------------------------------------------------------------ */
 /* LP pxd:10 `int ADMM_lp_iters_init()` (LPcpp:489-763).  Returns 1 like the reference. */
@@ -110,7 +117,10 @@ int lpbox_set_x_update(lpbox_t *h, int mode);
  * the reference calls pow(v, 1/2).  Only before the problem is uploaded (LPBOX_E_STATE after lpbox_init / lpbox_get_config / ...);
  * LPBOX_E_UNSUPPORTED together with the direct x-update or the iteration log (either call order).  An instance beyond the on-chip
  * limit makes lpbox_init fail with LPBOX_E_TOOLARGE.  lpbox_get_layout / _row_split / _col_split then report the identity layout,
- * one lane per row and whole columns. */
+ * one lane per row and whole columns.
+ * The reference order is also the one that carries STORED VALUES of E other than 1 (lpbox_set_problem_lp): choose
+ * it before handing such an instance over.  A batch with a valued instance runs the valued variants of these kernels, bit-exact against
+ * the same oracle; going back to LPBOX_ORDER_DEFAULT on a handle that holds a valued instance -> LPBOX_E_UNSUPPORTED. */
 #define LPBOX_ORDER_DEFAULT 0
 #define LPBOX_ORDER_REFERENCE 1
 int lpbox_set_order(lpbox_t *h, int mode);

@@ -1,9 +1,7 @@
 // lpbox_gen_capi.hip -- host side + C-ABI (lpbox_bqp_* in include/lpbox_hip.h) of the GENERIC constrained binary-QP path:
 // the reference's ADMM_bqp (SEGcpp:1384-1832) behind its four wrappers ADMM_bqp_unconstrained / _linear_eq / _linear_ineq /
 // _linear_eq_and_uneq (SEGcpp:1834-2109).  The kernels are in lpbox_gen_kernels.hip.
-#include "../../include/lpbox_hip.h"
-#include "lpbox_gen.h"
-#include "lpbox_capi_internal.h"
+#include "lpbox_gen_host.h"
 
 #include <algorithm>
 #include <cmath>
@@ -31,45 +29,18 @@ struct Buf {
         return hipMemcpy(p, v.data(), v.size() * sizeof(Tp), hipMemcpyHostToDevice);
     }
 };
-struct HostCsr { int rows = 0, cols = 0; std::vector<int> ptr, idx; std::vector<double> val; };
 struct DevCsr { Buf<int> ptr, idx; Buf<double> val; GenCsr view() const { return GenCsr{ptr.p, idx.p, val.p}; } };
 
-int load_csr(HostCsr &M, int rows, int cols, const int *ptr, const int *idx, const double *val, const char *what) {
-    if (!ptr || ptr[0] != 0) return lpbox_fail(LPBOX_E_BADARG, "%s: bad row pointer", what);
-    for (int i = 0; i < rows; i++) {
-        if (ptr[i + 1] < ptr[i]) return lpbox_fail(LPBOX_E_BADARG, "%s: row pointer not monotone", what);
-        for (int k = ptr[i]; k < ptr[i + 1]; k++) {
-            if (idx[k] < 0 || idx[k] >= cols) return lpbox_fail(LPBOX_E_BADARG, "%s: column index out of range", what);
-            if (k > ptr[i] && idx[k] <= idx[k - 1]) return lpbox_fail(LPBOX_E_BADARG, "%s: columns must ascend inside a row", what);
-        }
-    }
-    M.rows = rows; M.cols = cols;
-    M.ptr.assign(ptr, ptr + rows + 1); M.idx.assign(idx, idx + ptr[rows]); M.val.assign(val, val + ptr[rows]);
-    return LPBOX_OK;
-}
-void transpose(const HostCsr &S, HostCsr &Tt) {        // rows of the result = columns of S, entries in ascending original row order
-    Tt.rows = S.cols; Tt.cols = S.rows;
-    Tt.ptr.assign((size_t)S.cols + 1, 0);
-    for (int c : S.idx) Tt.ptr[c + 1]++;
-    for (int j = 0; j < S.cols; j++) Tt.ptr[j + 1] += Tt.ptr[j];
-    Tt.idx.resize(S.idx.size()); Tt.val.resize(S.val.size());
-    std::vector<int> cur(Tt.ptr.begin(), Tt.ptr.end() - 1);
-    for (int i = 0; i < S.rows; i++)
-        for (int k = S.ptr[i]; k < S.ptr[i + 1]; k++) { const int p = cur[S.idx[k]]++; Tt.idx[p] = i; Tt.val[p] = S.val[k]; }
-}
-hipError_t upload(DevCsr &D, const HostCsr &H) {
+hipError_t upload(DevCsr &D, const GenHostCsr &H) {
     hipError_t e = D.ptr.upload(H.ptr); if (e != hipSuccess) return e;
     e = D.idx.upload(H.idx); if (e != hipSuccess) return e;
     return D.val.upload(H.val);
 }
 }  // namespace
 
-struct lpbox_bqp {
-    int device = 0, n = 0, m = 0, l = 0;
+struct lpbox_bqp : GenHostProblem {
+    int device = 0;
     GenParams prm;
-    HostCsr A, C, Ct, E, Et;
-    std::vector<int> adiag;
-    std::vector<double> b, x0, d, f;
     bool has_problem = false, uploaded = false, solved = false;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -208,31 +179,12 @@ void lpbox_bqp_destroy(lpbox_bqp_t *h) {
 
 int lpbox_bqp_preset(lpbox_bqp_t *h, int type) {
     if (!h) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
-    GenParams &p = h->prm;
-    switch (type) {
-    case 0:      // ADMM_bqp_unconstrained_init SEGcpp:658-672
-        p.std_threshold = 1e-6; p.gamma_val = 1.0; p.gamma_factor = 0.99; p.initial_rho = 5; p.learning_fact = 1 + 3.0 / 100; p.history_size = 5;
-        p.rho_change_step = 5; p.stop_threshold = 1e-3; p.max_iters = (int)1e4; p.pcg_tol = 1e-3; p.pcg_maxiters = (int)1e3; return LPBOX_OK;
-    case 1:      // ADMM_bqp_linear_eq_init :587-601
-        p.stop_threshold = 1e-4; p.std_threshold = 1e-6; p.gamma_val = 1.6; p.gamma_factor = 0.95; p.rho_change_step = 5; p.max_iters = (int)5e3;
-        p.initial_rho = 1; p.history_size = 3; p.learning_fact = 1 + 5.0 / 100; p.pcg_tol = 1e-4; p.pcg_maxiters = (int)1e3; return LPBOX_OK;
-    case 2:      // ADMM_bqp_linear_ineq_init :603-617
-    case 3:      // ADMM_bqp_linear_eq_and_uneq_init :620-634
-        p.stop_threshold = 1e-4; p.std_threshold = 1e-6; p.gamma_val = 1.6; p.gamma_factor = 0.95; p.rho_change_step = 5; p.max_iters = (int)1e4;
-        p.initial_rho = 25; p.history_size = 3; p.learning_fact = 1 + 1.0 / 100; p.pcg_tol = 1e-4; p.pcg_maxiters = (int)1e3; return LPBOX_OK;
-    }
-    return lpbox_fail(LPBOX_E_BADARG, "preset %d: 0 unconstrained, 1 equality, 2 inequality, 3 both", type);
+    return gen_preset(h->prm, type);
 }
 
 int lpbox_bqp_set_params(lpbox_bqp_t *h, const double *p11) {
     if (!h || !p11) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
-    GenParams &p = h->prm;
-    p.stop_threshold = p11[0]; p.std_threshold = p11[1]; p.gamma_val = p11[2]; p.gamma_factor = p11[3]; p.rho_change_step = (int)p11[4];
-    p.max_iters = (int)p11[5]; p.initial_rho = p11[6]; p.history_size = (int)p11[7]; p.learning_fact = p11[8]; p.pcg_tol = p11[9];
-    p.pcg_maxiters = (int)p11[10];
-    if (p.history_size < 2 || p.history_size > GEN_HIST_MAX) return lpbox_fail(LPBOX_E_BADARG, "history_size must be in [2,%d]", GEN_HIST_MAX);
-    if (p.rho_change_step < 1 || p.max_iters < 0 || p.pcg_maxiters < 1) return lpbox_fail(LPBOX_E_BADARG, "bad iteration parameters");
-    return LPBOX_OK;
+    return gen_set_params(h->prm, p11);
 }
 
 int lpbox_bqp_set_problem(lpbox_bqp_t *h, int n, const int *Ap, const int *Ai, const double *Av, const double *b, const double *x0,
@@ -240,18 +192,7 @@ int lpbox_bqp_set_problem(lpbox_bqp_t *h, int n, const int *Ap, const int *Ai, c
                           int l, const int *Ep, const int *Ei, const double *Ev, const double *f) {
     if (!h) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
     if (h->uploaded) return lpbox_fail(LPBOX_E_STATE, "problem already uploaded; create a new handle");
-    if (n <= 0 || !b || !x0 || m < 0 || l < 0) return lpbox_fail(LPBOX_E_BADARG, "bad problem arguments");
-    CHK(load_csr(h->A, n, n, Ap, Ai, Av, "A"));
-    h->adiag.assign(n, -1);
-    for (int i = 0; i < n; i++) {
-        for (int k = Ap[i]; k < Ap[i + 1]; k++) if (Ai[k] == i) h->adiag[i] = k;
-        if (h->adiag[i] < 0)      // `.diagonal() +=` on a compressed sparse matrix needs the entry to exist (SEGcpp:1483): store explicit zeros
-            return lpbox_fail(LPBOX_E_BADARG, "A has no stored diagonal entry in row %d", i);
-    }
-    if (m > 0) { if (!d) return lpbox_fail(LPBOX_E_BADARG, "d missing"); CHK(load_csr(h->C, m, n, Cp, Ci, Cv, "C")); transpose(h->C, h->Ct); h->d.assign(d, d + m); }
-    if (l > 0) { if (!f) return lpbox_fail(LPBOX_E_BADARG, "f missing"); CHK(load_csr(h->E, l, n, Ep, Ei, Ev, "E")); transpose(h->E, h->Et); h->f.assign(f, f + l); }
-    h->n = n; h->m = m; h->l = l;
-    h->b.assign(b, b + n); h->x0.assign(x0, x0 + n);
+    CHK(gen_load_problem(*h, n, Ap, Ai, Av, b, x0, m, Cp, Ci, Cv, d, l, Ep, Ei, Ev, f));
     h->has_problem = true;
     return LPBOX_OK;
 }

@@ -7,6 +7,7 @@
 // columns are summed by one lane in ascending index order, no FMA contraction, IEEE divide / sqrt.
 #include "lpbox_gen.h"
 #include "lpbox_dev_common.h"
+#include "lpbox_gen_dev.h"
 
 #include <float.h>
 
@@ -28,8 +29,6 @@ __device__ __forceinline__ void store_partials(const GenDev &d, int slot0, doubl
     }
 }
 
-__device__ __forceinline__ double eigen_res(double tmp) { double r = 0.0; r += 1.0 * tmp; return r; }   // res[i] = 0 + alpha * tmp
-
 __global__ void __launch_bounds__(T) gen_k_fin(GenDev d, int nv) {
     __shared__ double red[2 * RED_MAXV * RED_MAXW];
     int parity = 0;
@@ -39,27 +38,11 @@ __global__ void __launch_bounds__(T) gen_k_fin(GenDev d, int nv) {
 // A x for row j with x read through `ld` (ascending columns, diagonal included)
 template <typename LD>
 __device__ __forceinline__ double a_row(const GenDev &d, int j, const double *vals, LD ld) {
-    double tmp = 0;
-    const int k1 = d.aptr[j + 1];
-    int k = d.aptr[j];
-    for (; k + 4 <= k1; k += 4) {
-        const double v0 = ld(d.aidx[k]), v1 = ld(d.aidx[k + 1]), v2 = ld(d.aidx[k + 2]), v3 = ld(d.aidx[k + 3]);
-        tmp += vals[k] * v0; tmp += vals[k + 1] * v1; tmp += vals[k + 2] * v2; tmp += vals[k + 3] * v3;
-    }
-    for (; k < k1; k++) tmp += vals[k] * ld(d.aidx[k]);
-    return eigen_res(tmp);
+    return gen_sparse_dot(d.aidx, vals, d.aptr[j], d.aptr[j + 1], ld);
 }
 // (scaled transpose row j) . q = sum over the column's entries in ascending row order
 __device__ __forceinline__ double col_dot(const GenCsr &c, const double *vals, int j, const double *q) {
-    double tmp = 0;
-    const int k1 = c.ptr[j + 1];
-    int k = c.ptr[j];
-    for (; k + 4 <= k1; k += 4) {
-        const double v0 = q[c.idx[k]], v1 = q[c.idx[k + 1]], v2 = q[c.idx[k + 2]], v3 = q[c.idx[k + 3]];
-        tmp += vals[k] * v0; tmp += vals[k + 1] * v1; tmp += vals[k + 2] * v2; tmp += vals[k + 3] * v3;
-    }
-    for (; k < k1; k++) tmp += vals[k] * q[c.idx[k]];
-    return eigen_res(tmp);
+    return gen_sparse_dot(c.idx, vals, c.ptr[j], c.ptr[j + 1], [q](int i) { return q[i]; });
 }
 
 __global__ void __launch_bounds__(T) gen_k_init(GenDev d, double c1, const double *x0) {     // SEGcpp:1430-1560
@@ -141,46 +124,7 @@ __global__ void __launch_bounds__(T) gen_k_prep(GenDev d, int in, int out, int d
         GenState *s = d.st + out;
         if (fin) {
             s->have_prev = 0;
-            const double xn = sqrt(d.red[0]);
-            const double t0 = (xn < 2.2204e-16) ? 2.2204e-16 : xn;
-            s->cvg1 = sqrt(d.red[1]) / t0; s->cvg2 = sqrt(d.red[2]) / t0;                                   // :1742-1744
-            bool stopped = false;
-            if (s->cvg1 <= P.stop_threshold && s->cvg2 <= P.stop_threshold) { s->stop = GEN_STOP_XYY; stopped = true; }   // :1745
-            else {
-                if ((it + 1) % P.rho_change_step == 0) {                                                     // :1753-1770
-                    s->prev_rho1 = s->rho1; s->prev_rho2 = s->rho2;
-                    s->rho1 = P.learning_fact * s->rho1; s->rho2 = P.learning_fact * s->rho2;
-                    if (d.eq && d.ineq) { s->prev_rho3 = s->rho3; s->rho3 = P.learning_fact * s->rho3; }   // update_rho3: type 3 only (:1906, :2045)
-                    if (d.ineq) { s->prev_rho4 = s->rho4; s->rho4 = P.learning_fact * s->rho4; }
-                    const double g = s->gamma_val * P.gamma_factor;
-                    s->gamma_val = g < 1.0 ? 1.0 : g;
-                    s->rhoUpdated = 1; s->rcr = P.learning_fact - 1.0;
-                }
-                s->obj_val = d.red[3] + d.red[4];                                                            // :1772
-                const int H = P.history_size;
-                int hn = s->hist_n;
-                if (hn < H) s->hist[hn] = s->obj_val;
-                else { for (int k = 0; k < H - 1; k++) s->hist[k] = s->hist[k + 1]; s->hist[H - 1] = s->obj_val; }
-                if (hn < 0x3fffffff) hn++;
-                s->hist_n = hn;
-                if (hn >= H) {                                                                               // :482-507, :574-585
-                    double mean = 0;
-                    for (int k = 0; k < H; k++) mean += s->hist[k];
-                    mean /= (double)H;
-                    double dev = 0;
-                    for (int k = 0; k < H; k++) dev += (s->hist[k] - mean) * (s->hist[k] - mean);
-                    dev /= (double)(H - 1);
-                    const double sd = (dev == 0) ? 0.0 : sqrt(dev);
-                    s->std_obj = sd / fabs(s->hist[H - 1]);
-                }
-                if (s->std_obj <= P.std_threshold) { s->stop = GEN_STOP_OBJSTD; stopped = true; }             // :1777
-                else {
-                    s->cur_obj = d.red[5] + d.red[6];                                                        // :1786-1793
-                    if (s->best_bin_obj >= s->cur_obj) { s->best_bin_obj = s->cur_obj; s->copy_best = 1; }
-                }
-            }
-            if (stopped) s->halt = GEN_HALT_STOP;
-            else s->iter = it + 1;
+            gen_finish_iteration(s, P, d.red, it, d.eq, d.ineq);
         }
         if (!s->halt && s->iter >= P.max_iters) s->halt = GEN_HALT_END;
         if (!s->halt && do_prep) s->phase = 1;
@@ -192,7 +136,7 @@ __global__ void __launch_bounds__(T) gen_k_prep(GenDev d, int in, int out, int d
     for (int q = 0; q < d.EPT; q++) {
         const int j = blockIdx.x * (T * d.EPT) + q * T + threadIdx.x;
         double c = 0.0;
-        if (j < d.n) { const double u = (d.x[j] + d.z2[j] / rho2) - 0.5; c = u * u; }
+        if (j < d.n) { const double u = gen_y2_centre(d.x[j], d.z2[j], rho2); c = u * u; }
         pa[0] = pa[0] + c;
     }
     store_partials<1>(d, 0, pa, red, parity);
@@ -215,10 +159,8 @@ __global__ void __launch_bounds__(T) gen_k_y(GenDev d, int in, int out) {
             if (j >= d.n) continue;
             const double x = d.x[j], z1 = d.z1[j], z2 = d.z2[j];
             if (copy_best) d.best[j] = x;
-            const double t = x + z1 / rho1;
-            const double y1 = t > 1 ? 1 : (t < 0 ? 0 : t);                       // :1598-1601
-            double y2 = (x + z2 / rho2) - 0.5;                                   // :1603-1606, :553-558
-            y2 = y2 * c1 / c2 + 0.5;
+            const double y1 = gen_y1(x, z1, rho1);                               // :1598-1601
+            const double y2 = gen_y2(gen_y2_centre(x, z2, rho2), c1, c2);        // :1603-1606, :553-558
             d.y1[j] = y1; d.y2[j] = y2;
             double pd = d.pdiag[j];
             if (refresh) {
@@ -232,7 +174,7 @@ __global__ void __launch_bounds__(T) gen_k_y(GenDev d, int in, int out) {
                 const double dg = type == 0 ? d.tmval[d.adiag[j]] : pd;
                 d.dinv[j] = (dg != 0.0) ? 1.0 / dg : 1.0;
             }
-            d.rhs[j] = (rho1 * y1 + rho2 * y2) - ((d.b[j] + z1) + z2);            // :1656
+            d.rhs[j] = gen_rhs_base(rho1, y1, rho2, y2, d.b[j], z1, z2);            // :1656
             d.gsrc[j] = y1;                                                       // x_sol = y1 (:1721)
         }
     if (refresh) {                                                                // the scaled transposes (:1643, :1648)
@@ -245,8 +187,7 @@ __global__ void __launch_bounds__(T) gen_k_y(GenDev d, int in, int out) {
             const int i = blockIdx.x * (T * d.EPTl) + q * T + threadIdx.x;
             if (i >= d.l) continue;
             const double f = d.f[i];
-            const double v = f - d.Ex[i] - d.z4[i] / rho4;                        // :1609-1613
-            const double y3 = v < 0 ? 0 : v;
+            const double y3 = gen_y3(f, d.Ex[i], d.z4[i], rho4);                  // :1609-1613
             d.y3[i] = y3; d.fy[i] = f - y3;
         }
     if (LEADER) { d.st[out] = *si; d.st[out].rhoUpdated = 0; d.st[out].copy_best = 0; }

@@ -110,6 +110,14 @@ SYMBOLS = {
     "lpbox_bqp_solve": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "lpbox_bqp_get_vec": (C.c_int, [C.c_void_p, C.c_char_p, _dp, C.c_long]),
     "lpbox_bqp_get_scalar": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_double)]),
+    "lpbox_bqp_batch_create": (C.c_void_p, [C.c_int, C.c_int]),
+    "lpbox_bqp_batch_destroy": (None, [C.c_void_p]),
+    "lpbox_bqp_batch_preset": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "lpbox_bqp_batch_set_params": (C.c_int, [C.c_void_p, C.c_int, _dp]),
+    "lpbox_bqp_batch_set_problem": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 4),
+    "lpbox_bqp_batch_solve": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "lpbox_bqp_batch_get_vec": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, _dp, C.c_long]),
+    "lpbox_bqp_batch_get_scalar": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.POINTER(C.c_double)]),
 }
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p)
@@ -159,6 +167,8 @@ class LpboxError(RuntimeError):
 
 
 E_TOOLARGE = -9          # include/lpbox_hip.h: LPBOX_E_TOOLARGE
+E_STATE = -3             # LPBOX_E_STATE
+E_NODEVICE = -6          # LPBOX_E_NODEVICE
 
 
 def check(rc, what="lpbox call"):

@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import check
+from ._lib import LpboxError, check
 
 PRESET_UNCONSTRAINED, PRESET_EQ, PRESET_INEQ, PRESET_EQ_INEQ = 0, 1, 2, 3
 PARAM_NAMES = ("stop_threshold", "std_threshold", "gamma_val", "gamma_factor", "rho_change_step", "max_iters", "initial_rho",
@@ -135,3 +135,138 @@ def ADMM_bqp_linear_ineq(n, A, b, x0, l, E, f, **kw):
 
 def ADMM_bqp_linear_eq_and_uneq(n, A, b, x0, m, C_, d, l, E, f, **kw):
     return _run(n, A, b, x0, C_=C_, d=np.asarray(d)[:m], E=E, f=np.asarray(f)[:l], preset=PRESET_EQ_INEQ, **kw)
+
+
+# ---- many small problems at once (max(n, m, l) <= 2048 each): one persistent workgroup per problem ---------------------------------
+BATCH_MAX_DIM = 2048
+
+
+def _per_problem(value, count, what):
+    """None, one value for every problem, or a sequence with one entry per problem."""
+    if value is None:
+        return [None] * count
+    if isinstance(value, dict):
+        raise TypeError("%s: a single value or one per problem, not a dict" % what)
+    if what == "presets" and np.isscalar(value):
+        return [int(value)] * count
+    value = list(value)
+    if any(isinstance(v, dict) for v in value):
+        raise TypeError("%s: the 11 values in the order of bqp.PARAM_NAMES, not a dict" % what)
+    if what == "params" and value and all(np.isscalar(v) for v in value):       # one parameter vector for every problem
+        if len(value) != len(PARAM_NAMES):
+            raise ValueError("params: the %d values in the order of bqp.PARAM_NAMES" % len(PARAM_NAMES))
+        return [value] * count
+    if len(value) != count:
+        raise ValueError("%s: %d entries for %d problems" % (what, len(value), count))
+    if what == "params" and any(v is not None and len(v) != len(PARAM_NAMES) for v in value):
+        raise ValueError("params: the %d values in the order of bqp.PARAM_NAMES" % len(PARAM_NAMES))
+    return value
+
+
+class BqpBatch:
+    """A batch of independent small BQPs solved together; every problem gives the bits `BqpSolver` gives for it alone.
+
+    problems: a sequence of dicts with the keys n, A, b, x0 and optionally C, d, E, f (CSR triples or scipy.sparse matrices).
+    presets / params: None, a single value, or one per problem; the default preset follows the constraints present."""
+
+    def __init__(self, problems, presets=None, params=None, device=0):
+        problems = list(problems)
+        if not problems:
+            raise ValueError("BqpBatch: no problems")
+        count = len(problems)
+        presets = _per_problem(presets, count, "presets")
+        params = _per_problem(params, count, "params")
+        for P in problems:
+            if not isinstance(P, dict) or any(k not in P for k in ("n", "A", "b", "x0")):
+                raise TypeError("BqpBatch: every problem is a dict with the keys n, A, b, x0 (and C, d, E, f)")
+        self._L = _lib.load()
+        self.count = count
+        self.dims = []
+        self._h = None
+        h = self._L.lpbox_bqp_batch_create(count, int(device))
+        if not h:
+            msg = self._L.lpbox_last_error()
+            err = LpboxError("lpbox_bqp_batch_create failed: %s" % (msg.decode() if msg else ""))
+            err.code = _lib.E_NODEVICE if msg and b"no HIP device" in msg else -2
+            raise err
+        self._h = C.c_void_p(h)
+        try:
+            for i, P in enumerate(problems):
+                self._set(i, P, presets[i], params[i])
+        except Exception:
+            self.close()
+            raise
+
+    def _set(self, i, P, preset, params):
+        n = int(P["n"])
+        m = 0 if P.get("C") is None else len(P["d"])
+        l = 0 if P.get("E") is None else len(P["f"])
+        keep = []
+
+        def ptrs(M):
+            if M is None:
+                return [None, None, None]
+            keep.extend(M)
+            return [a.ctypes.data_as(C.c_void_p) for a in M]
+
+        def vec(v):
+            if v is None:
+                return None
+            a = np.ascontiguousarray(v, np.float64)
+            keep.append(a)
+            return a.ctypes.data_as(C.c_void_p)
+        A_ = _csr(P["A"], n)
+        if any(j not in A_[1][A_[0][j]:A_[0][j + 1]] for j in range(n)):
+            A_ = with_diagonal(A_[0], A_[1], A_[2], n)
+        args = [self._h, i, n] + ptrs(A_) + [vec(P["b"]), vec(P["x0"]), m] + ptrs(_csr(P.get("C"), m)) + [vec(P.get("d") if m else None), l] + \
+            ptrs(_csr(P.get("E"), l)) + [vec(P.get("f") if l else None)]
+        check(self._L.lpbox_bqp_batch_set_problem(*args), "lpbox_bqp_batch_set_problem")
+        ptype = (1 if m else 0) | (2 if l else 0)
+        check(self._L.lpbox_bqp_batch_preset(self._h, i, ptype if preset is None else int(preset)), "lpbox_bqp_batch_preset")
+        if params is not None:
+            check(self._L.lpbox_bqp_batch_set_params(self._h, i, np.ascontiguousarray(params, np.float64)), "lpbox_bqp_batch_set_params")
+        self.dims.append((n, m, l))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.lpbox_bqp_batch_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def solve(self):
+        it = np.zeros(self.count, np.int32)
+        check(self._L.lpbox_bqp_batch_solve(self._h, it.ctypes.data_as(C.c_void_p)), "lpbox_bqp_batch_solve")
+        return it
+
+    def vec(self, i, name):
+        out = np.zeros(BATCH_MAX_DIM)
+        k = check(self._L.lpbox_bqp_batch_get_vec(self._h, int(i), name.encode(), out, len(out)), "lpbox_bqp_batch_get_vec")
+        return out[:k].copy()
+
+    def scalar(self, i, name):
+        v = C.c_double()
+        check(self._L.lpbox_bqp_batch_get_scalar(self._h, int(i), name.encode(), C.byref(v)), "lpbox_bqp_batch_get_scalar")
+        return v.value
+
+    def solution(self, i):
+        """The same dict as `BqpSolver.solution`, for problem i."""
+        return dict(x_sol=self.vec(i, "x"), y1=self.vec(i, "y1"), y2=self.vec(i, "y2"), best_sol=self.vec(i, "best_sol"))
+
+
+def solve_many(problems, **kw):
+    """Solve a sequence of small problems in one batch; a list of the dicts the ADMM_bqp_* entry points return."""
+    s = BqpBatch(problems, **kw)
+    its = s.solve()
+    out = []
+    for i in range(s.count):
+        sol = s.solution(i)
+        sol.update(iterations=int(its[i]), stop=int(s.scalar(i, "stop")), best_bin_obj=s.scalar(i, "best_bin_obj"),
+                   time_elapsed_ms=s.scalar(0, "kernel_ms"))
+        out.append(sol)
+    s.close()
+    return out

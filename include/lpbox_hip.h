@@ -305,6 +305,25 @@ int lpbox_bqp_solve(lpbox_bqp_t *h, int *iterations);          /* the whole ADMM
 int lpbox_bqp_get_vec(lpbox_bqp_t *h, const char *name, double *out, long cap);   /* Solution (LPh): "x" (x_sol), "y1", "y2", "best_sol"; also "z1","z2","z3","z4","y3" */
 int lpbox_bqp_get_scalar(lpbox_bqp_t *h, const char *name, double *out);          /* "iters","stop" (1 xyy, 2 obj_std, 0 max_iters),"cur_obj","best_bin_obj","total_pcg",... */
 
+/* ---- a batch of SMALL generic constrained binary QPs (max(n, m, l) <= 2048 each), one persistent workgroup per problem -------------
+ * The same ADMM_bqp loop (SEGcpp:1384-1832: the y updates :1598-1613, the rho refresh :1619-1650, the PCG on the matrix expression
+ * :361-469, the duals :1733-1739, the stop tests and the rho / gamma schedule :1742-1794) solved for `count` independent problems in
+ * one launch per window of outer iterations.  The problems of a batch may differ in size, type and hyper-parameters.  Everything
+ * the getters return for a problem is bit for bit what lpbox_bqp_solve returns for it alone.  Validation and messages are those of
+ * lpbox_bqp_*; a problem with max(n, m, l) > 2048 is refused with LPBOX_E_TOOLARGE (use lpbox_bqp_* for it) and leaves the rest of
+ * the batch untouched.  No device: lpbox_bqp_batch_create returns NULL with LPBOX_E_NODEVICE in lpbox_last_error. */
+typedef struct lpbox_bqp_batch lpbox_bqp_batch_t;
+lpbox_bqp_batch_t *lpbox_bqp_batch_create(int count, int device);
+void lpbox_bqp_batch_destroy(lpbox_bqp_batch_t *h);
+int lpbox_bqp_batch_preset(lpbox_bqp_batch_t *h, int idx, int type);               /* the *_init presets (:587-672) of lpbox_bqp_preset; idx -1 = every problem */
+int lpbox_bqp_batch_set_params(lpbox_bqp_batch_t *h, int idx, const double *p11);  /* the 11 values of lpbox_bqp_set_params; idx -1 = every problem */
+int lpbox_bqp_batch_set_problem(lpbox_bqp_batch_t *h, int idx, int n, const int *Ap, const int *Ai, const double *Av, const double *b,
+                                const double *x0, int m, const int *Cp, const int *Ci, const double *Cv, const double *d,
+                                int l, const int *Ep, const int *Ei, const double *Ev, const double *f);
+int lpbox_bqp_batch_solve(lpbox_bqp_batch_t *h, int *iterations);                  /* ADMM_bqp (:1384-1832) for every problem, each to its own stop; iterations[count] may be NULL; LPBOX_E_STATE while an index is unset */
+int lpbox_bqp_batch_get_vec(lpbox_bqp_batch_t *h, int idx, const char *name, double *out, long cap);   /* the names of lpbox_bqp_get_vec */
+int lpbox_bqp_batch_get_scalar(lpbox_bqp_batch_t *h, int idx, const char *name, double *out);          /* the names of lpbox_bqp_get_scalar per problem; batch-wide (idx ignored): "kernel_ms","launches","threads","chunk","window","slots" */
+
 #ifdef __cplusplus
 }
 #endif

@@ -123,7 +123,18 @@ class EarlyFixPolicy:
             out[r0:r0 + self.chunk_rows] = self._chunk(x[r0:r0 + self.chunk_rows])
         return out
 
-    def _chunk(self, x):
+    @torch.no_grad()
+    def encode(self, x):
+        """The encoder alone: x (rows, tokens, 5) -> the flattened activations (rows, tokens*128) that the MLP head reads, in self.dtype."""
+        x = x.to(self.device, self.dtype)
+        if x.dim() != 3 or x.shape[1] != self.tokens or x.shape[2] != CODE_DIM:
+            raise ValueError("expected (rows, %d, %d), got %s" % (self.tokens, CODE_DIM, tuple(x.shape)))
+        out = torch.empty((x.shape[0], self.tokens * EMBED), device=self.device, dtype=self.dtype)
+        for r0 in range(0, x.shape[0], self.chunk_rows):
+            out[r0:r0 + self.chunk_rows] = self._encode_chunk(x[r0:r0 + self.chunk_rows])
+        return out
+
+    def _encode_chunk(self, x):
         R, T = x.shape[0], self.tokens
         hd = EMBED // N_HEADS
         h = (x.reshape(R * T, CODE_DIM) @ self.w_in).view(R, T, EMBED) + self.b_in
@@ -134,12 +145,15 @@ class EarlyFixPolicy:
             h = h * L["n1_s"] + L["n1_t"]
             h = h + (torch.relu(h.view(R * T, EMBED) @ L["w1"] + L["b1"]) @ L["w2"] + L["b2"]).view(R, T, EMBED)
             h = h * L["n2_s"] + L["n2_t"]
-        z = h.reshape(R, T * EMBED)
+        return h.reshape(R, T * EMBED)
+
+    def _chunk(self, x):
+        z = self._encode_chunk(x)
         for k, (w, b) in enumerate(self.head):
             z = z @ w + b
             if k < 3:
                 z = torch.relu(z)
-        return z.view(R).to(torch.float32)
+        return z.view(x.shape[0]).to(torch.float32)
 
     def __call__(self, x):
         return torch.sigmoid(self.logits(x))

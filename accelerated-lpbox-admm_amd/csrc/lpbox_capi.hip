@@ -1506,6 +1506,23 @@ int lpbox_debug_get_scalar(lpbox_t *h, int idx, const char *name, double *out) {
     return fail(LPBOX_E_BADARG, "unknown scalar '%s'", name);
 }
 
+int lpbox_debug_block_sum(int threads, int nv, int stage, int groups, int rounds, const double *in, double *out) {
+    if (!in || !out || groups <= 0 || groups > 1024 || rounds <= 0 || rounds > 1024) return fail(LPBOX_E_BADARG, "lpbox_debug_block_sum: bad argument");
+    if (lpbox_device_count() < 1) return fail(LPBOX_E_NODEVICE, "no HIP device");
+    HIPCHK(hipSetDevice(g_device));
+    const size_t per = (size_t)rounds * threads * nv;
+    struct Scratch : DevBuf<double> { ~Scratch() { release(); } } din, dout;     // freed on every return path
+    HIPCHK(din.alloc(per));
+    HIPCHK(dout.alloc(per * groups));
+    HIPCHK(hipMemcpy(din.p, in, per * sizeof(double), hipMemcpyHostToDevice));
+    hipError_t e = lp_launch_debug_block_sum(threads, nv, stage, groups, rounds, din.p, dout.p, nullptr);
+    if (e == hipErrorInvalidConfiguration) return fail(LPBOX_E_BADARG, "lpbox_debug_block_sum: no kernel for %d threads, %d values, stage %d", threads, nv, stage);
+    HIPCHK(e);
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out, dout.p, per * groups * sizeof(double), hipMemcpyDeviceToHost));
+    return LPBOX_OK;
+}
+
 // ---- segmentation flavour (SEG pxd = Segmentation/Segmentation/cython/src/LPboxADMMsolver.pxd) ----
 static int seg_handle(lpbox_t *h) {
     if (!valid_handle(h)) return fail(LPBOX_E_BADHANDLE, "bad handle");

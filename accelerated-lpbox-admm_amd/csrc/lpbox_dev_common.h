@@ -85,11 +85,41 @@ __device__ __forceinline__ int wave_max_int(int v) {
 constexpr int RED_MAXV = 6;    // values reduced together
 constexpr int RED_MAXW = 16;   // waves per workgroup
 
+// Second stage of block_sum (how the W wave partials of a value get from LDS into every lane), chosen per caller.
+// Both forms add in the same tree over the wave index -- pairs (0,1) (2,3) ..., quads, eight -- so they give the same bits.
+constexpr int RED_STAGE_BCAST = 0;   // every lane reads all W partials (broadcast reads) and adds them in registers: the default
+constexpr int RED_STAGE_PAIRS = 1;   // W = 8: lane reads the pair (p[2j], p[2j+1]), j = lane & 3, with one ds_read_b128 per value
+                                     // and adds it (the tree's "pairs" level); two quad_perm steps finish the tree
+
+// First stage of RED_STAGE_PAIRS: the wave butterflies of block_sum, then ONE predicated store per butterfly -- the first lane
+// of every row of 16 lanes writes what its row holds (rows [v0, v2, v1, v3]; with fewer than four values a row that repeats a value
+// writes it to a slot nobody reads), instead of one exec-mask region per value.
+template <int NV>
+__device__ __forceinline__ void wave_partials_store(const double *v, double *buf, int lane, int w) {
+    const int row = lane >> 4, k = ((row & 1) << 1) | (row >> 1);    // value index of this lane's row after wave_reduce_scatter<3 or 4>;
+    const bool owner = (lane & 15) == 0;                              // after <2> rows 0, 1 hold value 0 and rows 2, 3 value 1: slots 0, 2, 1, 3
+    double *at = buf + k * RED_MAXW + w;                         // loop-invariant up to the parity offset
+    if constexpr (NV == 1) {
+        const double t0 = wave_allreduce_sum(v[0]);                   // every lane holds it: the slots of k = 1..3 get copies
+        if (owner) *at = t0;
+    } else {
+        constexpr int NS4 = NV > 4 ? 4 : NV;
+        const double sc = wave_reduce_scatter<NS4>(v);
+        if constexpr (NV == 6) {                                      // values 4 and 5 share a second butterfly: halves [v4, v5]
+            const double sc2 = wave_reduce_scatter<2>(v + 4);
+            if (owner) { *at = sc; buf[(4 + (k & 1)) * RED_MAXW + w] = sc2; }
+        } else {
+            static_assert(NV <= 4, "1, 2, 3, 4 or 6 values");
+            if (owner) *at = sc;
+        }
+    }
+}
+
 // Sum NV per-thread partials over the workgroup; every thread receives the totals.  Wave partials go through LDS and
 // are combined by a second butterfly (lane i reads partial i mod W; balanced tree over the wave index), i.e. ONE LDS
-// round trip instead of W dependent reads.  `red` is a ping-pong scratch (2 * RED_MAXV * RED_MAXW doubles): a thread
+// round trip instead of W dependent reads.  `red` is a ping-pong scratch (2 * RED_MAXV * RED_MAXW doubles, 16-byte aligned): a thread
 // can run at most one block_sum ahead of the slowest one.
-template <int T, int NV>
+template <int T, int NV, int STAGE = RED_STAGE_BCAST>
 __device__ __forceinline__ void block_sum(double (&v)[NV], double *red, int &parity) {
     constexpr int W = T / 64;
     static_assert(W == 1 || W == 2 || W == 4 || W == 8 || W == 16, "waves per workgroup");
@@ -100,6 +130,23 @@ __device__ __forceinline__ void block_sum(double (&v)[NV], double *red, int &par
     }
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     double *buf = red + parity * (RED_MAXV * RED_MAXW);
+    if constexpr (STAGE != RED_STAGE_BCAST) {
+        static_assert(W == 8 && STAGE == RED_STAGE_PAIRS, "built for eight waves");
+        wave_partials_store<NV>(v, buf, lane, w);
+        __syncthreads();
+        double2 t[NV];
+#pragma unroll
+        for (int k = 0; k < NV; k++) t[k] = *(const double2 *)(buf + k * RED_MAXW + 2 * (lane & 3));
+#pragma unroll
+        for (int k = 0; k < NV; k++) {
+            double u = t[k].x + t[k].y;                  // waves (0,1) (2,3) (4,5) (6,7)
+            u = u + dpp_mov<0xB1>(u);                    // quads of waves
+            u = u + dpp_mov<0x4E>(u);                    // eight
+            v[k] = u;
+        }
+        parity ^= 1;
+        return;
+    }
     if constexpr (NV == 1) {
         const double t0 = wave_allreduce_sum(v[0]);
         if (lane == 0) buf[w] = t0;
@@ -130,20 +177,6 @@ __device__ __forceinline__ void block_sum(double (&v)[NV], double *red, int &par
         parity ^= 1;
         return;
     }
-#ifdef LPBOX_STAGE2_DPP
-    double t[NV];
-#pragma unroll
-    for (int k = 0; k < NV; k++) t[k] = buf[k * RED_MAXW + (lane & (W - 1))];
-#pragma unroll
-    for (int k = 0; k < NV; k++) {
-        double u = t[k];
-        u = u + dpp_mov<0xB1>(u);                    // waves (0,1) (2,3) ...
-        if (W >= 4) u = u + dpp_mov<0x4E>(u);        // quads of waves
-        if (W >= 8) u = u + dpp_mov<0x141>(u);       // 8 waves
-        if (W >= 16) u = u + dpp_mov<0x140>(u);      // 16 waves
-        v[k] = u;
-    }
-#else
     // every lane reads all W wave partials (same address in all lanes: an LDS broadcast) and adds them in registers in the
     // balanced tree over the wave index -- pairs (0,1) (2,3) ..., quads, ... -- i.e. the association of the xor butterfly the
     // first version ran on DPP (floating-point addition is commutative, so the bits are identical), without its dependent
@@ -161,7 +194,6 @@ __device__ __forceinline__ void block_sum(double (&v)[NV], double *red, int &par
             for (int w2 = 0; w2 < W; w2 += 2 * span) t[k][w2] = t[k][w2] + t[k][w2 + span];
         v[k] = t[k][0];
     }
-#endif
     parity ^= 1;
 }
 

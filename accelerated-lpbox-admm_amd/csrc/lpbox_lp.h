@@ -86,6 +86,8 @@ hipError_t lp_launch_init(const LpBatchDev &bd, int T, int EPT, const double *f_
                           const uint8_t *live_init, hipStream_t s);
 hipError_t lp_launch_window(const LpBatchDev &bd, int T, int EPT, size_t lds, int iter_start, int iter_end, int l2f,
                             hipStream_t s, bool direct = false, bool log = false);
+// lpbox_debug_block_sum: block_sum<T, NV, stage> `rounds` times in `groups` workgroups; hipErrorInvalidConfiguration = not compiled
+hipError_t lp_launch_debug_block_sum(int T, int NV, int stage, int groups, int rounds, const double *in, double *out, hipStream_t s);
 bool lp_log_supported(int T, int EPT);         // geometries the logging variant is compiled for (the default ones: 512 threads)
 bool lp_direct_supported(int T, int EPT);      // geometries the DIRECT variant is compiled for
 // opt-in reference-order kernels (lpbox_lp_ref_kernels.hip, lpbox_set_order): identity layout, 512 threads, EPT = 1, 2 or 4

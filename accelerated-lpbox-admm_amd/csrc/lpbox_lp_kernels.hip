@@ -85,6 +85,11 @@ struct LdsLayout {
 // register-lean variants (cold vectors in memory / LDS): the multi-slot ones and every 16-wave geometry (128 registers per lane)
 __host__ __device__ constexpr bool lp_is_lean(int T, int EPT) { return EPT >= 4 || T == 1024; }
 
+// second stage of block_sum per geometry of lp_window_kernel (each measured on its own)
+__host__ __device__ constexpr int lp_red_stage(int T, int EPT) {
+    return T == 512 && EPT == 1 ? RED_STAGE_PAIRS : RED_STAGE_BCAST;     // (512 x 4: 81.5 vs 77.4 us per iteration with PAIRS, it keeps the default)
+}
+
 typedef __attribute__((address_space(3))) double lds_double;
 
 __device__ __forceinline__ unsigned lds_addr(const void *p) {
@@ -439,6 +444,7 @@ struct RowVec {
 template <int T, int EPT, typename RCAPS, typename CCAPS, typename HCAPS, bool DIRECT = false, bool LOG = false>
 __global__ void __launch_bounds__(T) lp_window_kernel(LpBatchDev bd, int iter_start, int iter_end, int mode) {
     const int l2f = mode & 1, rec = mode & 2;     // rec: keep x after every iteration in xhist (x_iters of the l2f loop; print_fix_info 2/3 of the plain loop)
+    constexpr int RS = (DIRECT || LOG) ? RED_STAGE_BCAST : lp_red_stage(T, EPT);    // second stage of every block_sum of this kernel
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int inst = blockIdx.x, tid = threadIdx.x;
     int *isc = bd.isc + (size_t)inst * NI_COUNT;
@@ -661,7 +667,7 @@ __global__ void __launch_bounds__(T) lp_window_kernel(LpBatchDev bd, int iter_st
             part[0] = part[0] + (nf[s] ? b.get(s) * val : 0.0);     // fix_obj = b2.dot(x2), :1237
             gx[pos] = nf[s] ? val : 0.0;
         }
-        block_sum<T, 1>(part, red, parity);                      // (barrier inside also publishes gx)
+        block_sum<T, 1, RS>(part, red, parity);                      // (barrier inside also publishes gx)
         fix_obj = part[0];
         if (n_live_new == 0) {                                   // :1212-1217 (nothing else is updated)
             ret = 1; stop = LP_STOP_ALLFIXED; n_live = 0; finished = true;
@@ -678,7 +684,7 @@ __global__ void __launch_bounds__(T) lp_window_kernel(LpBatchDev bd, int iter_st
             double px[1] = {0.0};
 #pragma unroll
             for (int s = 0; s < EPT; s++) px[0] = px[0] + (live[s] ? x[s] * x[s] : 0.0);
-            block_sum<T, 1>(px, red, parity);
+            block_sum<T, 1, RS>(px, red, parity);
             if (sqrt(px[0]) < 1e-3) ret = 1;                          // :1223
             prev_sum = sum_fix_obj; sum_fix_obj += fix_obj; prev_obj = cur_obj;   // :1247-1250
             n_live = n_live_new;
@@ -749,7 +755,7 @@ __global__ void __launch_bounds__(T) lp_window_kernel(LpBatchDev bd, int iter_st
         double pnorm;
         {
             double pn[1] = {prepare(rho1, rho2, rho4)};
-            block_sum<T, 1>(pn, red, parity);                         // (its barrier publishes the l-vectors and the start vector)
+            block_sum<T, 1, RS>(pn, red, parity);                         // (its barrier publishes the l-vectors and the start vector)
             pnorm = pn[0];
         }
 
@@ -935,7 +941,7 @@ __global__ void __launch_bounds__(T) lp_window_kernel(LpBatchDev bd, int iter_st
                 p3[1] = p3[1] + (live[s] ? r[s] * r[s] : 0.0);        // residualNorm2 :282
                 p3[2] = p3[2] + (live[s] ? r[s] * p[s] : 0.0);        // absNew :294
             }
-            block_sum<T, 3>(p3, red, parity);
+            block_sum<T, 3, RS>(p3, red, parity);
             STAMP(2)
             const double rhsNorm2 = p3[0];
             double residualNorm2 = p3[1], absNew = p3[2];
@@ -991,7 +997,7 @@ __global__ void __launch_bounds__(T) lp_window_kernel(LpBatchDev bd, int iter_st
                         }
                         STAMP(6)
 #ifndef LPBOX_KO_RED1
-                        block_sum<T, 1>(p1, red, parity);
+                        block_sum<T, 1, RS>(p1, red, parity);
 #endif
                         STAMP(7)
 #ifdef LPBOX_KO_DIV
@@ -1012,7 +1018,7 @@ __global__ void __launch_bounds__(T) lp_window_kernel(LpBatchDev bd, int iter_st
                         }
                         STAMP(8)
 #ifndef LPBOX_KO_RED2
-                        block_sum<T, 2>(p2, red, parity);
+                        block_sum<T, 2, RS>(p2, red, parity);
 #endif
                         STAMP(9)
                         residualNorm2 = p2[0];
@@ -1113,8 +1119,8 @@ __global__ void __launch_bounds__(T) lp_window_kernel(LpBatchDev bd, int iter_st
                 p5[4] = p5[4] + (live[s] ? b.get(s) * xb : 0.0);
             }
             STAMP_POST(12)
-            block_sum<T, 6>(p5, red, parity);
-            if constexpr (LOG) block_sum<T, 6>(lg, red, parity);
+            block_sum<T, 6, RS>(p5, red, parity);
+            if constexpr (LOG) block_sum<T, 6, RS>(lg, red, parity);
             pnorm = p5[5];
             STAMP_POST(13)
             {
@@ -1250,7 +1256,38 @@ __global__ void lp_pack_xiters_kernel(LpBatchDev bd, const int *live_pos, const 
     }
 }
 
+// lpbox_debug_block_sum: `rounds` block_sums back to back on the same scratch (so the parity halves are reused), what EVERY thread
+// received goes out.  in[(r * T + t) * NV + k] is thread t's partial of value k in round r, the same for every workgroup.
+template <int T, int NV, int STAGE>
+__global__ void __launch_bounds__(T) debug_block_sum_kernel(const double *in, double *out, int rounds) {
+    __shared__ __attribute__((aligned(16))) double red[2 * RED_MAXV * RED_MAXW];
+    const int tid = threadIdx.x;
+    int parity = 0;
+    for (int r = 0; r < rounds; r++) {
+        double v[NV];
+#pragma unroll
+        for (int k = 0; k < NV; k++) v[k] = in[((size_t)r * T + tid) * NV + k];
+        block_sum<T, NV, STAGE>(v, red, parity);
+#pragma unroll
+        for (int k = 0; k < NV; k++) out[(((size_t)blockIdx.x * rounds + r) * T + tid) * NV + k] = v[k];
+    }
+}
+
 }  // namespace
+
+hipError_t lp_launch_debug_block_sum(int T, int NV, int stage, int groups, int rounds, const double *in, double *out, hipStream_t s) {
+#define CALL_DBG(TT, VV, SS)                                                                                             \
+    if (T == TT && NV == VV && stage == SS) {                                                                           \
+        hipLaunchKernelGGL((debug_block_sum_kernel<TT, VV, SS>), dim3(groups), dim3(TT), 0, s, in, out, rounds);      \
+        return hipGetLastError();                                                                                     \
+    }
+#define CALL_DBG_NV(TT, SS) CALL_DBG(TT, 1, SS) CALL_DBG(TT, 2, SS) CALL_DBG(TT, 3, SS) CALL_DBG(TT, 6, SS)
+    CALL_DBG_NV(256, RED_STAGE_BCAST) CALL_DBG_NV(512, RED_STAGE_BCAST) CALL_DBG_NV(1024, RED_STAGE_BCAST)
+    CALL_DBG_NV(512, RED_STAGE_PAIRS)
+#undef CALL_DBG_NV
+#undef CALL_DBG
+    return hipErrorInvalidConfiguration;
+}
 
 // ------------------------------------------------------------------------------------------------
 // launchers

@@ -237,6 +237,12 @@ int lpbox_kernel_time(lpbox_t *h, double *ms_total, long long *launches, int res
 /* Copy a named device state vector of instance idx ("x","z1","z2","z4","f","pd","b"); returns its length. */
 int lpbox_debug_get_vec(lpbox_t *h, int idx, const char *name, double *out, int cap);
 int lpbox_debug_get_scalar(lpbox_t *h, int idx, const char *name, double *out);
+/* Test entry for the workgroup reduction of the LP kernels (no solver state, used by no product path): `groups` workgroups of `threads`
+ * threads each call the reduction `rounds` times back to back on one scratch area.  in[(r * threads + t) * nv + k] is thread t's
+ * partial of value k in round r (the same for every workgroup); out[((g * rounds + r) * threads + t) * nv + k] is what thread t of
+ * workgroup g received.  stage: 0 = the default second stage (threads 256 / 512 / 1024), 1 = the one the 512-thread window kernel
+ * runs (threads 512); nv = 1, 2, 3 or 6.  Anything else: LPBOX_E_BADARG. */
+int lpbox_debug_block_sum(int threads, int nv, int stage, int groups, int rounds, const double *in, double *out);
 
 /* ---- LARGE single LP, variable-sharded over ranks (BASELINE config 5; no reference counterpart: the reference is one
  * process).  Rank r holds the columns [c0, c0+n_loc) of E (all l rows), its slice of b, and the full f; the l-vectors are

@@ -21,6 +21,7 @@ namespace {
 
 thread_local std::string g_err;
 thread_local int g_device = 0;
+thread_local int g_status = 0;        // the code that came with g_err
 
 int fail(int code, const char *fmt, ...) {
     char buf[512];
@@ -28,7 +29,7 @@ int fail(int code, const char *fmt, ...) {
     va_start(ap, fmt);
     vsnprintf(buf, sizeof(buf), fmt, ap);
     va_end(ap);
-    g_err = buf;
+    g_err = buf; g_status = code;
     return code;
 }
 
@@ -40,7 +41,7 @@ int lpbox_fail(int code, const char *fmt, ...) {
     va_start(ap, fmt);
     vsnprintf(buf, sizeof(buf), fmt, ap);
     va_end(ap);
-    g_err = buf;
+    g_err = buf; g_status = code;
     return code;
 }
 
@@ -693,6 +694,7 @@ extern "C" {
 
 const char *lpbox_version(void) { return "lpbox_hip 0.1 (gfx950)"; }
 const char *lpbox_last_error(void) { return g_err.c_str(); }
+int lpbox_last_status(void) { return g_status; }
 
 int lpbox_device_count(void) {
     int cnt = 0;
@@ -1558,6 +1560,38 @@ int lpbox_seg_legacy_batch(lpbox_t **hs, int count, int *energies) {
         ss[i] = hs[i]->seg;
     }
     return segc_legacy_batch(ss.data(), count, energies);
+}
+
+// ---- early-fixing windows for a batch of segmentation handles (lpbox_seg_capi.hip) ----
+lpbox_seg_batch_t *lpbox_seg_batch_create(lpbox_t **hs, int count) {
+    if (!hs || count <= 0) { fail(LPBOX_E_BADARG, "empty batch"); return nullptr; }
+    std::vector<SegSolver *> ss(count);
+    for (int i = 0; i < count; i++) {
+        if (!valid_handle(hs[i])) { fail(LPBOX_E_BADHANDLE, "problem %d of the batch is not a handle", i); return nullptr; }
+        if (!hs[i]->seg) { fail(LPBOX_E_STATE, "problem %d of the batch is an LP-flavour handle", i); return nullptr; }
+        ss[i] = hs[i]->seg;
+    }
+    return segbc_create(ss.data(), count);                         // NULL: refused, lpbox_last_status() / lpbox_last_error() say why
+}
+
+void lpbox_seg_batch_destroy(lpbox_seg_batch_t *b) { segbc_destroy(b); }
+
+#define SEG_BATCH_OR_FAIL(b) do { if (!(b)) return fail(LPBOX_E_BADHANDLE, "bad batch handle"); } while (0)
+int lpbox_seg_batch_init(lpbox_seg_batch_t *b) { SEG_BATCH_OR_FAIL(b); return segbc_init(b); }
+int lpbox_seg_batch_set_active(lpbox_seg_batch_t *b, const unsigned char *active) { SEG_BATCH_OR_FAIL(b); return segbc_set_active(b, active); }
+int lpbox_seg_batch_iterate_l2f(lpbox_seg_batch_t *b, int iter_start, int iter_end, const double *vecs, long vec_stride, const int *nums,
+                                int *rets) {
+    SEG_BATCH_OR_FAIL(b);
+    return segbc_l2f(b, iter_start, iter_end, vecs, vec_stride, nums, rets);
+}
+int lpbox_seg_batch_get_x_iters_device(lpbox_seg_batch_t *b, int ws, void **dev_ptr, long *row_off) {
+    SEG_BATCH_OR_FAIL(b);
+    return segbc_get_x_iters_device(b, ws, dev_ptr, row_off);
+}
+int lpbox_seg_batch_iterate_l2f_scores(lpbox_seg_batch_t *b, int iter_start, int iter_end, const float *scores_dev, double hi, double lo,
+                                       int min_fix, int *rets, int *fixed) {
+    SEG_BATCH_OR_FAIL(b);
+    return segbc_l2f_scores(b, iter_start, iter_end, scores_dev, hi, lo, min_fix, rets, fixed);
 }
 
 int lpbox_seg_get_obj(lpbox_t *h, double *out) {

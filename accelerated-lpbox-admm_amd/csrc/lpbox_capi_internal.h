@@ -32,3 +32,14 @@ int segc_kernel_time(SegSolver *s, double *ms, long long *launches, int reset);
 int segc_debug_vec(SegSolver *s, const char *name, double *out, int cap);
 int segc_debug_scalar(SegSolver *s, const char *name, double *out);
 int segc_get_problem(SegSolver *s, int *n, int *nnz, int *rowptr, int *colidx, double *vals, double *b, double *c);
+
+// early-fixing windows for a batch of segmentation handles (lpbox_seg_batch_*; the handles are borrowed)
+struct lpbox_seg_batch;
+lpbox_seg_batch *segbc_create(SegSolver **ss, int count);
+void segbc_destroy(lpbox_seg_batch *b);
+int segbc_init(lpbox_seg_batch *b);
+int segbc_set_active(lpbox_seg_batch *b, const unsigned char *active);
+int segbc_l2f(lpbox_seg_batch *b, int iter_start, int iter_end, const double *vecs, long vec_stride, const int *nums, int *rets);
+int segbc_l2f_scores(lpbox_seg_batch *b, int iter_start, int iter_end, const float *scores_dev, double hi, double lo, int min_fix,
+                     int *rets, int *fixed);
+int segbc_get_x_iters_device(lpbox_seg_batch *b, int ws, void **dev_ptr, long *row_off);

@@ -67,12 +67,16 @@ struct SegDev {
     double *x, *y1, *y2, *z1, *z2, *b, *rhs, *r, *z, *tmp, *dinv, *td, *p0, *p1;
     uint8_t *live;          // 1 live, 0 fixed (x = 0 there; the fixed value is kept in fixval)
     uint8_t *fixval;
-    const uint8_t *newfix;  // consumed by the fix kernel: 0 none, 1 fix to 0, 2 fix to 1
+    uint8_t *newfix;        // consumed (and, in a batch, cleared) by the fix kernels: 0 none, 1 fix to 0, 2 fix to 1
     double *part;           // [phase(5)][SEG_NPART][Gmax]
     double *xhist; int ws_cap;
     SegState *st;           // st[0], st[1] ping-pong
     double c1_init;         // pow(n, 1/2) for the batched init (SEGcpp:557,670)
 };
+
+// batched early fixing: what the host decides per problem from the device's counts, and where a problem's rows sit
+struct SegFixPar { int apply, n_live_new; double c1_new; };   // apply 0: fix nothing (newfix cleared); n_live_new 0: SEG_HALT_ALLFIXED
+struct SegBatchAux { int *left; int row0, rows; };            // live list (original indices, ascending), first packed row, live count
 
 hipError_t seg_launch_init(const SegDev &d, double c1, hipStream_t s);
 // Every launch below reads st[*parity], writes st[*parity ^ 1] and flips *parity.
@@ -96,3 +100,10 @@ hipError_t segb_enqueue_iterations(const SegDev *devs, int B, int Gmax, int iter
 hipError_t segb_enqueue_pcg_more(const SegDev *devs, int B, int Gmax, int pairs, int *parity, hipStream_t s);
 hipError_t segb_enqueue_finalize(const SegDev *devs, int B, int Gmax, int *parity, hipStream_t s);
 hipError_t segb_collect_states(const SegDev *devs, int B, int parity, SegState *out, hipStream_t s);
+// early-fixing windows of a batch: decide (scores -> newfix codes + counts[2 B] = ones, zeros per problem), fix (also clears the staged
+// x_iters columns), compact (aux.left keeps the unfixed entries in order, aux.rows = live count BEFORE the fix), pack (x_iters rows)
+hipError_t segb_launch_decide(const SegDev *devs, const SegBatchAux *aux, int B, int max_rows, const float *scores, double hi, double lo,
+                              int *counts, hipStream_t s);
+hipError_t segb_launch_fix(const SegDev *devs, const SegFixPar *par, int B, int Gmax, int *parity, hipStream_t s);
+hipError_t segb_launch_compact(const SegDev *devs, const SegBatchAux *aux, const SegFixPar *par, int B, hipStream_t s);
+hipError_t segb_launch_pack_xiters(const SegDev *devs, const SegBatchAux *aux, int B, int max_rows, int ws, double *out, hipStream_t s);

@@ -38,6 +38,9 @@ struct SegSolver {
     std::vector<double> vals, orgb;
     std::vector<int> left_idx, xi_left_idx;   // original indices of the live variables (ascending)
     int xi_rows = 0;
+    bool left_stale = false;     // a batched window fixed on the device: d_left is current, left_idx is refreshed from it on demand
+    bool dleft_valid = false;    // d_left holds the live list (false between an init and the first early-fixing window)
+    long win_serial = 0;         // inits and early-fixing windows run so far (a batch's packed rows belong to one of them)
     bool has_problem = false, uploaded = false, inited = false, xi_valid = false;
     int G = 0, EPT = 2, kmax = 10, parity = 0;
     hipStream_t stream = nullptr;
@@ -342,6 +345,67 @@ int run_window(SegSolver *s, int iter_end) {
     return LPBOX_OK;
 }
 
+// the host copy of the live list after device-side fixes (batched windows compact d_left on the device)
+int refresh_left(SegSolver *s) {
+    if (!s->left_stale) return LPBOX_OK;
+    s->left_idx.resize((size_t)s->hst.n_live);
+    if (!s->left_idx.empty())
+        HIPCHK(hipMemcpy(s->left_idx.data(), s->d_left.p, sizeof(int) * s->left_idx.size(), hipMemcpyDeviceToHost));
+    s->left_stale = false;
+    return LPBOX_OK;
+}
+
+// the host side of segc_init for a member of a batch: upload, b, identity live list (the init KERNEL runs batched)
+int batch_reset_handle(SegSolver *s) {
+    int rc = s->uploaded ? use_device(s) : upload(s);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(s->b.p, s->orgb.data(), sizeof(double) * (size_t)s->n, hipMemcpyHostToDevice, s->stream));
+    s->left_idx.resize(s->n);
+    for (int k = 0; k < s->n; k++) s->left_idx[k] = k;
+    s->left_stale = false; s->dleft_valid = false; s->win_serial++;
+    return LPBOX_OK;
+}
+
+// The lockstep chain of a batch (devs = device array of B descriptors, the window already set): iterations up to iter_end for every
+// problem, each on its own control state -- one that has stopped, is all fixed or whose PCG has converged falls through, a
+// SEG_HALT_PCG_MORE on any problem resumes the chain.  hs[B] receives the final states; *kmax carries the adaptive launch count.
+int batch_run_chain(const SegDev *devs, SegState *dstates, int B, int Gmax, int iter_end, int *parity, int *kmax, bool adaptive,
+                    SegState *hs, long long *launches, hipStream_t st) {
+    // spare (matvec, update) pairs per iteration beyond the largest PCG count any problem showed in the previous batch of iterations: 0, as
+    // in the single-problem chain (a miss halts that problem's PCG and the chain resumes it).  Measured, 100 problems at 10^4 nodes, fastest
+    // / median of five runs: margin 2 119 / 120 ms, margin 1 111 / 112 ms, margin 0 108 / 108 ms; 16 problems 46 -> 41 ms.
+    static const int bmargin = getenv("LPBOX_SEG_KMARGIN") ? std::max(0, atoi(getenv("LPBOX_SEG_KMARGIN"))) : 0;
+    for (;;) {
+        HIPCHK(segb_collect_states(devs, B, *parity, dstates, st));
+        HIPCHK(hipMemcpyAsync(hs, dstates, sizeof(SegState) * (size_t)B, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        bool more = false, any_run = false;
+        int remaining = 0, pcg_max = 0, pcg_k = 0;
+        for (int i = 0; i < B; i++) {
+            const SegState &h = hs[i];
+            if (h.halt == SEG_HALT_PCG_MORE) { more = true; pcg_k = std::max(pcg_k, h.pcg_k); continue; }
+            if (h.halt != SEG_HALT_NONE) continue;
+            const int rem = iter_end - h.iter;
+            if (rem <= 0 && !h.have_prev) continue;
+            any_run = true; remaining = std::max(remaining, rem); pcg_max = std::max(pcg_max, h.outer_total > 0 ? h.pcg_max : *kmax - bmargin);
+        }
+        if (more) {                                                 // some PCG ran out of launches: resume it (the others fall through)
+            HIPCHK(segb_enqueue_pcg_more(devs, B, Gmax, 16, parity, st));
+            *launches += 34;
+            if (adaptive) *kmax = std::min(SEG_KMAX_LIMIT, std::max(*kmax, pcg_k + 4));
+            continue;
+        }
+        if (!any_run) break;
+        if (adaptive) *kmax = std::min(SEG_KMAX_LIMIT, std::max(2, pcg_max + bmargin));
+        HIPCHK(segb_launch_copy(devs, B, 1, parity, st));
+        const int batch = std::min(std::max(remaining, 0), 32);
+        if (batch > 0) HIPCHK(segb_enqueue_iterations(devs, B, Gmax, batch, *kmax, parity, st));
+        HIPCHK(segb_enqueue_finalize(devs, B, Gmax, parity, st));
+        *launches += 2 + (long long)batch * (4 + 2 * *kmax);
+    }
+    return LPBOX_OK;
+}
+
 }  // namespace
 
 SegSolver *segc_create(int print_info, int device) {
@@ -410,6 +474,7 @@ int segc_init(SegSolver *s) {
     HIPCHK(hipMemcpyAsync(s->b.p, s->orgb.data(), sizeof(double) * (size_t)s->n, hipMemcpyHostToDevice, s->stream));
     s->left_idx.resize(s->n);
     for (int i = 0; i < s->n; i++) s->left_idx[i] = i;
+    s->left_stale = false; s->dleft_valid = false; s->win_serial++;
     s->xi_valid = false; s->parity = 0;
     HIPCHK(seg_launch_init(s->dev(), std::pow((double)s->n, 1.0 / 2), s->stream));    // pow(n, 1/p), p = 2 (SEGcpp:557,670)
     rc = read_state(s);
@@ -431,7 +496,7 @@ int segc_legacy(SegSolver *s, int *energy) {                                  //
     rc = run_window(s, SEG_MAX_ITERS);
     if (rc) return rc;
     s->rec_cols = s->record > 0 ? std::min(s->hst.cc, s->ws_cap) : 0;
-    s->xi_valid = false;
+    s->xi_valid = false; s->win_serial++;
     if (energy) *energy = (int)(s->hst.cur_obj + s->c);                        // :1379
     return LPBOX_OK;
 }
@@ -455,13 +520,8 @@ int segc_legacy_batch(SegSolver **ss, int B, int *energies) {
     int rc = LPBOX_OK;
     int Gmax = 0;
     for (int i = 0; i < B; i++) {                                   // upload + host-side reset of segc_init (the init KERNEL runs batched)
-        SegSolver *s = ss[i];
-        rc = s->uploaded ? use_device(s) : upload(s);
-        if (rc) return rc;
-        HIPCHK(hipMemcpyAsync(s->b.p, s->orgb.data(), sizeof(double) * (size_t)s->n, hipMemcpyHostToDevice, s->stream));
-        s->left_idx.resize(s->n);
-        for (int k = 0; k < s->n; k++) s->left_idx[k] = k;
-        Gmax = std::max(Gmax, s->G);
+        if ((rc = batch_reset_handle(ss[i]))) return rc;
+        Gmax = std::max(Gmax, ss[i]->G);
     }
     for (int i = 0; i < B; i++) HIPCHK(hipStreamSynchronize(ss[i]->stream));
     hipStream_t st = s0->stream;
@@ -474,47 +534,11 @@ int segc_legacy_batch(SegSolver **ss, int B, int *energies) {
     std::vector<SegState> hs(B);
     int parity = 0, kmax = s0->kmax;
     long long launches = 0;
-    auto read_states = [&]() -> int {
-        HIPCHK(segb_collect_states(devs.p, B, parity, dstates.p, st));
-        HIPCHK(hipMemcpyAsync(hs.data(), dstates.p, sizeof(SegState) * (size_t)B, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        return LPBOX_OK;
-    };
-    // spare (matvec, update) pairs per iteration beyond the largest PCG count any problem showed in the previous batch of iterations: 0, as
-    // in the single-problem chain (a miss halts that problem's PCG and the chain resumes it).  Measured, 100 problems at 10^4 nodes, fastest
-    // / median of five runs: margin 2 119 / 120 ms, margin 1 111 / 112 ms, margin 0 108 / 108 ms; 16 problems 46 -> 41 ms.
-    static const int bmargin = getenv("LPBOX_SEG_KMARGIN") ? std::max(0, atoi(getenv("LPBOX_SEG_KMARGIN"))) : 0;
     HIPCHK(hipEventRecord(s0->ev0, st));
     HIPCHK(segb_launch_init(devs.p, B, Gmax, st));
     HIPCHK(segb_launch_set_window(devs.p, B, 0, SEG_MAX_ITERS, 0, &parity, st));
     launches += 2;
-    for (;;) {
-        rc = read_states();
-        if (rc) return rc;
-        bool more = false, any_run = false;
-        int remaining = 0, pcg_max = 0, pcg_k = 0;
-        for (int i = 0; i < B; i++) {
-            const SegState &h = hs[i];
-            if (h.halt == SEG_HALT_PCG_MORE) { more = true; pcg_k = std::max(pcg_k, h.pcg_k); continue; }
-            if (h.halt != SEG_HALT_NONE) continue;
-            const int rem = SEG_MAX_ITERS - h.iter;
-            if (rem <= 0 && !h.have_prev) continue;
-            any_run = true; remaining = std::max(remaining, rem); pcg_max = std::max(pcg_max, h.outer_total > 0 ? h.pcg_max : kmax - bmargin);
-        }
-        if (more) {                                                 // some PCG ran out of launches: resume it (the others fall through)
-            HIPCHK(segb_enqueue_pcg_more(devs.p, B, Gmax, 16, &parity, st));
-            launches += 34;
-            if (s0->adaptive) kmax = std::min(SEG_KMAX_LIMIT, std::max(kmax, pcg_k + 4));
-            continue;
-        }
-        if (!any_run) break;
-        if (s0->adaptive) kmax = std::min(SEG_KMAX_LIMIT, std::max(2, pcg_max + bmargin));
-        HIPCHK(segb_launch_copy(devs.p, B, 1, &parity, st));
-        const int batch = std::min(std::max(remaining, 0), 32);
-        if (batch > 0) HIPCHK(segb_enqueue_iterations(devs.p, B, Gmax, batch, kmax, &parity, st));
-        HIPCHK(segb_enqueue_finalize(devs.p, B, Gmax, &parity, st));
-        launches += 2 + (long long)batch * (4 + 2 * kmax);
-    }
+    if ((rc = batch_run_chain(devs.p, dstates.p, B, Gmax, SEG_MAX_ITERS, &parity, &kmax, s0->adaptive, hs.data(), &launches, st))) return rc;
     HIPCHK(hipEventRecord(s0->ev1, st));
     HIPCHK(hipStreamSynchronize(st));
     float ms = 0.f;
@@ -534,6 +558,7 @@ int segc_l2f(SegSolver *s, int iter_start, int iter_end, const double *vec, int 
     if (ws > SEG_XITERS_COLS) return lpbox_fail(LPBOX_E_BADARG, "window of %d iterations exceeds the %d columns of x_iters (SEGcpp:924)", ws, SEG_XITERS_COLS);
     int rc = use_device(s);
     if (rc) return rc;
+    if ((rc = refresh_left(s))) return rc;
     const int n_live = (int)s->left_idx.size();
     if (num < 0 || num > n_live) return lpbox_fail(LPBOX_E_BADARG, "fix count %d outside [0,%d]", num, n_live);
     if (num != 0) {
@@ -563,9 +588,10 @@ int segc_l2f(SegSolver *s, int iter_start, int iter_end, const double *vec, int 
     if (s->ws_cap > 0 && s->xhist.p) HIPCHK(hipMemsetAsync(s->xhist.p, 0, sizeof(double) * (size_t)s->ws_cap * s->n, s->stream));   // x_iters = Zero (SEGcpp:924): ALL staged columns, also those of an earlier, longer window
     s->rec_cols = 0;
     if (!s->left_idx.empty()) HIPCHK(hipMemcpyAsync(s->d_left.p, s->left_idx.data(), sizeof(int) * s->left_idx.size(), hipMemcpyHostToDevice, s->stream));
+    s->dleft_valid = true;
     rc = run_window(s, iter_end);
     if (rc) return rc;
-    s->last_ws = ws; s->xi_valid = true;
+    s->last_ws = ws; s->xi_valid = true; s->win_serial++;
     if (ret) *ret = s->hst.ret;
     return LPBOX_OK;
 }
@@ -718,5 +744,294 @@ int segc_get_problem(SegSolver *s, int *n, int *nnz, int *rowptr, int *colidx, d
     if (vals) memcpy(vals, s->vals.data(), sizeof(double) * (size_t)s->nnz);
     if (b) memcpy(b, s->orgb.data(), sizeof(double) * (size_t)s->n);
     if (c) *c = s->c;
+    return LPBOX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Early-fixing windows (SEGcpp:917-1195; the loop of SEG/trainer.py:699-745) for a BATCH of handles: every active problem runs
+// iterations [iter_start, iter_end) through one lockstep launch chain (the chain of segc_legacy_batch, cut at iter_end), the
+// fix of all problems is one launch, the live lists are compacted on the device and the windows are packed into one buffer.
+// Per problem the arithmetic is that of segc_l2f on its own; the handles stay ordinary handles.
+struct lpbox_seg_batch {
+    std::vector<SegSolver *> ss;
+    std::vector<uint8_t> active;
+    int B = 0, kmax = 10;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    Buf<SegDev> devs; Buf<SegBatchAux> aux; Buf<SegFixPar> par; Buf<SegState> dstates; Buf<int> counts; Buf<double> pack;
+    uint8_t *h_newfix = nullptr;                 // pinned staging of the host-vector form, problem i at nf_off[i]
+    std::vector<size_t> nf_off;
+    std::vector<SegDev> h_devs; std::vector<SegBatchAux> h_aux;   // host side of devs / aux (alive until the stream has taken them)
+    // the most recent pack: rows of handle i = [row_off[i], row_off[i+1]), taken after window pack_serial[i] of that handle (-1: not packed)
+    std::vector<int> row_off; std::vector<long> pack_serial;
+    bool pack_valid = false;
+};
+
+namespace {
+
+int segb_ensure(lpbox_seg_batch *b) {
+    if (b->stream) return LPBOX_OK;
+    const int B = b->B;
+    HIPCHK(hipStreamCreate(&b->stream));
+    HIPCHK(hipEventCreate(&b->ev0)); HIPCHK(hipEventCreate(&b->ev1));
+    HIPCHK(b->devs.alloc(B)); HIPCHK(b->aux.alloc(B)); HIPCHK(b->par.alloc(B)); HIPCHK(b->dstates.alloc(B)); HIPCHK(b->counts.alloc(2 * (size_t)B));
+    size_t tot = 0;
+    b->nf_off.assign(B, 0);
+    for (int i = 0; i < B; i++) { b->nf_off[i] = tot; tot += (size_t)b->ss[i]->n; }
+    HIPCHK(hipHostMalloc((void **)&b->h_newfix, tot));
+    return LPBOX_OK;
+}
+
+// descriptors of the handles `act` (device arrays devs / aux in that order); rows[k] / row0[k]: live count and first packed row
+int segb_describe(lpbox_seg_batch *b, const std::vector<int> &act, const std::vector<int> &rows, const std::vector<int> &row0) {
+    std::vector<SegDev> &hd = b->h_devs; std::vector<SegBatchAux> &ha = b->h_aux;
+    hd.resize(act.size()); ha.resize(act.size());
+    for (size_t k = 0; k < act.size(); k++) {
+        SegSolver *s = b->ss[act[k]];
+        hd[k] = s->dev();
+        ha[k].left = s->d_left.p; ha[k].row0 = row0[k]; ha[k].rows = rows[k];
+    }
+    HIPCHK(hipMemcpyAsync(b->devs.p, hd.data(), sizeof(SegDev) * hd.size(), hipMemcpyHostToDevice, b->stream));
+    HIPCHK(hipMemcpyAsync(b->aux.p, ha.data(), sizeof(SegBatchAux) * ha.size(), hipMemcpyHostToDevice, b->stream));
+    return LPBOX_OK;
+}
+
+std::vector<int> segb_active(const lpbox_seg_batch *b) {
+    std::vector<int> act;
+    for (int i = 0; i < b->B; i++) if (b->active[i]) act.push_back(i);
+    return act;
+}
+
+// one window.  Host-vector form: vecs / nums (deter_fix_2 done by the caller); score form: scores (device, float32, one per packed row of
+// the last pack) or NULL, the rule runs on the device.  `score_form` selects which.
+int segb_window(lpbox_seg_batch *b, int iter_start, int iter_end, bool score_form, const double *vecs, long vec_stride, const int *nums,
+                const float *scores, double hi, double lo, int min_fix, int *rets, int *fixed) {
+    const int ws = iter_end - iter_start;
+    if (ws > SEG_XITERS_COLS) return lpbox_fail(LPBOX_E_BADARG, "window of %d iterations exceeds the %d columns of x_iters (SEGcpp:924)", ws, SEG_XITERS_COLS);
+    const std::vector<int> act = segb_active(b);
+    const int A = (int)act.size();
+    std::vector<int> live(A), num(A, 0);
+    for (int k = 0; k < A; k++) { SegSolver *s = b->ss[act[k]]; live[k] = s->inited ? s->hst.n_live : s->n; }
+    if (!score_form) {
+        for (int k = 0; k < A; k++) {
+            const int i = act[k];
+            num[k] = nums ? nums[i] : 0;
+            if (num[k] < 0 || num[k] > live[k]) return lpbox_fail(LPBOX_E_BADARG, "problem %d of the batch: fix count %d outside [0,%d]", i, num[k], live[k]);
+            if (num[k] == 0) continue;
+            if (!vecs) return lpbox_fail(LPBOX_E_BADARG, "problem %d of the batch: fix vector missing", i);
+            if (vec_stride < live[k]) return lpbox_fail(LPBOX_E_BADARG, "problem %d of the batch: fix vector holds %ld entries, %d live variables", i, vec_stride, live[k]);
+            const double *vec = vecs + (size_t)i * vec_stride;
+            int cnt = 0;
+            for (int q = 0; q < live[k]; q++) if (vec[q] == 1 || vec[q] == 0) cnt++;
+            if (cnt != num[k]) return lpbox_fail(LPBOX_E_BADARG, "problem %d of the batch: vec fixes %d variables but num = %d", i, cnt, num[k]);
+        }
+    } else if (scores) {
+        if (!b->pack_valid) return lpbox_fail(LPBOX_E_STATE, "scores given, but lpbox_seg_batch_get_x_iters_device has not been called since the last window");
+        for (int k = 0; k < A; k++)
+            if (b->pack_serial[act[k]] != b->ss[act[k]]->win_serial || b->pack_serial[act[k]] < 0 ||
+                b->row_off[act[k] + 1] - b->row_off[act[k]] != live[k])
+                return lpbox_fail(LPBOX_E_STATE, "problem %d of the batch is active but its window is not in the packed buffer the scores refer to", act[k]);
+    }
+    for (int k = 0; k < A; k++)
+        if (!b->ss[act[k]]->inited) return lpbox_fail(LPBOX_E_STATE, "problem %d of the batch: solve_init has not been called", act[k]);
+    int rc = use_device(b->ss[0]);
+    if (rc) return rc;
+    if (A == 0) return LPBOX_OK;
+    if ((rc = segb_ensure(b))) return rc;
+    hipStream_t st = b->stream;
+    int Gmax = 0;
+    for (int k = 0; k < A; k++) {
+        SegSolver *s = b->ss[act[k]];
+        Gmax = std::max(Gmax, s->G);
+        if (ws > 0 && (!s->xhist.p || s->ws_cap < ws)) {
+            HIPCHK(hipStreamSynchronize(s->stream));
+            HIPCHK(s->xhist.alloc((size_t)SEG_XITERS_COLS * s->n)); s->ws_cap = SEG_XITERS_COLS; drop_graphs(s);
+        }
+        if (!s->dleft_valid) {                       // first early-fixing window after an init: the identity list
+            if (!s->left_idx.empty()) HIPCHK(hipMemcpyAsync(s->d_left.p, s->left_idx.data(), sizeof(int) * s->left_idx.size(), hipMemcpyHostToDevice, st));
+            s->dleft_valid = true;
+        }
+    }
+    // one ping-pong parity for the chain: a handle that ran windows of its own in between may sit on the other one
+    int parity = b->ss[act[0]]->parity;
+    long long launches = 0;
+    for (int k = 1; k < A; k++) {
+        SegSolver *s = b->ss[act[k]];
+        if (s->parity != parity) { HIPCHK(seg_launch_copy(s->dev(), 0, &s->parity, st)); launches++; }
+    }
+    std::vector<int> row0(A, 0);
+    if (score_form && scores) for (int k = 0; k < A; k++) row0[k] = b->row_off[act[k]];
+    if ((rc = segb_describe(b, act, live, row0))) return rc;
+    HIPCHK(hipEventRecord(b->ev0, st));
+
+    std::vector<SegFixPar> hp(A);
+    std::vector<int> applied(A, 0);
+    std::vector<std::vector<int>> kept(A);        // host-vector form: the new live lists, taken over once the window has completed
+    bool any = false;
+    if (score_form && scores) {
+        std::vector<int> hc(2 * (size_t)A);
+        HIPCHK(hipMemsetAsync(b->counts.p, 0, sizeof(int) * hc.size(), st));
+        HIPCHK(segb_launch_decide(b->devs.p, b->aux.p, A, *std::max_element(live.begin(), live.end()), scores, hi, lo, b->counts.p, st));
+        HIPCHK(hipMemcpyAsync(hc.data(), b->counts.p, sizeof(int) * hc.size(), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        launches++;
+        for (int k = 0; k < A; k++) { const int kf = hc[2 * k] + hc[2 * k + 1]; if (kf > min_fix) applied[k] = kf; }     // SEG/trainer.py:735-736
+    } else if (!score_form) {
+        for (int k = 0; k < A; k++) {
+            if (num[k] == 0) continue;
+            SegSolver *s = b->ss[act[k]];
+            if ((rc = refresh_left(s))) return rc;
+            const double *vec = vecs + (size_t)act[k] * vec_stride;
+            uint8_t *nf = b->h_newfix + b->nf_off[act[k]];
+            memset(nf, 0, (size_t)s->n);
+            std::vector<int> &keep = kept[k]; keep.reserve(live[k] - num[k]);
+            for (int q = 0; q < live[k]; q++) {
+                const int org = s->left_idx[q];
+                if (vec[q] == 1) nf[org] = 2; else if (vec[q] == 0) nf[org] = 1; else keep.push_back(org);
+            }
+            HIPCHK(hipMemcpyAsync(s->newfix.p, nf, (size_t)s->n, hipMemcpyHostToDevice, st));
+            applied[k] = num[k];
+        }
+    }
+    for (int k = 0; k < A; k++) {
+        const int nl = live[k] - applied[k];
+        hp[k].apply = applied[k] > 0 ? 1 : 0; hp[k].n_live_new = nl;
+        hp[k].c1_new = std::pow((double)nl, 1.0 / 2);             // on the host, as segc_l2f: pow and a device sqrt differ by an ulp now and then
+        any |= applied[k] > 0;
+    }
+    HIPCHK(hipMemcpyAsync(b->par.p, hp.data(), sizeof(SegFixPar) * (size_t)A, hipMemcpyHostToDevice, st));
+    HIPCHK(segb_launch_set_window(b->devs.p, A, iter_start, iter_end, 3, &parity, st));
+    HIPCHK(segb_launch_fix(b->devs.p, b->par.p, A, Gmax, &parity, st));          // also x_iters = Zero, all staged columns
+    launches += 2;
+    if (any) { HIPCHK(segb_launch_compact(b->devs.p, b->aux.p, b->par.p, A, st)); launches++; }
+
+    std::vector<SegState> hs(A);
+    int kmax = b->kmax;
+    if ((rc = batch_run_chain(b->devs.p, b->dstates.p, A, Gmax, iter_end, &parity, &kmax, b->ss[0]->adaptive, hs.data(), &launches, st))) return rc;
+    b->kmax = kmax;
+    HIPCHK(hipEventRecord(b->ev1, st));
+    HIPCHK(hipStreamSynchronize(st));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, b->ev0, b->ev1));
+    for (int k = 0; k < A; k++) {
+        SegSolver *s = b->ss[act[k]];
+        s->hst = hs[k]; s->parity = parity; s->rec_cols = 0;
+        s->xi_rows = live[k] - applied[k]; s->last_ws = ws; s->xi_valid = true; s->win_serial++;
+        if (score_form && applied[k]) s->left_stale = true;          // fixed on the device: the host list follows on demand
+        else if (applied[k]) s->left_idx.swap(kept[k]);
+        s->xi_left_idx.clear();
+        if (rets) rets[act[k]] = s->hst.ret;
+        if (fixed) fixed[act[k]] = applied[k];
+    }
+    b->ss[act[0]]->kernel_ms += ms; b->ss[act[0]]->launches += launches;
+    b->pack_valid = false;
+    return LPBOX_OK;
+}
+
+}  // namespace
+
+lpbox_seg_batch *segbc_create(SegSolver **ss, int B) {
+    auto refuse = [](int) -> lpbox_seg_batch * { return nullptr; };        // lpbox_fail has recorded status and text
+    if (!ss || B <= 0) return refuse(lpbox_fail(LPBOX_E_BADARG, "empty batch"));
+    for (int i = 0; i < B; i++) {                                   // the checks of segc_legacy_batch; no device call
+        if (!ss[i] || !ss[i]->has_problem) return refuse(lpbox_fail(LPBOX_E_STATE, "problem %d of the batch has no image / problem", i));
+        if (ss[i]->device != ss[0]->device) return refuse(lpbox_fail(LPBOX_E_BADARG, "problem %d of the batch lives on another device than problem 0", i));
+        if (ss[i]->record > 0) return refuse(lpbox_fail(LPBOX_E_UNSUPPORTED, "problem %d of the batch is recording; recording is per-solver (lpbox_seg_legacy)", i));
+        for (int k = 0; k < i; k++)
+            if (ss[k] == ss[i]) return refuse(lpbox_fail(LPBOX_E_BADARG, "problem %d and problem %d of the batch are the same handle", k, i));
+    }
+    lpbox_seg_batch *b = new lpbox_seg_batch();
+    b->ss.assign(ss, ss + B); b->B = B; b->active.assign(B, 1); b->kmax = ss[0]->kmax;
+    b->row_off.assign((size_t)B + 1, 0); b->pack_serial.assign(B, -1);
+    return b;
+}
+
+void segbc_destroy(lpbox_seg_batch *b) {
+    if (!b) return;
+    if (b->stream) {
+        (void)hipSetDevice(b->ss[0]->device);
+        (void)hipStreamSynchronize(b->stream);
+        b->devs.release(); b->aux.release(); b->par.release(); b->dstates.release(); b->counts.release(); b->pack.release();
+        if (b->h_newfix) (void)hipHostFree(b->h_newfix);
+        (void)hipEventDestroy(b->ev0); (void)hipEventDestroy(b->ev1);
+        (void)hipStreamDestroy(b->stream);
+    }
+    delete b;
+}
+
+int segbc_set_active(lpbox_seg_batch *b, const unsigned char *active) {
+    for (int i = 0; i < b->B; i++) b->active[i] = active ? (active[i] ? 1 : 0) : 1;
+    return LPBOX_OK;
+}
+
+// lpbox_init on every handle: upload, host-side reset, ONE batched init launch (the head of segc_legacy_batch)
+int segbc_init(lpbox_seg_batch *b) {
+    const int B = b->B;
+    for (int i = 0; i < B; i++) { b->ss[i]->inited = false; b->ss[i]->xi_valid = false; }
+    b->pack_valid = false;
+    int rc = LPBOX_OK, Gmax = 0;
+    for (int i = 0; i < B; i++) {
+        if ((rc = batch_reset_handle(b->ss[i]))) return rc;
+        Gmax = std::max(Gmax, b->ss[i]->G);
+    }
+    for (int i = 0; i < B; i++) HIPCHK(hipStreamSynchronize(b->ss[i]->stream));
+    if ((rc = segb_ensure(b))) return rc;
+    std::vector<int> all(B), zero(B, 0);
+    for (int i = 0; i < B; i++) all[i] = i;
+    if ((rc = segb_describe(b, all, zero, zero))) return rc;
+    HIPCHK(segb_launch_init(b->devs.p, B, Gmax, b->stream));
+    std::vector<SegState> hs(B);
+    HIPCHK(segb_collect_states(b->devs.p, B, 0, b->dstates.p, b->stream));
+    HIPCHK(hipMemcpyAsync(hs.data(), b->dstates.p, sizeof(SegState) * (size_t)B, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    for (int i = 0; i < B; i++) { SegSolver *s = b->ss[i]; s->hst = hs[i]; s->parity = 0; s->rec_cols = 0; s->inited = true; }
+    b->ss[0]->launches += 1;
+    return 1;
+}
+
+int segbc_l2f(lpbox_seg_batch *b, int iter_start, int iter_end, const double *vecs, long vec_stride, const int *nums, int *rets) {
+    return segb_window(b, iter_start, iter_end, false, vecs, vec_stride, nums, nullptr, 0.0, 0.0, 0, rets, nullptr);
+}
+
+int segbc_l2f_scores(lpbox_seg_batch *b, int iter_start, int iter_end, const float *scores_dev, double hi, double lo, int min_fix,
+                     int *rets, int *fixed) {
+    return segb_window(b, iter_start, iter_end, true, nullptr, 0, nullptr, scores_dev, hi, lo, min_fix, rets, fixed);
+}
+
+// the (n_live x ws) windows of all active handles, one after the other, in ONE buffer of the batch (one launch)
+int segbc_get_x_iters_device(lpbox_seg_batch *b, int ws, void **dev_ptr, long *row_off) {
+    if (ws <= 0 || ws > SEG_XITERS_COLS) return lpbox_fail(LPBOX_E_BADARG, "ws = %d outside (0,%d]", ws, SEG_XITERS_COLS);
+    const std::vector<int> act = segb_active(b);
+    const int A = (int)act.size();
+    for (int k = 0; k < A; k++)
+        if (!b->ss[act[k]]->xi_valid) return lpbox_fail(LPBOX_E_STATE, "problem %d of the batch: solve_iter_l2f has not been called", act[k]);
+    int rc = use_device(b->ss[0]);
+    if (rc) return rc;
+    if ((rc = segb_ensure(b))) return rc;
+    std::vector<int> rows(A), row0(A);
+    std::fill(b->pack_serial.begin(), b->pack_serial.end(), -1L);
+    int tot = 0, k = 0, max_rows = 0;
+    for (int i = 0; i < b->B; i++) {
+        b->row_off[i] = tot;
+        if (k < A && act[k] == i) {
+            rows[k] = b->ss[i]->xi_rows; row0[k] = tot; tot += rows[k]; max_rows = std::max(max_rows, rows[k]);
+            b->pack_serial[i] = b->ss[i]->win_serial; k++;
+        }
+    }
+    b->row_off[b->B] = tot;
+    if (!b->pack.p) {
+        size_t cap = 0;
+        for (int i = 0; i < b->B; i++) cap += (size_t)b->ss[i]->n;
+        HIPCHK(b->pack.alloc(cap * SEG_XITERS_COLS));
+    }
+    if (A > 0 && tot > 0) {
+        if ((rc = segb_describe(b, act, rows, row0))) return rc;
+        HIPCHK(segb_launch_pack_xiters(b->devs.p, b->aux.p, A, max_rows, ws, b->pack.p, b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));
+        b->ss[act[0]]->launches += 1;
+    }
+    b->pack_valid = true;
+    if (dev_ptr) *dev_ptr = b->pack.p;
+    if (row_off) for (int i = 0; i <= b->B; i++) row_off[i] = b->row_off[i];
     return LPBOX_OK;
 }

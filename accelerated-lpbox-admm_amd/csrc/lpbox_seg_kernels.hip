@@ -19,6 +19,7 @@
 #include "lpbox_dev_common.h"
 
 #include <float.h>
+#include <algorithm>
 
 namespace {
 
@@ -181,8 +182,17 @@ __device__ __forceinline__ void seg_b_resume(const SegDev &d, int in, int out, i
     if (reset_pcg_max) d.st[out].pcg_max = 0;
 }
 
-// early fixing as a mask (SEGcpp:927-1062): fixed variables leave the problem, b := 2*Mb*x2 + b1, temp_mat rebuilt
-__global__ void __launch_bounds__(T) seg_k_fix(SegDev d, int in, int out, int n_live_new, double c1_new) {
+// early fixing as a mask (SEGcpp:927-1062): fixed variables leave the problem, b := 2*Mb*x2 + b1, temp_mat rebuilt.
+// apply == 0 (a problem of a batch that fixes nothing in this window): only the newfix bytes are cleared and the state moves on.
+__device__ __forceinline__ void seg_b_fix(const SegDev &d, int in, int out, int apply, int n_live_new, double c1_new) {
+    if (!apply) {
+        for (int q = 0; q < d.EPT; q++) {
+            const int i = blockIdx.x * (T * d.EPT) + q * T + threadIdx.x;
+            if (i < d.n) d.newfix[i] = 0;
+        }
+        forward_state(d, in, out);
+        return;
+    }
     const double rho12 = d.st[in].rho1 + d.st[in].rho2;
     for (int q = 0; q < d.EPT; q++) {
         const int i = blockIdx.x * (T * d.EPT) + q * T + threadIdx.x;
@@ -221,6 +231,90 @@ __global__ void __launch_bounds__(T) seg_k_fix(SegDev d, int in, int out, int n_
         SegState *s = d.st + out;
         if (n_live_new == 0) { s->ret = 1; s->stop = SEG_STOP_ALLFIXED; s->halt = SEG_HALT_ALLFIXED; s->n_live = 0; }   // :1028-1032
         else { s->n_live = n_live_new; s->c1 = c1_new; s->dinv_stale = 1; }
+    }
+}
+__global__ void __launch_bounds__(T) seg_k_fix(SegDev d, int in, int out, int n_live_new, double c1_new) { seg_b_fix(d, in, out, 1, n_live_new, c1_new); }
+// the batched fix launch also opens the window: x_iters = Zero (SEGcpp:924), every staged column of the workgroup's own variables
+__global__ void __launch_bounds__(T) seg_kb_fix(const SegDev *devs, const SegFixPar *par, int in, int out) {
+    const SegDev &d = devs[blockIdx.y];
+    if ((int)blockIdx.x >= d.G) return;
+    if (d.xhist)
+        for (int c = 0; c < d.ws_cap; c++)
+            for (int q = 0; q < d.EPT; q++) {
+                const int i = blockIdx.x * (T * d.EPT) + q * T + threadIdx.x;
+                if (i < d.n) d.xhist[(size_t)c * d.n + i] = 0.0;
+            }
+    const SegFixPar p = par[blockIdx.y];
+    seg_b_fix(d, in, out, p.apply, p.n_live_new, p.c1_new);
+}
+
+// deter_fix_2 on the device: packed row q of problem y (score scores[row0 + q], original index left[q]) -> newfix code, and the
+// problem's counts of fixes to one / to zero (integer atomics: the sums do not depend on the order)
+__global__ void __launch_bounds__(T) seg_kb_decide(const SegDev *devs, const SegBatchAux *aux, const float *scores, double hi, double lo, int *counts) {
+    const SegDev &d = devs[blockIdx.y];
+    const SegBatchAux a = aux[blockIdx.y];
+    __shared__ int cnt[2];
+    if (threadIdx.x < 2) cnt[threadIdx.x] = 0;
+    __syncthreads();
+    for (int q = blockIdx.x * T + threadIdx.x; q < a.rows; q += gridDim.x * T) {
+        const double s = (double)scores[(size_t)a.row0 + q];
+        const int code = s > hi ? 2 : (s < lo ? 1 : 0);                      // NaN: neither
+        d.newfix[a.left[q]] = (uint8_t)code;
+        if (code) atomicAdd(&cnt[code == 2 ? 0 : 1], 1);
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 && cnt[threadIdx.x]) atomicAdd(&counts[2 * blockIdx.y + threadIdx.x], cnt[threadIdx.x]);
+}
+
+// ordered stream compaction of a problem's live list after a fix: the entries whose newfix code is 0 stay, in the same (ascending)
+// order; the codes are cleared on the way (every non-zero code sits at an entry of the old list).  One workgroup per problem walks
+// the list in chunks of CT * CE entries with a block prefix sum and a carried offset; in place: a chunk's writes land at or before
+// its own entries, which were all read before the first write.
+constexpr int CT = 1024, CE = 4;
+__global__ void __launch_bounds__(CT) seg_kb_compact(const SegDev *devs, const SegBatchAux *aux, const SegFixPar *par) {
+    const SegDev &d = devs[blockIdx.x];
+    const SegBatchAux a = aux[blockIdx.x];
+    if (!par[blockIdx.x].apply) return;
+    __shared__ int wsum[CT / 64 + 1];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int carried = 0;
+    for (int base = 0; base < a.rows; base += CT * CE) {
+        int org[CE], keep[CE], c = 0;
+#pragma unroll
+        for (int k = 0; k < CE; k++) {
+            const int q = base + threadIdx.x * CE + k;
+            org[k] = q < a.rows ? a.left[q] : -1;
+            keep[k] = 0;
+            if (org[k] >= 0) {
+                if (d.newfix[org[k]]) d.newfix[org[k]] = 0; else keep[k] = 1;
+            }
+            c += keep[k];
+        }
+        int v = c;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) { const int t = __shfl_up(v, off, 64); if (lane >= off) v += t; }
+        if (lane == 63) wsum[w + 1] = v;
+        __syncthreads();
+        if (threadIdx.x == 0) { wsum[0] = 0; for (int k = 1; k <= CT / 64; k++) wsum[k] += wsum[k - 1]; }
+        __syncthreads();
+        int pos = carried + wsum[w] + v - c;
+        const int total = wsum[CT / 64];
+#pragma unroll
+        for (int k = 0; k < CE; k++) if (keep[k]) a.left[pos++] = org[k];
+        carried += total;
+        __syncthreads();
+    }
+}
+
+// seg_k_pack over the descriptor array: problem y's (rows x ws) window goes to out + row0 * ws
+__global__ void seg_kb_pack(const SegDev *devs, const SegBatchAux *aux, int ws, double *out) {
+    const SegDev &d = devs[blockIdx.y];
+    const SegBatchAux a = aux[blockIdx.y];
+    const long total = (long)a.rows * ws;
+    double *o = out + (size_t)a.row0 * ws;
+    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+        const int r = (int)(e / ws), c = (int)(e % ws);
+        o[e] = c < d.ws_cap ? d.xhist[(size_t)c * d.n + a.left[r]] : 0.0;
     }
 }
 
@@ -894,5 +988,25 @@ hipError_t segb_enqueue_finalize(const SegDev *devs, int B, int Gmax, int *parit
 }
 hipError_t segb_collect_states(const SegDev *devs, int B, int parity, SegState *out, hipStream_t s) {
     hipLaunchKernelGGL(seg_kb_collect, dim3(B), dim3(1), 0, s, devs, parity, out);
+    return hipGetLastError();
+}
+hipError_t segb_launch_fix(const SegDev *devs, const SegFixPar *par, int B, int Gmax, int *parity, hipStream_t s) {
+    hipLaunchKernelGGL(seg_kb_fix, dim3(Gmax, B), dim3(T), 0, s, devs, par, *parity, *parity ^ 1);
+    *parity ^= 1;
+    return hipGetLastError();
+}
+hipError_t segb_launch_decide(const SegDev *devs, const SegBatchAux *aux, int B, int max_rows, const float *scores, double hi, double lo,
+                              int *counts, hipStream_t s) {
+    const int gx = std::min(std::max((max_rows + T - 1) / T, 1), 64);
+    hipLaunchKernelGGL(seg_kb_decide, dim3(gx, B), dim3(T), 0, s, devs, aux, scores, hi, lo, counts);
+    return hipGetLastError();
+}
+hipError_t segb_launch_compact(const SegDev *devs, const SegBatchAux *aux, const SegFixPar *par, int B, hipStream_t s) {
+    hipLaunchKernelGGL(seg_kb_compact, dim3(B), dim3(CT), 0, s, devs, aux, par);
+    return hipGetLastError();
+}
+hipError_t segb_launch_pack_xiters(const SegDev *devs, const SegBatchAux *aux, int B, int max_rows, int ws, double *out, hipStream_t s) {
+    const int gx = (int)std::min<long>(std::max<long>(((long)max_rows * ws + 255) / 256, 1), 64);
+    hipLaunchKernelGGL(seg_kb_pack, dim3(gx, B), dim3(256), 0, s, devs, aux, ws, out);
     return hipGetLastError();
 }

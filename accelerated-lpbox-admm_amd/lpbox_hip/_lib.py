@@ -23,6 +23,7 @@ _ip = np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS")
 SYMBOLS = {
     "lpbox_version": (C.c_char_p, []),
     "lpbox_last_error": (C.c_char_p, []),
+    "lpbox_last_status": (C.c_int, []),
     "lpbox_device_count": (C.c_int, []),
     "lpbox_set_device": (C.c_int, [C.c_int]),
     "lpbox_create": (C.c_void_p, [C.c_int, C.c_int, C.c_int]),
@@ -66,6 +67,14 @@ SYMBOLS = {
     "lpbox_read_jpeg_gray": (C.c_int, [C.c_char_p, C.c_void_p, C.c_long, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "lpbox_seg_legacy": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "lpbox_seg_legacy_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "lpbox_seg_batch_create": (C.c_void_p, [C.c_void_p, C.c_int]),
+    "lpbox_seg_batch_destroy": (None, [C.c_void_p]),
+    "lpbox_seg_batch_init": (C.c_int, [C.c_void_p]),
+    "lpbox_seg_batch_set_active": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "lpbox_seg_batch_iterate_l2f": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p]),
+    "lpbox_seg_batch_get_x_iters_device": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]),
+    "lpbox_seg_batch_iterate_l2f_scores": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_void_p,
+                                                     C.c_void_p]),
     "lpbox_seg_get_obj": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "lpbox_seg_get_shape": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "lpbox_seg_get_problem": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p,

@@ -145,6 +145,44 @@ def run_l2f_seg_device(solver, policy, ws=10, max_iter=30, min_fix=10, C=0.9):
     return dict(energy=solver.get_obj(), windows=windows, fixed=fixed)
 
 
+def run_l2f_seg_batch(solvers, policy, ws=10, max_iter=30, min_fix=10, C=0.9):
+    """The loop of run_l2f_seg_device for all images at once (lpbox_hip.seg.SegBatch; `solvers` hold their images, solve_init is done
+    here): per window ONE lockstep launch chain over the unfinished images, one pack, ONE policy call over the packed rows of all of
+    them, and the fix decided on the device from the scores, which never leave it.  policy: a FusedEarlyFixPolicy(tokens=5) (called
+    through scores_from_xiters, token stride 1) or a plain torch callable on the float32 (rows, 5, 5) sliding windows
+    (SEG/trainer.py:721-725).  An image whose window returned non-zero is deactivated.  Returns [dict(energy, windows, fixed)]."""
+    import torch
+
+    from .seg import SegBatch
+    solvers = list(solvers)
+    batch = SegBatch(solvers)
+    try:
+        B = batch.B
+        batch.solve_init()
+        done = np.zeros(B, bool)
+        windows, fixed = np.zeros(B, int), np.zeros(B, int)
+        sig = None
+        for i in range(int(max_iter / ws)):
+            batch.set_active(~done)
+            rets, fx = batch.solve_iter_l2f_scores(ws * i, ws * (i + 1), sig, C, min_fix)
+            windows[~done] += 1
+            fixed[~done] += fx[~done]
+            done |= rets != 0
+            if done.all():
+                break
+            batch.set_active(~done)
+            X, _ = batch.x_iters_torch(ws)
+            if hasattr(policy, "scores_from_xiters"):
+                off = torch.arange(X.shape[0], device=X.device, dtype=torch.int64) * ws
+                sig = policy.scores_from_xiters(X.reshape(-1), off, 1)
+            else:
+                sig = policy(X.unfold(1, 5, 1)[:, :5].to(torch.float32))    # token j = iterates j .. j+4, j < 5
+            sig = sig.reshape(-1).to(torch.float32)
+    finally:
+        batch.close()
+    return [dict(energy=s.get_obj(), windows=int(windows[k]), fixed=int(fixed[k])) for k, s in enumerate(solvers)]
+
+
 def run_l2f_big(big, score_fn_torch, ws=100, max_iter=10000, tokens=20, min_fix=10, C=0.9):
     """The loop on ONE large variable-sharded instance (BASELINE config 5; lpbox_hip.big.BigLp, one process per GPU): every rank
     scores ITS OWN live variables from its device-resident x_iters (no gather); the only extra collective is the sum of the

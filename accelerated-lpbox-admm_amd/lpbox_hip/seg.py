@@ -258,3 +258,106 @@ def solve_batch(solvers):
     en = (C.c_int * len(solvers))()
     check(L.lpbox_seg_legacy_batch(hs, len(solvers), en), "lpbox_seg_legacy_batch")
     return [int(v) for v in en]
+
+
+class SegBatch:
+    """The early-fixing windows of solve_iter_l2f for a list of segmentation solvers at once (C-ABI lpbox_seg_batch_*): all active
+    problems advance through ONE lockstep launch chain per window, their iterate windows are packed into one device buffer, and the
+    fix can be decided on the device from a score tensor.  The solvers are borrowed: they stay ordinary solvers (every getter answers
+    after a batched window, and each may go on with solve_iter_l2f of its own) and must outlive the batch.  Per problem every result
+    is bit-identical to the single-solver calls."""
+
+    def __init__(self, solvers):
+        self.solvers = list(solvers)
+        if not self.solvers:
+            raise ValueError("SegBatch needs at least one solver")
+        for s in self.solvers:
+            if not s._have_problem:
+                root = s.data_root or os.environ.get("LPBOX_SEG_DATA_ROOT") or "../data"
+                s.set_image(load_gray(os.path.join(root, f"{s.problem}.jpg")))
+        self._L = self.solvers[0]._L
+        self.B = len(self.solvers)
+        hs = (C.c_void_p * self.B)(*[s._h for s in self.solvers])
+        h = self._L.lpbox_seg_batch_create(hs, self.B)
+        if not h:
+            check(self._L.lpbox_last_status() or -2, "lpbox_seg_batch_create")
+        self._h = C.c_void_p(h)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.lpbox_seg_batch_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def solve_init(self):
+        return check(self._L.lpbox_seg_batch_init(self._h), "lpbox_seg_batch_init")
+
+    def set_active(self, mask):
+        if mask is None:
+            return check(self._L.lpbox_seg_batch_set_active(self._h, None), "lpbox_seg_batch_set_active")
+        m = np.ascontiguousarray(np.asarray(mask).astype(bool).astype(np.uint8))
+        if m.shape != (self.B,):
+            raise ValueError("mask must have one entry per solver")
+        return check(self._L.lpbox_seg_batch_set_active(self._h, m.ctypes.data_as(C.c_void_p)), "lpbox_seg_batch_set_active")
+
+    def solve_iter_l2f(self, i, j, vecs, nums):
+        """vecs: (B, stride) fix vectors (row k: the vector of solver k, as solve_iter_l2f takes it) or None; nums: B fix counts.
+        Returns the int32 array of return codes (entries of inactive solvers stay 0)."""
+        nums = np.ascontiguousarray(nums, np.int32).ravel()
+        if nums.shape[0] != self.B:
+            raise ValueError("nums must have one entry per solver")
+        if vecs is None:
+            ptr, stride = None, 0
+        else:
+            vecs = np.ascontiguousarray(vecs, np.float64)
+            if vecs.ndim != 2 or vecs.shape[0] != self.B:
+                raise ValueError("vecs must be (solvers, stride)")
+            ptr, stride = vecs.ctypes.data_as(C.c_void_p), vecs.shape[1]
+        rets = np.zeros(self.B, np.int32)
+        check(self._L.lpbox_seg_batch_iterate_l2f(self._h, _as_int(i, "i"), _as_int(j, "j"), ptr, stride, nums.ctypes.data_as(C.c_void_p),
+                                                  rets.ctypes.data_as(C.c_void_p)), "lpbox_seg_batch_iterate_l2f")
+        return rets
+
+    def x_iters_torch(self, ws):
+        """(tensor (rows, ws) float64, zero-copy on the device; row_off int64 (B + 1)): rows row_off[k] .. row_off[k+1] are solver k's
+        live variables in ascending original index (none for an inactive solver).  Valid until the next call on the batch."""
+        import torch
+        ws = _as_int(ws, "ws")
+        ptr = C.c_void_p()
+        off = np.zeros(self.B + 1, np.int64)
+        check(self._L.lpbox_seg_batch_get_x_iters_device(self._h, ws, C.byref(ptr), off.ctypes.data_as(C.c_void_p)),
+              "lpbox_seg_batch_get_x_iters_device")
+        rows = int(off[-1])
+        self._packed_rows = rows
+        if rows == 0:
+            return torch.zeros((0, ws), dtype=torch.float64, device="cuda"), off
+
+        class _Dev:
+            __cuda_array_interface__ = {"shape": (rows * ws,), "typestr": "<f8", "data": (ptr.value, False), "version": 2}
+        return torch.as_tensor(_Dev(), device="cuda").view(rows, ws), off
+
+    def solve_iter_l2f_scores(self, i, j, scores, C=0.9, min_fix=10):
+        """The window with deter_fix_2 (threshold C) and the `<= min_fix -> none` guard applied on the device: scores = float32 CUDA
+        tensor, one score per row of the last x_iters_torch(), or None (fix nothing).  Returns (rets, fixed), int32 arrays."""
+        return self._window_scores(_as_int(i, "i"), _as_int(j, "j"), scores, float(C), 1 - float(C), int(min_fix))
+
+    def _window_scores(self, i, j, scores, hi, lo, min_fix):
+        ptr = None
+        if scores is not None:
+            import torch
+            if not (scores.is_cuda and scores.dtype == torch.float32):
+                raise TypeError("scores must be a float32 CUDA tensor")
+            scores = scores.contiguous().reshape(-1)
+            if scores.numel() != getattr(self, "_packed_rows", -1):
+                raise ValueError("scores must hold one entry per row of the last x_iters_torch()")
+            torch.cuda.current_stream(scores.device).synchronize()      # the batch runs on a stream of its own
+            ptr = C.c_void_p(scores.data_ptr())
+        rets, fixed = np.zeros(self.B, np.int32), np.zeros(self.B, np.int32)
+        check(self._L.lpbox_seg_batch_iterate_l2f_scores(self._h, i, j, ptr, hi, lo, min_fix, rets.ctypes.data_as(C.c_void_p),
+                                                         fixed.ctypes.data_as(C.c_void_p)), "lpbox_seg_batch_iterate_l2f_scores")
+        return rets, fixed

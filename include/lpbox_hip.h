@@ -43,6 +43,7 @@ typedef struct lpbox_solver lpbox_t;      /* one or a batch of independent insta
 /* ---- library / device ---------------------------------------------------------------------- */
 const char *lpbox_version(void);
 const char *lpbox_last_error(void);               /* thread-local text of the last failure */
+int lpbox_last_status(void);                       /* the LPBOX_E_* code that came with that text (for calls that return a pointer) */
 int  lpbox_device_count(void);                    /* number of HIP devices visible (0 if none) */
 int  lpbox_set_device(int device);                /* device used by handles created afterwards on this thread */
 
@@ -199,6 +200,36 @@ int lpbox_seg_legacy(lpbox_t *h, int *energy);
  * Per problem the arithmetic is that of lpbox_init + lpbox_seg_legacy on its own (own control state, sums, iteration counts); afterwards
  * every handle answers its getters as usual.  energies[count]. */
 int lpbox_seg_legacy_batch(lpbox_t **handles, int count, int *energies);
+/* The early-fixing windows of lpbox_iterate_l2f (SEGcpp:917-1195; the loop of SEG/trainer.py:699-745) for a batch of segmentation
+ * handles: a batch object that borrows `count` handles (they stay ordinary handles and must outlive it) and owns the descriptor,
+ * state and packing buffers.  Per problem the arithmetic is that of the single-handle calls, bit for bit; after any batched window
+ * every handle answers every getter and may go on with windows of its own.
+ * _create: NULL on refusal, lpbox_last_status() = the code, lpbox_last_error() names the problem's index: LPBOX_E_BADARG empty list, handles on
+ *   different devices, one handle twice; LPBOX_E_BADHANDLE not a handle; LPBOX_E_STATE an LP-flavour handle, a handle without image /
+ *   problem; LPBOX_E_UNSUPPORTED a recording handle.  No device call.
+ * _init: lpbox_init on every handle (upload, reset, one batched init launch); returns 1.
+ * _set_active: active[count], NULL = all.  An inactive handle is not touched by the calls below (state, staged window, counters, rets[i]).
+ * _iterate_l2f: problem i fixes by vecs + i * vec_stride / nums[i] (validated as lpbox_iterate_l2f does; vecs may be NULL when every
+ *   nums[i] is 0), then all active problems run iterations [iter_start, iter_end) through ONE lockstep launch chain.  rets[count].
+ *   Arguments are checked first (LPBOX_E_BADARG), then the call order (LPBOX_E_STATE before an init), then the device.
+ * _get_x_iters_device: one launch packs the (n_live x ws) row-major windows of all active handles into one buffer of the batch: handle
+ *   i's rows are [row_off[i], row_off[i+1]) (row_off[count + 1]; no rows for an inactive handle), row q = its q-th live variable in
+ *   ascending original index, the row order of lpbox_get_x_iters.  The buffer stays valid until the next call on the batch.
+ * _iterate_l2f_scores: the same window with the fix decided on the device.  scores_dev[r] = float32 score of packed row r of the most
+ *   recent _get_x_iters_device (LPBOX_E_STATE: none since the last window, or a handle active now that was not packed then); NULL =
+ *   fix nothing.  Per problem deter_fix_2 with the trainer's guard: the score widened to double, s > hi -> 1, s < lo -> 0, NaN -> nothing,
+ *   k = number of fixes, k <= min_fix -> nothing fixed.  fixed[count] = fixes applied.  The caller orders its own work on scores_dev
+ *   before the call (the batch runs on a stream of its own). */
+typedef struct lpbox_seg_batch lpbox_seg_batch_t;
+lpbox_seg_batch_t *lpbox_seg_batch_create(lpbox_t **handles, int count);
+void lpbox_seg_batch_destroy(lpbox_seg_batch_t *b);
+int lpbox_seg_batch_init(lpbox_seg_batch_t *b);
+int lpbox_seg_batch_set_active(lpbox_seg_batch_t *b, const unsigned char *active);
+int lpbox_seg_batch_iterate_l2f(lpbox_seg_batch_t *b, int iter_start, int iter_end,
+                                const double *vecs, long vec_stride, const int *nums, int *rets);
+int lpbox_seg_batch_get_x_iters_device(lpbox_seg_batch_t *b, int ws, void **dev_ptr, long *row_off);
+int lpbox_seg_batch_iterate_l2f_scores(lpbox_seg_batch_t *b, int iter_start, int iter_end, const float *scores_dev,
+                                       double hi, double lo, int min_fix, int *rets, int *fixed);
 /* SEG pxd:15 `double get_final_obj()` (SEGcpp:868-893): energy of the assembled rounded solution on the ORIGINAL A, b, plus c. */
 int lpbox_seg_get_obj(lpbox_t *h, double *out);
 int lpbox_seg_get_shape(lpbox_t *h, int *rows, int *cols);   /* scaled_row, scaled_col (SEGcpp:716-717), for save_img */

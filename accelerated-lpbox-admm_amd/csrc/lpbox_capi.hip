@@ -66,6 +66,7 @@ struct LpInstance {
     int nG = 0;
     struct Help { int var, first, count; };
     std::vector<Help> help_of_pos;     // storage position -> helper chunk (var < 0: none)
+    std::vector<int> wave_class;       // 512 x 1 kernel: (rn, cn, hn, tail) of every wavefront (lpbox_get_wave_classes), else empty
     std::vector<double> b, f_org;
     // early-fix bookkeeping (LPcpp:1192-1206): original index of each live variable, in compact order
     std::vector<int> left_idx;
@@ -101,6 +102,7 @@ struct lpbox_solver {
     bool colsplit = false;
     bool identity_rows = true;   // row storage index == row id (bank-aware placement off)
     bool direct = false;          // opt-in direct x-update (lpbox_set_x_update)
+    bool pcg_generic = false;     // LPBOX_LP_PCGLOOP=generic: the 512 x 1 kernel runs its generic PCG loop in every wave
     int order = LPBOX_ORDER_DEFAULT;   // opt-in reference summation order (lpbox_set_order): own kernels, identity layout
     bool valued = false, vals_in_lds = false;   // reference order only: some instance stores a value other than 1.0
     DevBuf<double> vr, vc, r4v;        // ... then the values in CSR / CSC entry order and the entries of rho4_E_transpose, ZS per instance
@@ -134,6 +136,7 @@ struct lpbox_solver {
         d.x = x.p; d.z1 = z1.p; d.z2 = z2.p; d.b = b.p; d.pd = pd.p; d.live = live.p; d.newfix = newfix.p;
         d.z4 = z4.p; d.f = f.p; d.dsc = dsc.p; d.isc = isc.p; d.hist = hist.p;
         d.ctl = ctl.p; d.dctl = dctl.p; d.xhist = xhist.p; d.ws_cap = ws_cap; d.logbuf = nullptr; d.log_cap = 0; d.stamps = stamps.p; d.stamp_wave = getenv("LPBOX_STAMP_WAVE") ? atoi(getenv("LPBOX_STAMP_WAVE")) : 0;
+        d.pcg_generic = pcg_generic ? 1 : 0;
         d.H = direct ? Hinv.p : nullptr; d.HL = direct ? HL : 0; d.HLD = direct ? HLD : 0; d.rdir = rdir.p; d.dng = dng.p;
         return d;
     }
@@ -264,6 +267,8 @@ int finalize(lpbox_t *h) {
     // iteration, measured over all eight rank shards of the j=500/k=2000 stream: on.  LPBOX_LP_BANKAWARE=1 / =0 overrides either way
     // (tools/lottery.sh measures both).
     const char *ba = getenv("LPBOX_LP_BANKAWARE");
+    // LPBOX_LP_PCGLOOP=generic: no wave takes a PCG loop specialised for its list lengths (A/B and tests; same results either way)
+    { const char *pl = getenv("LPBOX_LP_PCGLOOP"); h->pcg_generic = pl != nullptr && strcmp(pl, "generic") == 0; }
     const bool noconflict = getenv("LPBOX_LP_NOCONFLICT") != nullptr || !(ba ? atoi(ba) != 0 : h->EPT >= 4);
     for (size_t i = 0; i < B; i++) {
         LpInstance &I = h->inst[i];
@@ -575,6 +580,19 @@ int finalize(lpbox_t *h) {
             h_rmeta[i * NS + tp] = (uint16_t)((t.G << 4) | t.g);
         }
         h_rs_ptr[i * (NS + 1) + NS] = k;
+        // class of every wavefront in the 512 x 1 kernel's PCG loop: chunks of two register entries of its longest row, own-column and
+        // helper list (what build_list's wlen gives), and whether some lane's list goes beyond the register capacity
+        I.wave_class.clear();
+        if (h->T == 512 && h->EPT == 1) {
+            const int *ptr[3] = {&h_rs_ptr[i * (NS + 1)], &h_cs_ptr[i * (NS + 1)], &h_hs_ptr[i * (NS + 1)]};
+            for (int w = 0; w < W; w++) {
+                int len[3][64], cls[4];
+                for (int t = 0; t < 3; t++)
+                    for (int p = 0; p < 64; p++) len[t][p] = ptr[t][64 * w + p + 1] - ptr[t][64 * w + p];
+                lpbox_wave_class_rule(64, len[0], len[1], len[2], cls);
+                I.wave_class.insert(I.wave_class.end(), cls, cls + 4);
+            }
+        }
         for (int r = 0; r < I.l; r++) h_f[i * LS + r] = I.f_org[r];
         h_isc[i * NI_COUNT + NI_N] = I.n; h_isc[i * NI_COUNT + NI_L] = I.l; h_isc[i * NI_COUNT + NI_NNZ] = I.nnz;
         h_isc[i * NI_COUNT + NI_ACTIVE] = 1;
@@ -1369,6 +1387,42 @@ int lpbox_get_config(lpbox_t *h, int *threads, int *elems_per_thread, int *lds_b
     if (elems_per_thread) *elems_per_thread = h->EPT;
     if (lds_bytes) *lds_bytes = (int)h->lds;
     return LPBOX_OK;
+}
+
+int lpbox_get_pcg_loop(lpbox_t *h, int *specialised) {
+    if (!valid_handle(h) || h->seg) return fail(LPBOX_E_BADHANDLE, "bad handle");
+    int rc = finalize(h);
+    if (rc) return rc;
+    if (!specialised) return fail(LPBOX_E_BADARG, "null output");
+    *specialised = (h->order != LPBOX_ORDER_REFERENCE && !h->direct && !h->log_on && lp_pcg_specialised(h->T, h->EPT) && !h->pcg_generic) ? 1 : 0;
+    return LPBOX_OK;
+}
+
+int lpbox_wave_class_rule(int lanes, const int *row_len, const int *col_len, const int *help_len, int *class4) {
+    if (lanes < 0 || !class4 || (lanes > 0 && (!row_len || !col_len || !help_len))) return fail(LPBOX_E_BADARG, "null or negative argument");
+    int cap[3];
+    lp_pcg_list_caps(&cap[0], &cap[1], &cap[2]);
+    const int *len[3] = {row_len, col_len, help_len};
+    class4[0] = class4[1] = class4[2] = class4[3] = 0;
+    for (int t = 0; t < 3; t++)
+        for (int p = 0; p < lanes; p++) {
+            class4[t] = std::max(class4[t], (std::min(len[t][p], cap[t]) + 1) / 2);
+            if (len[t][p] > cap[t]) class4[3] = 1;
+        }
+    return LPBOX_OK;
+}
+
+int lpbox_get_wave_classes(lpbox_t *h, int idx, int *classes4) {
+    int rc = check_idx(h, idx);
+    if (rc) return rc;
+    if (h->seg) return fail(LPBOX_E_BADHANDLE, "bad handle");
+    rc = finalize(h);
+    if (rc) return rc;
+    if (!classes4) return fail(LPBOX_E_BADARG, "null output");
+    const LpInstance &I = h->inst[idx];
+    if (I.wave_class.empty()) return fail(LPBOX_E_UNSUPPORTED, "wave classes are defined for the 512 x 1 kernel of the default order");
+    for (size_t k = 0; k < I.wave_class.size(); k++) classes4[k] = I.wave_class[k];
+    return (int)(I.wave_class.size() / 4);
 }
 
 int lpbox_get_layout(lpbox_t *h, int idx, int *pos_of_var) {

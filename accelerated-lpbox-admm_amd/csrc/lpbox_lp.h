@@ -75,6 +75,7 @@ struct LpBatchDev {
     double *logbuf; int log_cap;
     unsigned long long *stamps;   // diagnostic build only (LPBOX_STAMPS): 16 phase counters per instance, else nullptr
     int stamp_wave;               // ... of this wavefront of the workgroup (LPBOX_STAMP_WAVE, default 0)
+    int pcg_generic;              // 1: every wave of the 512 x 1 kernel runs the generic PCG loop (LPBOX_LP_PCGLOOP=generic), 0: specialised per wave
 };
 
 // one log record: PCG iterations, |x|, |y1|, |y2|, |y3|, |z1|, |z2|, |z4|, b.x, b.round(x), device wall-clock ticks since the launch started, iteration
@@ -88,6 +89,9 @@ hipError_t lp_launch_window(const LpBatchDev &bd, int T, int EPT, size_t lds, in
                             hipStream_t s, bool direct = false, bool log = false);
 // lpbox_debug_block_sum: block_sum<T, NV, stage> `rounds` times in `groups` workgroups; hipErrorInvalidConfiguration = not compiled
 hipError_t lp_launch_debug_block_sum(int T, int NV, int stage, int groups, int rounds, const double *in, double *out, hipStream_t s);
+// 512 x 1 kernel: PCG loops compiled per wave class (false: diagnostic builds, other geometries) and the class rule's list capacities
+bool lp_pcg_specialised(int T, int EPT);
+void lp_pcg_list_caps(int *rows, int *cols, int *help);
 bool lp_log_supported(int T, int EPT);         // geometries the logging variant is compiled for (the default ones: 512 threads)
 bool lp_direct_supported(int T, int EPT);      // geometries the DIRECT variant is compiled for
 // opt-in reference-order kernels (lpbox_lp_ref_kernels.hip, lpbox_set_order): identity layout, 512 threads, EPT = 1, 2 or 4

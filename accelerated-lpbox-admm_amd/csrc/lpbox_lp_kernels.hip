@@ -51,6 +51,18 @@ namespace {
 #define STAMP_POST(k) STAMP(k)
 #endif
 
+#ifndef LPBOX_LP_G1
+#define LPBOX_LP_G1 2      // granularity of the wave-uniform list length of the one-slot gathers (gather_all)
+#endif
+// The per-wave specialised PCG loops of the 512 x 1 kernel (see lp_window_kernel) are built for the shipped kernel only: the diagnostic
+// builds (stamps, knock-outs, another list granularity) keep the one generic loop.
+#if !defined(LPBOX_STAMPS) && !defined(LPBOX_KO_COLCAP) && !defined(LPBOX_KO_ROWCAP) && !defined(LPBOX_KO_NOMUL) && !defined(LPBOX_KO_ROWS) && \
+    !defined(LPBOX_KO_COLS) && !defined(LPBOX_KO_RED1) && !defined(LPBOX_KO_RED2) && !defined(LPBOX_KO_DIV) && !defined(LPBOX_KO_FIXED_PCG) && LPBOX_LP_G1 == 2
+#define LPBOX_PCG_SPEC 1
+#else
+#define LPBOX_PCG_SPEC 0
+#endif
+
 // ------------------------------------------------------------------------------------------------
 // LDS carve-up shared by the launcher (size) and the kernel (pointers)
 // ------------------------------------------------------------------------------------------------
@@ -88,6 +100,19 @@ __host__ __device__ constexpr bool lp_is_lean(int T, int EPT) { return EPT >= 4 
 // second stage of block_sum per geometry of lp_window_kernel (each measured on its own)
 __host__ __device__ constexpr int lp_red_stage(int T, int EPT) {
     return T == 512 && EPT == 1 ? RED_STAGE_PAIRS : RED_STAGE_BCAST;     // (512 x 4: 81.5 vs 77.4 us per iteration with PAIRS, it keeps the default)
+}
+
+// PCG loop of lp_window_kernel per geometry.  512 x 1 (not DIRECT, not LOG): the exit tests are made wave-uniform for the compiler (a
+// scalar loop, no exec-mask bookkeeping), and a wave whose three gather lists sit in registers runs a copy of the loop compiled for its
+// chunk counts (rn, cn, hn) = ceil(wlen / 2) of the row, own-column and helper list -- the lengths never change during a launch, so the
+// per-iteration dispatch of gather_all moves out of the loop.  Measured on its own like lp_red_stage.
+constexpr int LP_PCG_RCAP = 12, LP_PCG_CCAP = 12, LP_PCG_HCAP = 8;      // register capacities of the three lists of the 512 x 1 kernel
+__host__ __device__ constexpr bool lp_pcg_scalar_loop(int T, int EPT, bool direct, bool log) { return LPBOX_PCG_SPEC != 0 && T == 512 && EPT == 1 && !direct && !log; }
+__host__ __device__ constexpr bool lp_pcg_spec_geometry(int T, int EPT, bool direct, bool log) { return lp_pcg_scalar_loop(T, EPT, direct, log); }
+// the triples a loop is compiled for; every other one (and every wave with a list tail) runs the generic loop, so results never
+// depend on this set
+__host__ __device__ constexpr bool lp_pcg_spec_built(int rn, int cn, int hn) {
+    return rn >= 0 && rn <= LP_PCG_RCAP / 2 && cn >= 0 && cn <= LP_PCG_CCAP / 2 && hn >= 0 && hn <= LP_PCG_HCAP / 2;
 }
 
 typedef __attribute__((address_space(3))) double lds_double;
@@ -183,9 +208,6 @@ __device__ __forceinline__ void gather_all(const Lists<C> &g, const uint16_t *id
 #pragma unroll
     for (int s = 0; s < N; s++) acc[s] = 0.0;
     if constexpr (N == 1) {
-#ifndef LPBOX_LP_G1
-#define LPBOX_LP_G1 2
-#endif
         constexpr int G1 = LPBOX_LP_G1;                                // granularity of the wave-uniform list length (a straight-line path per multiple)
         int nch_ = (g.wlen[0] + G1 - 1) / G1;
 #ifdef LPBOX_KO_COLCAP
@@ -247,6 +269,21 @@ __device__ __forceinline__ void gather_all(const Lists<C> &g, const uint16_t *id
         }
         out[s] = acc[s];
     });
+}
+
+// One-slot lists with the chunk count K = ceil(wlen / G1) known at compile time (the specialised PCG loops): the reads and the ordered
+// additions that gather_all's dispatch runs for nch == K.
+template <int COMP, int K, typename C>
+__device__ __forceinline__ void list_read(const Lists<C> &g, double (&v)[K > 0 ? K * LPBOX_LP_G1 : 1]) {
+#pragma unroll
+    for (int q = 0; q < K * LPBOX_LP_G1; q++) v[q] = lds_ld<COMP>(g.addr[q]);
+}
+template <int K, typename OP>
+__device__ __forceinline__ double list_sum(const double (&v)[K > 0 ? K * LPBOX_LP_G1 : 1], OP op) {
+    double acc = 0.0;
+#pragma unroll
+    for (int q = 0; q < K * LPBOX_LP_G1; q++) acc = op(acc, v[q]);
+    return acc;
 }
 
 // two sums per slot from components CA and CB of the gathered elements (rhs assembly)
@@ -445,6 +482,11 @@ template <int T, int EPT, typename RCAPS, typename CCAPS, typename HCAPS, bool D
 __global__ void __launch_bounds__(T) lp_window_kernel(LpBatchDev bd, int iter_start, int iter_end, int mode) {
     const int l2f = mode & 1, rec = mode & 2;     // rec: keep x after every iteration in xhist (x_iters of the l2f loop; print_fix_info 2/3 of the plain loop)
     constexpr int RS = (DIRECT || LOG) ? RED_STAGE_BCAST : lp_red_stage(T, EPT);    // second stage of every block_sum of this kernel
+    constexpr bool SCALAR_LOOP = lp_pcg_scalar_loop(T, EPT, DIRECT, LOG), SPEC = lp_pcg_spec_geometry(T, EPT, DIRECT, LOG);
+    // A test on a value that came out of block_sum is the same in every lane, which the compiler cannot see: it builds the PCG loop as a
+    // divergent one (iteration counter in a vector register, exec-mask save / restore behind both reductions).  Going through the lane
+    // mask (v_cmp into a scalar pair, s_cmp_lg_u64) states the uniformity.  All lanes of a wave are active wherever this is used.
+    auto uni = [](bool c) { if constexpr (SCALAR_LOOP) return __builtin_amdgcn_ballot_w64(c) != 0; else return c; };
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int inst = blockIdx.x, tid = threadIdx.x;
     int *isc = bd.isc + (size_t)inst * NI_COUNT;
@@ -588,15 +630,20 @@ __global__ void __launch_bounds__(T) lp_window_kernel(LpBatchDev bd, int iter_st
         clong[s] = (cm & 0x8000) != 0;
         anyhelp[s] = wave_max_int(s_hs_ptr[pos + 1] - s_hs_ptr[pos]) > 0;
     });
+    // specialised PCG loops: this wave's chunk counts, and whether it may run one (no list tail, not switched off by the host)
+    int spec_rn = 0, spec_cn = 0, spec_hn = 0;
+    bool spec_ok = false;
+    if constexpr (SPEC) {
+        static_assert(RCAPS::at(0) == LP_PCG_RCAP && CCAPS::at(0) == LP_PCG_CCAP && HCAPS::at(0) == LP_PCG_HCAP, "capacities of the 512 x 1 kernel");
+        spec_rn = (rl.wlen[0] + 1) / 2; spec_cn = (cl.wlen[0] + 1) / 2; spec_hn = (hl.wlen[0] + 1) / 2;
+        spec_ok = !bd.pcg_generic && !(rl.tail_any[0] | cl.tail_any[0] | hl.tail_any[0]);
+    }
     auto op_add = [](double acc, double v) { return acc + v; };                 // res += 1.0 * v
     // out = (E * gx)_row for this thread's row tasks: the G lanes of a task add their interleaved share of the row in
     // ascending column order, then combine by an xor butterfly inside the (aligned) lane group; every lane of the group
     // ends up with the row sum, the leader uses it.
     constexpr int GX2 = T * EPT + 2;             // the second n-vector of gx, as an immediate ds_read offset in doubles
-    auto rows_gather_at = [&](auto COMPC, double (&out)[EPT]) {
-        double part[EPT];
-        if constexpr (LEAN) touch_list(rl);
-        gather_all<RCAPS, 8, decltype(COMPC)::value>(rl, s_rs_col, op_add, part);
+    auto rows_combine = [&](const double (&part)[EPT], double (&out)[EPT]) {
         static_for<EPT>([&](auto S) {
             constexpr int s = decltype(S)::value;
             double v = part[s];
@@ -605,6 +652,12 @@ __global__ void __launch_bounds__(T) lp_window_kernel(LpBatchDev bd, int iter_st
             if (rGmax[s] >= 8) { const double u = v + dpp_mov<0x141>(v); v = rG(s) >= 8 ? u : v; }
             out[s] = v;
         });
+    };
+    auto rows_gather_at = [&](auto COMPC, double (&out)[EPT]) {
+        double part[EPT];
+        if constexpr (LEAN) touch_list(rl);
+        gather_all<RCAPS, 8, decltype(COMPC)::value>(rl, s_rs_col, op_add, part);
+        rows_combine(part, out);
     };
     auto rows_gather = [&](double (&out)[EPT]) { rows_gather_at(std::integral_constant<int, 0>{}, out); };
 
@@ -945,12 +998,108 @@ __global__ void __launch_bounds__(T) lp_window_kernel(LpBatchDev bd, int iter_st
             STAMP(2)
             const double rhsNorm2 = p3[0];
             double residualNorm2 = p3[1], absNew = p3[2];
-            if (rhsNorm2 == 0) {                                      // :273-278
+            if (uni(rhsNorm2 == 0)) {                                 // :273-278
 #pragma unroll
                 for (int s = 0; s < EPT; s++) xt[s] = 0.0;
             } else {
                 double threshold = LP_PCG_TOL * LP_PCG_TOL * rhsNorm2;    // :281
                 if (threshold < DBL_MIN) threshold = DBL_MIN;
+                if constexpr (SCALAR_LOOP) {
+                    // One PCG loop body.  RK, CK, HK >= 0: the chunk counts of this wave's row, own-column and helper list are compile-time
+                    // constants (no list has a tail) -- straight-line reads right behind the barriers.
+                    // -1: the lists are walked by gather_all's run-time dispatch.  Same expressions on the
+                    // same operands and the same four barriers either way, so the waves of a workgroup may run different copies.
+                    auto pcg_loop = [&](auto RKC, auto CKC, auto HKC) {
+                        constexpr int RK = decltype(RKC)::value, CK = decltype(CKC)::value, HK = decltype(HKC)::value;
+                        static_assert((RK >= 0) == (CK >= 0) && (RK >= 0) == (HK >= 0) && (RK < 0 || EPT == 1), "all three lists or none");
+                        while (k_it < LP_PCG_MAXITERS) {                  // :296
+#pragma unroll
+                            for (int s = 0; s < EPT; s++) gx[s * T + tid] = live[s] ? p[s] : 0.0;
+                            __syncthreads();
+                            {
+                                double q[EPT];
+                                if constexpr (RK >= 0) {
+                                    double v[RK > 0 ? RK * LPBOX_LP_G1 : 1], part[EPT];
+                                    list_read<0, RK>(rl, v);
+                                    part[0] = list_sum<RK>(v, op_add);
+                                    rows_combine(part, q);
+                                } else rows_gather(q);
+#pragma unroll
+                                // the column product adds (rho4 * 1.0) * q_i per ENTRY (LPcpp:115-162): that product is the same value for every
+                                // column that meets row i, so the row's owner forms it once and publishes r4 * q_i -- one multiplication per row
+                                // instead of one per entry of E in the gather below; fl(acc + fl(r4 * q_i)) is unchanged bit for bit
+                                for (int s = 0; s < EPT; s++) if (rvalid(s)) gl[3 * rgl(s)] = r4 * q[s];
+                            }
+                            __syncthreads();
+                            double tmp[EPT];
+                            double p1[1] = {0.0};
+                            if constexpr (CK >= 0) {                      // entries already carry the factor r4
+                                double vo[CK > 0 ? CK * LPBOX_LP_G1 : 1], vh[HK > 0 ? HK * LPBOX_LP_G1 : 1];
+                                // (the own list is read and summed before the helper reads are issued, and the fence keeps it so: issuing
+                                //  both lists' reads together was measured 0.7 % slower)
+                                list_read<0, CK>(cl, vo);
+                                const double own = list_sum<CK>(vo, op_add);
+                                __builtin_amdgcn_sched_barrier(0);
+                                list_read<0, HK>(hl, vh);
+                                if constexpr (HK > 0) {                   // (a wave has helper entries exactly when anyhelp is set)
+                                    const double ht = quad_sum(list_sum<HK>(vh, op_add));
+                                    tcol[0] = clong[0] ? own + ht : own;
+                                } else tcol[0] = own;
+                            } else cols_gather(std::integral_constant<int, 0>{}, op_add, tcol);
+#pragma unroll
+                            for (int s = 0; s < EPT; s++) {               // tmp = M p (:298), fused p.tmp
+                                const double t = tcol[s];
+                                double Mp = 0.0;
+                                Mp += dI * (1.0 * p[s]);
+                                Mp += t;
+                                tmp[s] = Mp;
+                                p1[0] = p1[0] + (live[s] ? p[s] * tmp[s] : 0.0);
+                            }
+                            block_sum<T, 1, RS>(p1, red, parity);
+                            const double alpha = absNew / p1[0];          // :300
+                            if (uni(alpha < 0)) { pcg_fail = true; break; }   // :301
+                            double p2[2] = {0.0, 0.0};
+                            double z[EPT];
+#pragma unroll
+                            for (int s = 0; s < EPT; s++) {
+                                xt[s] += alpha * p[s];                    // :302
+                                r[s] -= alpha * tmp[s];                   // :304
+                                z[s] = dinv[s] * r[s];                    // :314
+                                p2[0] = p2[0] + (live[s] ? r[s] * r[s] : 0.0);   // :305
+                                p2[1] = p2[1] + (live[s] ? r[s] * z[s] : 0.0);   // :317
+                            }
+                            block_sum<T, 2, RS>(p2, red, parity);
+                            residualNorm2 = p2[0];
+                            if (uni(residualNorm2 < threshold)) { k_it++; break; }    // :309-312
+                            const double absOld = absNew;
+                            absNew = p2[1];
+                            const double beta = absNew / absOld;          // :318
+#pragma unroll
+                            for (int s = 0; s < EPT; s++) p[s] = z[s] + beta * p[s];   // :319
+                            k_it++;
+                        }
+                    };
+                    constexpr std::integral_constant<int, -1> GEN{};
+                    if (uni(!(residualNorm2 < threshold))) {              // :284
+                        if constexpr (SPEC) {
+                            bool ran = false;
+                            if (spec_ok) {                                // wave-uniform; chosen per outer iteration, fixed for the launch
+                                dispatch_chunks<LP_PCG_RCAP / 2>(spec_rn, [&](auto R) {
+                                    dispatch_chunks<LP_PCG_CCAP / 2>(spec_cn, [&](auto Cn) {
+                                        dispatch_chunks<LP_PCG_HCAP / 2>(spec_hn, [&](auto H) {
+                                            if constexpr (lp_pcg_spec_built(decltype(R)::value, decltype(Cn)::value, decltype(H)::value)) {
+                                                pcg_loop(R, Cn, H);
+                                                ran = true;
+                                            }
+                                        });
+                                    });
+                                });
+                            }
+                            if (!ran) pcg_loop(GEN, GEN, GEN);
+                        } else pcg_loop(GEN, GEN, GEN);
+                    }
+                } else {
+                // every other kernel: the loop as it has been measured, walked by gather_all's run-time dispatch
                 if (!(residualNorm2 < threshold)) {                   // :284
                     while (k_it < LP_PCG_MAXITERS) {                  // :296
 #pragma unroll
@@ -1039,6 +1188,7 @@ __global__ void __launch_bounds__(T) lp_window_kernel(LpBatchDev bd, int iter_st
                         k_it++;
                         STAMP(10)
                     }
+                }
                 }
             }
             }   // PCG
@@ -1296,6 +1446,8 @@ size_t lp_window_lds_bytes(int T, int NS, int LS, int ZS, int HL, int HLD) {
     return LdsLayout(NS, LS, ZS, lp_is_lean(T, NS / T), HL, HLD).total;
 }
 
+bool lp_pcg_specialised(int T, int EPT) { return lp_pcg_spec_geometry(T, EPT, false, false); }
+void lp_pcg_list_caps(int *rows, int *cols, int *help) { *rows = LP_PCG_RCAP; *cols = LP_PCG_CCAP; *help = LP_PCG_HCAP; }
 bool lp_direct_supported(int T, int EPT) { return T == 512 && EPT == 1; }     // the default geometry of every n <= 512 batch
 bool lp_log_supported(int T, int EPT) { return T == 512 && (EPT == 1 || EPT == 2 || EPT == 4); }
 

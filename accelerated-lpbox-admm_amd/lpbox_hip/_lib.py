@@ -80,6 +80,9 @@ SYMBOLS = {
     "lpbox_seg_get_problem": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.POINTER(C.c_double)]),
     "lpbox_get_config": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "lpbox_get_pcg_loop": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "lpbox_get_wave_classes": (C.c_int, [C.c_void_p, C.c_int, _ip]),
+    "lpbox_wave_class_rule": (C.c_int, [C.c_int, _ip, _ip, _ip, _ip]),
     "lpbox_get_layout": (C.c_int, [C.c_void_p, C.c_int, _ip]),
     "lpbox_get_row_split": (C.c_int, [C.c_void_p, C.c_int, _ip]),
     "lpbox_get_col_split": (C.c_int, [C.c_void_p, C.c_int, _ip, _ip]),

@@ -26,6 +26,15 @@ def _as_int(v, name):
     return iv
 
 
+def wave_class_rule(row_len, col_len, help_len):
+    """(rn, cn, hn, tail) of a wavefront of the 512 x 1 kernel from the list lengths of its lanes (lpbox_wave_class_rule; host only)."""
+    a = [np.ascontiguousarray(v, np.int32) for v in (row_len, col_len, help_len)]
+    assert len(a[0]) == len(a[1]) == len(a[2])
+    out = np.zeros(4, np.int32)
+    check(_lib.load().lpbox_wave_class_rule(len(a[0]), a[0], a[1], a[2], out), "lpbox_wave_class_rule")
+    return tuple(int(v) for v in out)
+
+
 class LpBatch:
     """B independent LP instances solved together on one GPU (extension; no reference counterpart).
 
@@ -242,7 +251,16 @@ class LpBatch:
     def config(self):
         t, e, l = C.c_int(), C.c_int(), C.c_int()
         check(self._L.lpbox_get_config(self._h, C.byref(t), C.byref(e), C.byref(l)), "lpbox_get_config")
-        return dict(threads=t.value, elems_per_thread=e.value, lds_bytes=l.value)
+        sp = C.c_int()
+        check(self._L.lpbox_get_pcg_loop(self._h, C.byref(sp)), "lpbox_get_pcg_loop")
+        return dict(threads=t.value, elems_per_thread=e.value, lds_bytes=l.value, pcg_loop="specialised" if sp.value else "generic")
+
+    def wave_classes(self, idx=0):
+        """(waves, 4) array of (rn, cn, hn, tail) per wavefront of the 512 x 1 kernel: chunks of two register entries of the wave's
+        longest row, own-column and helper list, and whether some lane's list exceeds its register capacity (lpbox_get_wave_classes)."""
+        out = np.zeros(64, np.int32)
+        w = check(self._L.lpbox_get_wave_classes(self._h, idx, out), "lpbox_get_wave_classes")
+        return out[:4 * w].reshape(w, 4).copy()
 
     def layout(self, idx=0):
         """Storage position of every variable (the reduction tree of the kernels is defined over positions)."""

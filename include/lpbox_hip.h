@@ -240,6 +240,18 @@ int lpbox_seg_get_problem(lpbox_t *h, int *n, int *nnz, int *rowptr, int *colidx
 /* Workgroup geometry picked for the batch: threads per instance and slots per thread (threads*slots storage positions;
  * the reduction tree depends on both). */
 int lpbox_get_config(lpbox_t *h, int *threads, int *elems_per_thread, int *lds_bytes);
+/* PCG loop of the on-chip LP kernel: *specialised = 1 when a wavefront whose gather lists sit in registers runs a copy of the loop
+ * compiled for its list lengths (512 threads x 1 slot, default order and x-update, no iteration log), 0 when every wavefront runs the
+ * generic loop (every other geometry and mode; LPBOX_LP_PCGLOOP=generic in the environment when the problem is uploaded).  Both give
+ * the same bits. */
+int lpbox_get_pcg_loop(lpbox_t *h, int *specialised);
+/* 512 x 1 kernel: class of every wavefront w of instance idx in the PCG loop, classes4[4*w + {0,1,2,3}] = rn, cn, hn, tail: the
+ * chunks of two register entries of the wave's longest row list (capacity 12), own-column list (12) and helper list (8), i.e.
+ * ceil(min(longest, capacity) / 2), and tail = 1 when some list of a lane is longer than its capacity (such a wave always runs the
+ * generic loop).  Returns the number of wavefronts (8); LPBOX_E_UNSUPPORTED for other geometries and the reference order. */
+int lpbox_get_wave_classes(lpbox_t *h, int idx, int *classes4);
+/* The class rule itself, on the list lengths of the lanes of one wavefront (host only, no device needed): class4 = rn, cn, hn, tail. */
+int lpbox_wave_class_rule(int lanes, const int *row_len, const int *col_len, const int *help_len, int *class4);
 /* Storage position of every variable of instance idx (pos_of_var[org_n]): the kernels keep variables sorted by column
  * length, and the reduction tree is defined over positions (element at position p -> thread p % threads). */
 int lpbox_get_layout(lpbox_t *h, int idx, int *pos_of_var);

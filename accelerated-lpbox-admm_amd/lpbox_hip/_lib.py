@@ -91,6 +91,7 @@ SYMBOLS = {
     "lpbox_kernel_time": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.c_int]),
     "lpbox_debug_get_vec": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, _dp, C.c_int]),
     "lpbox_debug_get_scalar": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.POINTER(C.c_double)]),
+    "lpbox_debug_get_lp_table": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, _ip, C.c_int]),
     "lpbox_debug_block_sum": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp]),
     "lpbox_set_log": (C.c_int, [C.c_void_p, C.c_int]),
     "lpbox_get_log": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int]),

@@ -304,6 +304,16 @@ class LpBatch:
         k = check(self._L.lpbox_debug_get_vec(self._h, idx, name.encode(), out, cap), "lpbox_debug_get_vec")
         return out[:k].copy()
 
+    def debug_table(self, name, idx=0):
+        """One of the index tables the kernels read (rs_ptr, rs_col, cs_ptr, cs_row, hs_ptr, rid, rgl, rmeta, cmeta) for instance idx, at the
+        stride of the batch (lpbox_debug_get_lp_table).  Host only, like config / layout / row_split / col_split / wave_classes."""
+        cfg = self.config()
+        nnz = max(check(self._L.lpbox_get_problem_lp_vals(self._h, i, None), "lpbox_get_problem_lp_vals") for i in range(self.B))
+        cap = max(cfg["threads"] * cfg["elems_per_thread"] + 1, nnz + 8)
+        out = np.zeros(cap, np.int32)
+        k = check(self._L.lpbox_debug_get_lp_table(self._h, idx, name.encode(), out, cap), "lpbox_debug_get_lp_table")
+        return out[:k].copy()
+
     def debug_scalar(self, name, idx=0):
         v = C.c_double()
         check(self._L.lpbox_debug_get_scalar(self._h, idx, name.encode(), C.byref(v)), "lpbox_debug_get_scalar")

@@ -14,7 +14,11 @@
  *  - one handle owns one HIP stream; calls on a handle are synchronous and must be serialised by the
  *    caller; different handles may be used from different host threads;
  *  - all arithmetic is fp64 (LPh:16), indices int32 on the API, uint16 inside the kernels;
- *  - there is NO CPU fallback: without a HIP device every compute call fails with LPBOX_E_NODEVICE.
+ *  - there is NO CPU fallback: without a HIP device every compute call fails with LPBOX_E_NODEVICE.  Only the questions about the
+ *    planned layout of an LP batch, which no device is involved in, are answered without one: lpbox_get_config, lpbox_get_pcg_loop,
+ *    lpbox_get_layout, lpbox_get_row_split, lpbox_get_col_split, lpbox_get_wave_classes, lpbox_get_direct_rows and
+ *    lpbox_debug_get_lp_table.  All but lpbox_get_direct_rows plan the layout, which freezes the problem and the
+ *    summation order of the handle as lpbox_init does.
  */
 #ifndef LPBOX_HIP_H
 #define LPBOX_HIP_H
@@ -127,7 +131,8 @@ int lpbox_set_x_update(lpbox_t *h, int mode);
 int lpbox_set_order(lpbox_t *h, int mode);
 /* The row split of the direct mode for instance idx (the order of its arithmetic; tests hand it to the oracle's mirror): gidx_of_row[l] =
  * dense index of the row among the rows solved through the on-chip inverse, -1 for a row handled in closed form (its columns meet no
- * other such row).  Returns the number of dense rows. */
+ * other such row).  Returns the number of dense rows.  A function of the instance alone: it answers before lpbox_set_x_update and
+ * without a device. */
 int lpbox_get_direct_rows(lpbox_t *h, int idx, int *gidx_of_row);
 /* Segmentation flavour: with record on (on == 1: up to 2000 iterations, on > 1: that many), lpbox_seg_legacy keeps x_sol of every iteration
  * (print_info 1 -> ../xiter/<problem>.csv, SEGcpp:1209-1213, 1270-1277).  out == NULL: number of iterations recorded; otherwise copies
@@ -280,6 +285,12 @@ int lpbox_kernel_time(lpbox_t *h, double *ms_total, long long *launches, int res
 /* Copy a named device state vector of instance idx ("x","z1","z2","z4","f","pd","b"); returns its length. */
 int lpbox_debug_get_vec(lpbox_t *h, int idx, const char *name, double *out, int cap);
 int lpbox_debug_get_scalar(lpbox_t *h, int idx, const char *name, double *out);
+/* LP flavour, host only (no device needed): one of the index tables the kernels read, for instance idx, as the device sees it -- at the
+ * stride of the batch, padding included, widened to int.  name = "rs_ptr", "cs_ptr", "hs_ptr" (threads x slots + 1 entries: the lists of
+ * the row task / own column part / helper chunk of every slot), "rs_col", "cs_row" (the index pools they point into), "rid", "rgl",
+ * "rmeta", "cmeta" (per slot: row of the task or 0xFFFF, its storage index, lanes << 4 | lane, column length with bit 15 = split).
+ * Plans the layout like lpbox_get_layout does; returns the number of entries. */
+int lpbox_debug_get_lp_table(lpbox_t *h, int idx, const char *name, int *out, int cap);
 /* Test entry for the workgroup reduction of the LP kernels (no solver state, used by no product path): `groups` workgroups of `threads`
  * threads each call the reduction `rounds` times back to back on one scratch area.  in[(r * threads + t) * nv + k] is thread t's
  * partial of value k in round r (the same for every workgroup); out[((g * rounds + r) * threads + t) * nv + k] is what thread t of

@@ -120,6 +120,14 @@ struct lpbox_solver {
     bool record = false;   // plain loop keeps x of every iteration (lpbox_set_record; print_fix_info 2/3)
     long xi_out_stride = 0;
     int xi_out_ws = 0;
+    // row table of the last l2f window for a policy on the device (lpbox_get_x_iters_rows_device) and what the device decided from its scores
+    DevBuf<long long> row_off;
+    DevBuf<int> first_row, fix_counts;
+    DevBuf<uint8_t> fix_codes;
+    std::vector<int> h_first_row;     // B + 1: stacked rows of instance i are h_first_row[i] .. h_first_row[i + 1] - 1
+    bool rows_valid = false;          // built since the last window
+    bool rows_mask_changed = false;   // lpbox_set_active changed the mask after it was built
+    int rows_ws = 0;
     std::vector<int> h_isc;   // host mirror, refreshed after every solver call
     std::vector<double> h_dsc;
 
@@ -432,6 +440,7 @@ void lpbox_destroy(lpbox_t *h) {
     h->x.release(); h->z1.release(); h->z2.release(); h->b.release(); h->pd.release(); h->z4.release(); h->f.release();
     h->f_org.release(); h->dsc.release(); h->hist.release(); h->dctl.release(); h->c1_init.release(); h->xhist.release();
     h->vr.release(); h->vc.release(); h->r4v.release();
+    h->row_off.release(); h->first_row.release(); h->fix_counts.release(); h->fix_codes.release();
     h->xi_out.release(); h->live.release(); h->newfix.release(); h->stamps.release(); h->logbuf.release(); h->Hinv.release(); h->rdir.release(); h->dng.release();
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -517,6 +526,7 @@ int lpbox_init(lpbox_t *h) {
         I.xi_rows = 0; I.xi_left_idx.clear();
     }
     h->xi_valid = false;
+    h->rows_valid = false;
     HIPCHK(hipMemsetAsync(h->ctl.p, 0, (size_t)h->B * 4 * sizeof(int), h->stream));
     if (h->order == LPBOX_ORDER_REFERENCE) HIPCHK(lp_ref_launch_init(h->dev(), h->ref_vals(), h->lds, h->f_org.p, h->c1_init.p, h->live_init.p, h->stream));
     else HIPCHK(lp_launch_init(h->dev(), h->geo.T, h->geo.EPT, h->f_org.p, h->c1_init.p, h->live_init.p, h->stream));
@@ -546,6 +556,73 @@ static int stage_xiters(lpbox_t *h, int ws, const std::vector<int> &h_ctl, const
     return LPBOX_OK;
 }
 
+}  // extern "C"
+
+namespace {
+
+// The part of an l2f window the two entry points share (LPcpp:1124-1206 index bookkeeping, then the launch): instance i fixes num[i] of
+// its live variables, code_of(i, q) is the code of the q-th one (2 = fix to 1, 1 = fix to 0, 0 = stays live).  host_newfix: the codes go
+// to the device from here (the vec form); false = the decide kernel has already written them (the scores form).
+template <typename CodeOf>
+int l2f_window(lpbox_t *h, int iter_start, int iter_end, const std::vector<int> &num, bool host_newfix, CodeOf code_of, int *rets) {
+    const int ws = iter_end - iter_start;
+    const size_t B = h->B, NS = h->geo.NS;
+    std::vector<int> h_ctl(B * 4, 0);
+    std::vector<double> h_dctl(B, 0.0);
+    std::vector<uint8_t> h_newfix;
+    if (host_newfix) h_newfix.assign(B * NS, 0);
+    std::vector<int> h_rows(B, 0);
+    std::vector<int> h_left(B * NS, 0);
+    for (size_t i = 0; i < B; i++) {
+        LpInstance &I = h->inst[i];
+        const int n_live = (int)I.left_idx.size();
+        if (num[i] != 0) {                                                  // LPcpp:1124-1206 index bookkeeping
+            std::vector<int> keep;
+            keep.reserve(n_live - num[i]);
+            for (int q = 0; q < n_live; q++) {
+                const int org = I.left_idx[q];
+                const int code = code_of(i, q);
+                if (code == 0) keep.push_back(org);
+                else if (host_newfix) h_newfix[i * NS + I.lay.cpos[org]] = (uint8_t)code;
+            }
+            I.left_idx.swap(keep);
+            h_ctl[i * 4 + 0] = 1; h_ctl[i * 4 + 1] = num[i]; h_ctl[i * 4 + 2] = n_live - num[i];
+            h_dctl[i] = std::pow((double)(n_live - num[i]), 1.0 / 2);      // LPcpp:427 with the shrunken n
+        }
+        I.xi_rows = n_live - num[i];                                        // x_iters = Zero(n - fix_num, 500), :1113
+        I.xi_left_idx = I.left_idx;
+        h_rows[i] = I.xi_rows;
+        for (int q = 0; q < I.xi_rows; q++) h_left[i * NS + q] = I.lay.cpos[I.left_idx[q]];   // storage position of the q-th live variable
+    }
+    h->rows_valid = false;
+    int rc = stage_xiters(h, ws, h_ctl, h_dctl, host_newfix ? &h_newfix : nullptr, h_left, h_rows);
+    if (rc) return rc;
+    rc = run_window(h, iter_start, iter_end, 3);    // synchronises: the host staging vectors above stay alive until here
+    if (rc) return rc;
+    h->last_ws = ws;
+    h->xi_valid = true;
+    h->xi_out_ws = 0;
+    for (size_t i = 0; i < B; i++) {
+        if (rets) rets[i] = h->h_isc[i * NI_COUNT + NI_RET];
+    }
+    return h->h_isc[NI_RET];
+}
+
+// Pack the iterate windows of the whole batch at `ws` columns unless the last pack already did (once per (call, ws)).
+int pack_xiters(lpbox_t *h, int ws) {
+    if (h->xi_out_ws == ws) return LPBOX_OK;
+    const long stride = (long)h->geo.NS * ws;
+    if (h->xi_out.count < (size_t)h->B * stride) HIPCHK(h->xi_out.alloc((size_t)h->B * stride));
+    HIPCHK(lp_launch_pack_xiters(h->dev(), h->left_idx.p, h->xi_rows.p, ws, h->xi_out.p, stride, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->xi_out_ws = ws; h->xi_out_stride = stride;
+    return LPBOX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
 int lpbox_iterate(lpbox_t *h, int iter_start, int iter_end, int *rets) {
     if (valid_handle(h) && h->seg) return fail(LPBOX_E_STATE, "this entry point belongs to the LP flavour");
     if (!valid_handle(h)) return fail(LPBOX_E_BADHANDLE, "bad handle");
@@ -553,6 +630,7 @@ int lpbox_iterate(lpbox_t *h, int iter_start, int iter_end, int *rets) {
     int rc = use_device(h);
     if (rc) return rc;
     const bool rec = h->record && iter_end > iter_start;
+    h->rows_valid = false;
     if (rec) {                         // print_fix_info 2/3 (LPcpp:776-779,903-909): keep x of every iteration of this call
         const size_t B = h->B, NS = h->geo.NS;
         std::vector<int> h_ctl(B * 4, 0), h_rows(B, 0), h_left(B * NS, 0);
@@ -604,10 +682,7 @@ int lpbox_iterate_l2f(lpbox_t *h, int iter_start, int iter_end, const double *ve
     if (ws > LP_XITERS_COLS) return fail(LPBOX_E_BADARG, "window of %d iterations exceeds the %d columns of x_iters (LPcpp:1113)", ws, LP_XITERS_COLS);
     int rc = use_device(h);
     if (rc) return rc;
-    const size_t B = h->B, NS = h->geo.NS;
-    std::vector<int> h_ctl(B * 4, 0);
-    std::vector<double> h_dctl(B, 0.0);
-    std::vector<uint8_t> h_newfix;
+    const size_t B = h->B;
     bool any_fix = false;
     // validate everything before touching any state
     for (size_t i = 0; i < B; i++) {
@@ -627,43 +702,13 @@ int lpbox_iterate_l2f(lpbox_t *h, int iter_start, int iter_end, const double *ve
             any_fix = true;
         }
     }
-    if (any_fix) h_newfix.assign(B * NS, 0);
-    std::vector<int> h_rows(B, 0);
-    std::vector<int> h_left(B * NS, 0);
-    for (size_t i = 0; i < B; i++) {
-        LpInstance &I = h->inst[i];
-        const int n_live = (int)I.left_idx.size();
-        const int num = nums ? nums[i] : 0;
-        if (num != 0) {                                                     // LPcpp:1124-1206 index bookkeeping
-            const double *v = vec + (size_t)i * vec_stride;
-            std::vector<int> keep;
-            keep.reserve(n_live - num);
-            for (int q = 0; q < n_live; q++) {
-                const int org = I.left_idx[q];
-                if (v[q] == 1) h_newfix[i * NS + I.lay.cpos[org]] = 2;
-                else if (v[q] == 0) h_newfix[i * NS + I.lay.cpos[org]] = 1;
-                else keep.push_back(org);
-            }
-            I.left_idx.swap(keep);
-            h_ctl[i * 4 + 0] = 1; h_ctl[i * 4 + 1] = num; h_ctl[i * 4 + 2] = n_live - num;
-            h_dctl[i] = std::pow((double)(n_live - num), 1.0 / 2);         // LPcpp:427 with the shrunken n
-        }
-        I.xi_rows = n_live - num;                                           // x_iters = Zero(n - fix_num, 500), :1113
-        I.xi_left_idx = I.left_idx;
-        h_rows[i] = I.xi_rows;
-        for (int q = 0; q < I.xi_rows; q++) h_left[i * NS + q] = I.lay.cpos[I.left_idx[q]];   // storage position of the q-th live variable
-    }
-    rc = stage_xiters(h, ws, h_ctl, h_dctl, any_fix ? &h_newfix : nullptr, h_left, h_rows);
-    if (rc) return rc;
-    rc = run_window(h, iter_start, iter_end, 3);    // synchronises: the host staging vectors above stay alive until here
-    if (rc) return rc;
-    h->last_ws = ws;
-    h->xi_valid = true;
-    h->xi_out_ws = 0;
-    for (size_t i = 0; i < B; i++) {
-        if (rets) rets[i] = h->h_isc[i * NI_COUNT + NI_RET];
-    }
-    return h->h_isc[NI_RET];
+    std::vector<int> k(B, 0);
+    for (size_t i = 0; i < B; i++) k[i] = nums ? nums[i] : 0;
+    // the code of the q-th live variable: 2 = fix to 1, 1 = fix to 0, 0 = stays live
+    return l2f_window(h, iter_start, iter_end, k, any_fix, [&](size_t i, int q) {
+        const double v = vec[i * (size_t)vec_stride + q];
+        return v == 1 ? 2 : (v == 0 ? 1 : 0);
+    }, rets);
 }
 
 int lpbox_set_x_update(lpbox_t *h, int mode) {
@@ -852,7 +897,10 @@ int lpbox_set_active(lpbox_t *h, const int *active) {
     std::vector<int> a(h->B, 1);
     for (int i = 0; i < h->B && active; i++) a[i] = active[i] != 0;
     HIPCHK(hipMemcpy2D(h->isc.p + NI_ACTIVE, NI_COUNT * sizeof(int), a.data(), sizeof(int), sizeof(int), h->B, hipMemcpyHostToDevice));
-    for (int i = 0; i < h->B; i++) h->h_isc[(size_t)i * NI_COUNT + NI_ACTIVE] = a[i];
+    for (int i = 0; i < h->B; i++) {
+        if (h->h_isc[(size_t)i * NI_COUNT + NI_ACTIVE] != a[i]) h->rows_mask_changed = true;      // a row table built before this call is stale
+        h->h_isc[(size_t)i * NI_COUNT + NI_ACTIVE] = a[i];
+    }
     return LPBOX_OK;
 }
 
@@ -897,13 +945,8 @@ int lpbox_get_x_iters(lpbox_t *h, int idx, int ws, double *out) {
     rc = use_device(h);
     if (rc) return rc;
     const int wsd = std::min(ws, h->ws_cap);          // columns beyond the staged window stay zero, like the reference's matrix
-    if (h->xi_out_ws != wsd) {                         // pack the whole batch once per (call, ws)
-        const long stride = (long)h->geo.NS * wsd;
-        if (h->xi_out.count < (size_t)h->B * stride) HIPCHK(h->xi_out.alloc((size_t)h->B * stride));
-        HIPCHK(lp_launch_pack_xiters(h->dev(), h->left_idx.p, h->xi_rows.p, wsd, h->xi_out.p, stride, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        h->xi_out_ws = wsd; h->xi_out_stride = stride;
-    }
+    rc = pack_xiters(h, wsd);                          // the whole batch, once per (call, ws)
+    if (rc) return rc;
     if (wsd == ws) {
         HIPCHK(hipMemcpy(out, h->xi_out.p + (size_t)idx * h->xi_out_stride, sizeof(double) * (size_t)rows * ws, hipMemcpyDeviceToHost));
     } else {
@@ -922,16 +965,78 @@ int lpbox_get_x_iters_device(lpbox_t *h, int ws, void **dev_ptr, long *stride_do
     if (ws <= 0 || ws > h->ws_cap) return fail(LPBOX_E_BADARG, "ws = %d outside (0,%d] (the last window)", ws, h->ws_cap);
     int rc = use_device(h);
     if (rc) return rc;
-    if (h->xi_out_ws != ws) {
-        const long stride = (long)h->geo.NS * ws;
-        if (h->xi_out.count < (size_t)h->B * stride) HIPCHK(h->xi_out.alloc((size_t)h->B * stride));
-        HIPCHK(lp_launch_pack_xiters(h->dev(), h->left_idx.p, h->xi_rows.p, ws, h->xi_out.p, stride, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        h->xi_out_ws = ws; h->xi_out_stride = stride;
-    }
+    rc = pack_xiters(h, ws);
+    if (rc) return rc;
     if (dev_ptr) *dev_ptr = h->xi_out.p;
     if (stride_doubles) *stride_doubles = h->xi_out_stride;
     return LPBOX_OK;
+}
+
+long lpbox_get_x_iters_rows_device(lpbox_t *h, int ws, void **row_off_dev, int *first_row) {
+    if (valid_handle(h) && h->seg) return fail(LPBOX_E_STATE, "this entry point belongs to the LP flavour");
+    if (!valid_handle(h)) return fail(LPBOX_E_BADHANDLE, "bad handle");
+    if (!h->xi_valid) return fail(LPBOX_E_STATE, "solve_iter_l2f has not been called");
+    if (ws <= 0 || ws > h->ws_cap) return fail(LPBOX_E_BADARG, "ws = %d outside (0,%d] (the last window)", ws, h->ws_cap);
+    int rc = use_device(h);
+    if (rc) return rc;
+    rc = pack_xiters(h, ws);
+    if (rc) return rc;
+    const int B = h->B;
+    if (!h->rows_valid || h->rows_mask_changed || h->rows_ws != ws) {
+        h->rows_valid = false;
+        h->h_first_row.assign((size_t)B + 1, 0);
+        for (int i = 0; i < B; i++)
+            h->h_first_row[i + 1] = h->h_first_row[i] + (h->h_isc[(size_t)i * NI_COUNT + NI_ACTIVE] ? h->inst[i].xi_rows : 0);
+        const size_t rows = (size_t)h->h_first_row[B];
+        if (!h->first_row.p) { HIPCHK(h->first_row.alloc((size_t)B + 1)); HIPCHK(h->fix_counts.alloc(2 * (size_t)B)); }
+        if (h->row_off.count < rows) { HIPCHK(h->row_off.alloc(rows)); HIPCHK(h->fix_codes.alloc(rows)); }
+        HIPCHK(hipMemcpyAsync(h->first_row.p, h->h_first_row.data(), ((size_t)B + 1) * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        if (rows) HIPCHK(lp_launch_row_offsets(B, h->geo.NS, h->xi_rows.p, h->isc.p, h->first_row.p, ws, h->xi_out_stride, h->row_off.p, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));       // the caller reads the table on a stream of its own; h_first_row stays alive until here
+        h->rows_valid = true; h->rows_mask_changed = false; h->rows_ws = ws;
+    }
+    if (row_off_dev) *row_off_dev = h->row_off.p;
+    if (first_row) std::copy(h->h_first_row.begin(), h->h_first_row.end(), first_row);
+    return (long)h->h_first_row[B];
+}
+
+int lpbox_iterate_l2f_scores(lpbox_t *h, int iter_start, int iter_end, const float *scores_dev, double hi, double lo, int min_fix,
+                             int *rets, int *fixed) {
+    if (valid_handle(h) && h->seg) return fail(LPBOX_E_STATE, "this entry point belongs to the LP flavour (segmentation: lpbox_seg_batch_iterate_l2f_scores)");
+    if (!valid_handle(h)) return fail(LPBOX_E_BADHANDLE, "bad handle");
+    const int ws = iter_end - iter_start;
+    if (ws > LP_XITERS_COLS) return fail(LPBOX_E_BADARG, "window of %d iterations exceeds the %d columns of x_iters (LPcpp:1113)", ws, LP_XITERS_COLS);
+    if (min_fix < 0) return fail(LPBOX_E_BADARG, "min_fix = %d is negative", min_fix);
+    if (!std::isfinite(hi) || !std::isfinite(lo) || hi < lo) return fail(LPBOX_E_BADARG, "thresholds hi = %g, lo = %g: both must be finite and hi >= lo", hi, lo);
+    if (scores_dev && !h->rows_valid)
+        return fail(LPBOX_E_STATE, "scores given but lpbox_get_x_iters_rows_device has not been called since the last window");
+    if (scores_dev && h->rows_mask_changed)
+        return fail(LPBOX_E_STATE, "scores given but lpbox_set_active changed the active instances after the row table was built");
+    if (!h->inited) return fail(LPBOX_E_STATE, "solve_init has not been called");
+    int rc = use_device(h);
+    if (rc) return rc;
+    const size_t B = h->B;
+    std::vector<int> k(B, 0);
+    std::vector<uint8_t> codes;
+    const std::vector<int> first = h->h_first_row;      // (l2f_window invalidates the table)
+    if (scores_dev && first[B] > 0) {
+        std::vector<int> counts(2 * B, 0);
+        codes.resize((size_t)first[B]);
+        // codes of earlier windows sit at positions that have been fixed since: the decide kernel writes live positions only
+        HIPCHK(hipMemsetAsync(h->newfix.p, 0, B * (size_t)h->geo.NS, h->stream));
+        HIPCHK(lp_launch_decide_fix((int)B, h->geo.NS, scores_dev, h->xi_rows.p, h->isc.p, h->first_row.p, h->left_idx.p, hi, lo, h->newfix.p,
+                                    h->fix_codes.p, h->fix_counts.p, h->stream));
+        HIPCHK(hipMemcpyAsync(counts.data(), h->fix_counts.p, counts.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(codes.data(), h->fix_codes.p, codes.size(), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        for (size_t i = 0; i < B; i++) {
+            if (first[i + 1] == first[i]) continue;                         // parked
+            const int n = counts[2 * i] + counts[2 * i + 1];
+            if (n > min_fix) k[i] = n;                                      // LP/trainer.py:533-535: k <= min_fix fixes nothing
+        }
+    }
+    if (fixed) std::copy(k.begin(), k.end(), fixed);
+    return l2f_window(h, iter_start, iter_end, k, false, [&](size_t i, int q) { return (int)codes[(size_t)first[i] + q]; }, rets);
 }
 
 int lpbox_get_x_sol(lpbox_t *h, int idx, double *out) {

@@ -111,3 +111,12 @@ hipError_t lp_ref_launch_window(const LpBatchDev &bd, const LpRefVals &vv, int E
                                 hipStream_t s);
 hipError_t lp_launch_pack_xiters(const LpBatchDev &bd, const int *live_pos, const int *rows, int ws, double *out,
                                  long out_stride, hipStream_t s);
+// early-fixing loop with the policy on the device (lpbox_lp_fix_kernels.hip).  rows = live rows per instance of the last window, isc = the
+// int scalars (NI_ACTIVE decides whether an instance has rows at all), first = B + 1 ints, exclusive prefix of the rows of the ACTIVE
+// instances (from the host).  out[first[i] + q] = i * stride + q * ws.
+hipError_t lp_launch_row_offsets(int B, int NS, const int *rows, const int *isc, const int *first, int ws, long stride, long long *out,
+                                 hipStream_t s);
+// deter_fix_2 on float32 scores, one workgroup per instance: code 2 (s > hi), 1 (s < lo) or 0 per stacked row into codes[first[i] + q] and
+// into newfix[i * NS + live_pos[i * NS + q]]; counts[2 i] = codes 2, counts[2 i + 1] = codes 1.
+hipError_t lp_launch_decide_fix(int B, int NS, const float *scores, const int *rows, const int *isc, const int *first, const int *live_pos,
+                                double hi, double lo, uint8_t *newfix, uint8_t *codes, int *counts, hipStream_t s);

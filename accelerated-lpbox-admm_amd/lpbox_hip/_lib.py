@@ -56,6 +56,8 @@ SYMBOLS = {
     "lpbox_policy_rescore_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
     "lpbox_set_active": (C.c_int, [C.c_void_p, C.c_void_p]),
     "lpbox_get_x_iters_device": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_long)]),
+    "lpbox_get_x_iters_rows_device": (C.c_long, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]),
+    "lpbox_iterate_l2f_scores": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p]),
     "lpbox_get_x_sol": (C.c_int, [C.c_void_p, C.c_int, _dp]),
     "lpbox_get_final_x_sol": (C.c_int, [C.c_void_p, C.c_int, _dp]),
     "lpbox_cal_obj": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double)]),

@@ -93,6 +93,56 @@ def run_l2f_batch(batch, score_fn_torch, ws=100, max_iter=10000, tokens=20, min_
                 infeasible=np.array([batch.check_infeasible_l2f(i) for i in range(B)]), windows=windows)
 
 
+def run_l2f_batch_device(batch, policy, ws=100, max_iter=10000, tokens=20, min_fix=10, C=0.9, timing=None):
+    """run_l2f_batch with nothing but return codes and fix counts coming to the host: per window the row table of the live variables
+    of all unfinished instances is built on the device (LpBatch.x_iters_rows_torch), the policy scores them there, and the next
+    window decides the fix from those scores in a kernel (LpBatch.solve_iter_l2f_scores).  policy: an object with
+    scores_from_xiters (lpbox_hip.policy.FusedEarlyFixPolicy; called with flat, row_off, ws // tokens) or a plain torch callable on
+    the float32 (rows, tokens, ws // tokens) tensor gathered through row_off.  `timing`, if a dict, receives seconds per phase.
+    Returns what run_l2f_batch returns plus, per instance, `fixed` (variables fixed) and `instance_windows` (windows it ran)."""
+    import time
+
+    from . import _lib
+    if _lib.load().lpbox_device_count() < 1:                      # before torch is asked for a device it does not have
+        err = _lib.LpboxError("run_l2f_batch_device: no HIP device available (there is no CPU fallback)")
+        err.code = _lib.E_NODEVICE
+        raise err
+    import torch
+    B = batch.B
+    done = np.zeros(B, bool)
+    fixed, inst_windows = np.zeros(B, np.int64), np.zeros(B, np.int64)
+    t = dict(solve=0.0, policy=0.0, host=0.0)
+    windows = 0
+    sig = None
+    batch.set_active(~done)
+    for w in range(int(max_iter / ws)):
+        t0 = time.perf_counter()
+        rets, fx = batch.solve_iter_l2f_scores(ws * w, ws * (w + 1), sig, C, min_fix)
+        windows += 1
+        inst_windows[~done] += 1
+        fixed += fx
+        done |= rets != 0
+        t1 = time.perf_counter()
+        t["solve"] += t1 - t0
+        if done.all():
+            break
+        batch.set_active(~done)
+        flat, row_off, _ = batch.x_iters_rows_torch(ws)
+        if hasattr(policy, "scores_from_xiters"):
+            sig = policy.scores_from_xiters(flat, row_off, ws // tokens)
+        else:
+            X = flat[row_off[:, None] + torch.arange(ws, device=flat.device)]
+            sig = policy(X.view(-1, tokens, ws // tokens).to(torch.float32))
+        sig = sig.reshape(-1).to(torch.float32)
+        torch.cuda.current_stream(flat.device).synchronize()      # (the window would wait for it anyway: counted as policy time)
+        t["policy"] += time.perf_counter() - t1
+    if timing is not None:
+        timing.update(t)
+    return dict(objective=np.array([-batch.cal_obj(i) for i in range(B)]),
+                infeasible=np.array([batch.check_infeasible_l2f(i) for i in range(B)]), windows=windows, fixed=fixed,
+                instance_windows=inst_windows)
+
+
 def sliding_windows(xiters, tokens=5, width=5):
     """SEG/trainer.py:721-725: token j of a variable = its iterates j .. j+width-1."""
     a = xiters.shape[0]

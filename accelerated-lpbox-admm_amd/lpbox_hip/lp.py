@@ -221,6 +221,49 @@ class LpBatch:
             __cuda_array_interface__ = {"shape": (self.B * stride.value,), "typestr": "<f8", "data": (ptr.value, False), "version": 2}
         return torch.as_tensor(_Dev(), device="cuda"), stride.value
 
+    def x_iters_rows_torch(self, ws):
+        """x_iters_torch plus the table a policy on the device reads it through: returns (flat, row_off, first_row).  flat is the
+        packed buffer of x_iters_torch(ws); row_off is an int64 CUDA tensor (adopted, no copy) with one entry per live variable of every
+        ACTIVE instance, stacked in instance order: the offset in flat of that variable's first iterate of the window; first_row is a
+        numpy array (B + 1): instance i owns rows first_row[i] .. first_row[i+1] - 1 (none while it is parked).  Valid until the next
+        solver call; solve_iter_l2f_scores takes one score per row."""
+        import torch
+        ws = _as_int(ws, "ws")
+        ptr = C.c_void_p()
+        first = np.zeros(self.B + 1, np.int32)
+        rows = check(self._L.lpbox_get_x_iters_rows_device(self._h, ws, C.byref(ptr), first.ctypes.data_as(C.c_void_p)),
+                     "lpbox_get_x_iters_rows_device")
+        flat, _ = self.x_iters_torch(ws)
+        self._table_rows = int(rows)
+        if rows == 0:
+            return flat, torch.zeros(0, dtype=torch.int64, device=flat.device), first
+
+        class _Dev:
+            __cuda_array_interface__ = {"shape": (int(rows),), "typestr": "<i8", "data": (ptr.value, False), "version": 2}
+        return flat, torch.as_tensor(_Dev(), device="cuda"), first
+
+    def solve_iter_l2f_scores(self, i, j, scores=None, C=0.9, min_fix=10):
+        """solve_iter_l2f with the fix decided on the device: deter_fix_2 with threshold C (score > C -> 1, < 1 - C -> 0) and the
+        `<= min_fix fixes -> none` guard, per instance.  scores: float32 CUDA tensor with one entry per row of the last
+        x_iters_rows_torch(), or None (fix nothing); it never comes to the host.  Returns (rets, fixed), int32 arrays."""
+        import ctypes
+        i, j = _as_int(i, "i"), _as_int(j, "j")
+        ptr = None
+        if scores is not None:
+            import torch
+            if not (isinstance(scores, torch.Tensor) and scores.is_cuda and scores.dtype == torch.float32):
+                raise ValueError("scores must be a float32 CUDA tensor")
+            scores = scores.contiguous().reshape(-1)
+            if scores.numel() != getattr(self, "_table_rows", -1):
+                raise ValueError("scores must hold one entry per row of the last x_iters_rows_torch()")
+            torch.cuda.current_stream(scores.device).synchronize()      # the batch runs on a stream of its own
+            ptr = ctypes.c_void_p(scores.data_ptr()) if scores.numel() else None
+        rets, fixed = np.zeros(self.B, np.int32), np.zeros(self.B, np.int32)
+        check(self._L.lpbox_iterate_l2f_scores(self._h, i, j, ptr, float(C), 1 - float(C), int(min_fix), rets.ctypes.data_as(ctypes.c_void_p),
+                                               fixed.ctypes.data_as(ctypes.c_void_p)), "lpbox_iterate_l2f_scores")
+        self._table_rows = -1
+        return rets, fixed
+
     def get_x_sol(self, idx=0):
         out = np.zeros(self.get_org_n(idx), np.float64)
         check(self._L.lpbox_get_x_sol(self._h, idx, out), "lpbox_get_x_sol")

@@ -175,6 +175,18 @@ int lpbox_set_active(lpbox_t *h, const int *active);
  * doubles and holds lpbox_get_x_iters(h, idx, ws, NULL) rows.  Lets a policy network read the iterates without a host
  * round trip (valid until the next solver call). */
 int lpbox_get_x_iters_device(lpbox_t *h, int ws, void **dev_ptr, long *stride_doubles);
+/* The live rows of the last l2f window of all ACTIVE instances, stacked in instance order, for a policy that reads x_iters on the
+ * device.  Packs as lpbox_get_x_iters_device(ws) does if that has not happened.  *row_off_dev: int64[rows], element offset of the
+ * row's first iterate in that packed buffer; first_row (may be NULL): B + 1 host ints, rows of instance i are
+ * first_row[i] .. first_row[i+1] - 1 (empty for a parked instance).  Returns rows (>= 0). */
+long lpbox_get_x_iters_rows_device(lpbox_t *h, int ws, void **row_off_dev, int *first_row);
+/* lpbox_iterate_l2f with the fix decided on the device.  scores_dev: float32, one per stacked row of the table above, or NULL = fix
+ * nothing.  Per instance deter_fix_2 with the trainer's guard (widened to double: s > hi -> 1, s < lo -> 0, NaN -> nothing; k fixes,
+ * k <= min_fix -> nothing fixed).  fixed[B] (may be NULL) = fixes applied.  rets / return value as lpbox_iterate_l2f.  The caller
+ * orders its own work on scores_dev before the call.  The table must have been built since the last window, for the active mask that
+ * is still in place (LPBOX_E_STATE otherwise; a lpbox_set_active call that repeats the current mask keeps it). */
+int lpbox_iterate_l2f_scores(lpbox_t *h, int iter_start, int iter_end, const float *scores_dev, double hi, double lo,
+                             int min_fix, int *rets, int *fixed);
 int lpbox_get_x_sol(lpbox_t *h, int idx, double *out);        /* LP pxd:17 (LPcpp:1648-1665): out[org_n] in {0,1} */
 int lpbox_get_final_x_sol(lpbox_t *h, int idx, double *out);  /* LP pxd:18 (LPcpp:1668-1685): raw live x, returns its length */
 int lpbox_cal_obj(lpbox_t *h, int idx, double *out);          /* LP pxd:12 cal_obj() (LPcpp:1630-1642)      */

@@ -95,3 +95,40 @@ hipError_t big_launch_post(const BigDev &d, int *parity, hipStream_t s);        
 hipError_t big_launch_z4(const BigDev &d, int init_only, int *parity, hipStream_t s); // Ex = q [, z4 update]
 hipError_t big_launch_resume(const BigDev &d, int reset_pcg_max, int *parity, hipStream_t s);
 hipError_t big_launch_rank_sum(const double *g, int W, long count, long stride, double *out, hipStream_t s);   // rank-ordered sum of W gathered contributions
+
+// ---- reference-order mode of this path (lpbox_big_set_order(LPBOX_ORDER_REFERENCE), one rank; lpbox_big_ref_kernels.hip) ----
+// Every reduction over the live variables follows Eigen's redux (oracle/lpbox_oracle.c redux_sum_eigen): the producers write their
+// per-variable terms into `stage` at the variable's LIVE RANK instead of summing them per workgroup, a walker kernel adds them up in
+// the four-chain order and leaves the totals in BigDev::red.  The descriptor travels in a kernel argument of its own: BigDev, and with
+// it every default-order kernel, is untouched.
+#define BIG_REF_MAXV 5     // values of one phase (post)
+#define BIG_REF_NSTAGE 13  // staging rows of n_loc doubles: A 1, B 3, C 1, D 2, E 5, X 1 (one set per phase, as BigDev::part)
+struct BigRef {
+    int valued;                           // any stored value of E differs from 1.0: the VALUED instantiations run
+    const double *vcsr, *vcsc;            // the stored values in the order of rcol / crow (valued only)
+    double *r4v;                          // rho4_E_transpose, one entry per stored entry in CSC order (valued only; unit: the scalar r4Et)
+    double *stage;                        // [BIG_REF_NSTAGE][n_loc]
+    int *rank;                            // live rank of every variable (-1: fixed), a device prefix sum at init and in every fix
+    int *frank;                           // rank among the variables fixed by the current call (-1: not one of them)
+    int *cnt;                             // [0] live variables, [1] variables fixed by the current call
+};
+__host__ __device__ constexpr int big_ref_stage_off(int phase) {
+    return phase == BIG_PH_A ? 0 : phase == BIG_PH_B ? 1 : phase == BIG_PH_C ? 4 : phase == BIG_PH_D ? 5 : phase == BIG_PH_E ? 7 : 12;
+}
+// mode 0: rank over live -> rank, cnt[0]; 1: over newfix -> frank, cnt[1]; 2: over live && !newfix -> rank, cnt[0] (the live set after the fix)
+hipError_t bigref_launch_rank(const BigDev &d, const BigRef &rf, int mode, hipStream_t s);
+// red[phase][0..nv) = redux over the first cnt[which] staged terms.  sidx >= 0: skipped when st[sidx] shows that the producer fell through
+// (halted chain; for the PCG phases C and D also a finished PCG) -- red[] keeps the totals a resumed PCG needs.
+hipError_t bigref_launch_walk(const BigDev &d, const BigRef &rf, int nv, int phase, int which, int sidx, hipStream_t s);
+hipError_t bigref_launch_init(const BigDev &d, const BigRef &rf, double c1, hipStream_t s);
+hipError_t bigref_launch_fix1(const BigDev &d, const BigRef &rf, hipStream_t s);
+hipError_t bigref_launch_fix2(const BigDev &d, const BigRef &rf, int *parity, hipStream_t s);
+hipError_t bigref_launch_fix3(const BigDev &d, const BigRef &rf, long n_live_new, double c1_new, int *parity, hipStream_t s);
+hipError_t bigref_launch_prep(const BigDev &d, const BigRef &rf, int do_prep, int *parity, hipStream_t s);
+hipError_t bigref_launch_y(const BigDev &d, const BigRef &rf, int *parity, hipStream_t s);
+hipError_t bigref_launch_rhs_cols(const BigDev &d, const BigRef &rf, int *parity, hipStream_t s);
+hipError_t bigref_launch_rows(const BigDev &d, const BigRef &rf, int mode, int *parity, hipStream_t s);
+hipError_t bigref_launch_resid(const BigDev &d, const BigRef &rf, int *parity, hipStream_t s);
+hipError_t bigref_launch_pcg_cols(const BigDev &d, const BigRef &rf, int *parity, hipStream_t s);
+hipError_t bigref_launch_pcg_upd(const BigDev &d, const BigRef &rf, int *parity, hipStream_t s);
+hipError_t bigref_launch_post(const BigDev &d, const BigRef &rf, int *parity, hipStream_t s);

@@ -101,6 +101,18 @@ struct lpbox_big {
     bool record = false, xi_plain = false;   // lpbox_big_set_record: the plain loop stages every iterate; the last staged window came from it
     Buf<BigState> st;
     BigState hst;
+    // reference-order mode (lpbox_big_set_order): one rank, one column slice, no folded reductions; see BigRef in lpbox_big.h
+    bool ref = false, valued = false;
+    std::vector<double> vals, vcsr_h;     // stored values of E in the order of crow / rcol (empty: a unit instance)
+    Buf<double> d_vcsc, d_vcsr, r4v, stage;
+    Buf<int> d_rank, d_frank, d_cnt;
+
+    BigRef rf() const {
+        BigRef r;
+        r.valued = valued ? 1 : 0; r.vcsr = d_vcsr.p; r.vcsc = d_vcsc.p; r.r4v = r4v.p; r.stage = stage.p;
+        r.rank = d_rank.p; r.frank = d_frank.p; r.cnt = d_cnt.p;
+        return r;
+    }
 
     BigDev dev() const {
         BigDev d;
@@ -176,6 +188,13 @@ int agree_ok(lpbox_big *h, bool ok_here) {
 }
 
 #define CHK(expr) do { int rc_ = (expr); if (rc_ < 0) return rc_; } while (0)
+// c1 = pow(n, 1/p), p = 2 (LPcpp:427,503) through libm's pow, as the reference and the oracle call it: with the literal exponent the
+// compiler turns the call into sqrt, and glibc's pow is not correctly rounded (n = 2921: one ulp apart).  Reference order only; the
+// default order keeps the expression it has always had.
+static double ref_c1(long n) {
+    volatile double e = 1.0 / 2;
+    return std::pow((double)n, e);
+}
 // the totals of a phase's workgroup partials for its consumers.  Folded route: the consumers add them up themselves; only W > 1 ranks
 // have something to do here -- ONE all-gather of the partials (nv * Gs doubles per rank), no reduction launch, no rank-sum launch.
 // Other route: the reduction launch leaves them in red[], all-reduced over the ranks in rank order.
@@ -191,10 +210,14 @@ int gather_partials(lpbox_big *h, const BigDev &d, int phase, int nv) {
     h->collectives++;
     return LPBOX_OK;
 }
-#define FIN(nv, phase) do { if (h->fold) { if (h->gpart.p) CHK(gather_partials(h, d, phase, nv)); } \
+// reference order: the walker in the place of the reduction launch (no folding, one rank); the launches of the chain go to their
+// reference-order counterparts (KL)
+#define KL(name, ...) (h->ref ? bigref_launch_##name(d, h->rf(), ##__VA_ARGS__) : big_launch_##name(d, ##__VA_ARGS__))
+#define WALK(nv, phase, which, sidx) do { HIPCHK(bigref_launch_walk(d, h->rf(), nv, phase, which, sidx, h->stream)); h->launches++; } while (0)
+#define FIN(nv, phase) do { if (h->ref) WALK(nv, phase, 0, h->parity); else if (h->fold) { if (h->gpart.p) CHK(gather_partials(h, d, phase, nv)); } \
                             else { HIPCHK(big_launch_fin(d, nv, phase, h->stream)); h->launches++; CHK(allreduce(h, d.red + (phase) * BIG_NPART, nv)); } } while (0)
 #define FINX(nv) do { HIPCHK(big_launch_fin(d, nv, BIG_PH_X, h->stream)); h->launches++; CHK(allreduce(h, d.red + BIG_PH_X * BIG_NPART, nv)); } while (0)
-#define ROWS(mode) do { HIPCHK(big_launch_rows(d, mode, &h->parity, h->stream)); h->launches++; CHK(allreduce(h, d.q, h->l)); } while (0)
+#define ROWS(mode) do { HIPCHK(KL(rows, mode, &h->parity, h->stream)); h->launches++; CHK(allreduce(h, d.q, h->l)); } while (0)
 
 // comm-lean PCG, W > 1: the q exchange of allreduce() with the scalars riding along -- the row blocks go to their owners (one grouped
 // send/recv), the owner adds its block in rank order and squares it (big_k_rank_sum_qq: q.q partials behind the p.p partials the row
@@ -243,16 +266,16 @@ int enqueue_pcg(lpbox_big *h, const BigDev &d, int pairs) {
     }
     for (int k = 0; k < pairs; k++) {
         ROWS(1);
-        HIPCHK(big_launch_pcg_cols(d, &h->parity, h->stream)); h->launches++;
+        HIPCHK(KL(pcg_cols, &h->parity, h->stream)); h->launches++;
         FIN(1, BIG_PH_C);
-        HIPCHK(big_launch_pcg_upd(d, &h->parity, h->stream)); h->launches++;
+        HIPCHK(KL(pcg_upd, &h->parity, h->stream)); h->launches++;
         FIN(2, BIG_PH_D);
     }
     return LPBOX_OK;
 }
 
 int enqueue_tail(lpbox_big *h, const BigDev &d) {
-    HIPCHK(big_launch_post(d, &h->parity, h->stream)); h->launches++;
+    HIPCHK(KL(post, &h->parity, h->stream)); h->launches++;
     FIN(5, BIG_PH_E);
     ROWS(0);
     HIPCHK(big_launch_z4(d, 0, &h->parity, h->stream)); h->launches++;
@@ -260,12 +283,12 @@ int enqueue_tail(lpbox_big *h, const BigDev &d) {
 }
 
 int enqueue_iteration(lpbox_big *h, const BigDev &d) {
-    HIPCHK(big_launch_prep(d, 1, &h->parity, h->stream)); h->launches++;
+    HIPCHK(KL(prep, 1, &h->parity, h->stream)); h->launches++;
     FIN(1, BIG_PH_A);
-    HIPCHK(big_launch_y(d, &h->parity, h->stream)); h->launches++;
-    HIPCHK(big_launch_rhs_cols(d, &h->parity, h->stream)); h->launches++;
+    HIPCHK(KL(y, &h->parity, h->stream)); h->launches++;
+    HIPCHK(KL(rhs_cols, &h->parity, h->stream)); h->launches++;
     ROWS(0);
-    HIPCHK(big_launch_resid(d, &h->parity, h->stream)); h->launches++;
+    HIPCHK(KL(resid, &h->parity, h->stream)); h->launches++;
     FIN(3, BIG_PH_B);
     CHK(enqueue_pcg(h, d, h->kmax));
     return enqueue_tail(h, d);
@@ -332,6 +355,8 @@ void lpbox_big_destroy(lpbox_big_t *h) {
     for (auto &kv : h->gexec) (void)hipGraphExecDestroy(kv.second);
     for (hipGraph_t g : h->graphs) (void)hipGraphDestroy(g);
     if (h->comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(h->comm);
+    for (Buf<double> *bp : {&h->d_vcsc, &h->d_vcsr, &h->r4v, &h->stage}) bp->release();
+    h->d_rank.release(); h->d_frank.release(); h->d_cnt.release();
     h->st.release(); h->live.release(); h->newfix.release(); h->d_live_idx.release(); h->zp.release(); h->fz.release();
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -362,6 +387,7 @@ int lpbox_big_set_pcg_mode(lpbox_big_t *h, int mode) {
     if (!h) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
     if (h->inited) return lpbox_fail(LPBOX_E_STATE, "set the PCG mode before lpbox_big_init");
     if (mode != LPBOX_PCG_REFERENCE && mode != LPBOX_PCG_COMM_LEAN) return lpbox_fail(LPBOX_E_BADARG, "unknown PCG mode %d", mode);
+    if (h->ref && mode == LPBOX_PCG_COMM_LEAN) return lpbox_fail(LPBOX_E_UNSUPPORTED, "the comm-lean PCG is not the reference's arithmetic: not available in the reference summation order");
     h->lean = mode == LPBOX_PCG_COMM_LEAN;
     return LPBOX_OK;
 }
@@ -370,6 +396,7 @@ int lpbox_big_set_allgather(lpbox_big_t *h, lpbox_allgather_fn fn, void *user) {
     if (!h) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
     // the exchange buffers are sized by lpbox_big_init from the transport that is set then (as for lpbox_big_rccl_init)
     if (h->inited) return lpbox_fail(LPBOX_E_STATE, "set the all-gather callback before lpbox_big_init");
+    if (h->ref && fn) return lpbox_fail(LPBOX_E_UNSUPPORTED, "the reference summation order runs on one rank without a transport");
     h->ag = fn; h->ag_user = user;
     return LPBOX_OK;
 }
@@ -387,6 +414,7 @@ int lpbox_big_rccl_unique_id(void *out128) {
 int lpbox_big_rccl_init(lpbox_big_t *h, const void *unique_id128) {
     if (!h || !unique_id128) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle / id");
     if (h->comm) return lpbox_fail(LPBOX_E_STATE, "communicator already created");
+    if (h->ref) return lpbox_fail(LPBOX_E_UNSUPPORTED, "the reference summation order runs on one rank without a transport");
     if (h->inited) return lpbox_fail(LPBOX_E_STATE, "the communicator must be created before solve_init");
     int rc = rccl_load();
     if (rc < 0) return rc;
@@ -398,8 +426,37 @@ int lpbox_big_rccl_init(lpbox_big_t *h, const void *unique_id128) {
     return LPBOX_OK;
 }
 
+// Opt-in: the reference's summation order on this path, one rank.  Before lpbox_big_set_problem.
+int lpbox_big_set_order(lpbox_big_t *h, int mode) {
+    if (!h) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
+    if (mode != LPBOX_ORDER_DEFAULT && mode != LPBOX_ORDER_REFERENCE) return lpbox_fail(LPBOX_E_BADARG, "unknown summation order %d", mode);
+    if (h->has_problem || h->uploaded || h->inited) return lpbox_fail(LPBOX_E_STATE, "set the summation order before lpbox_big_set_problem");
+    if (mode == LPBOX_ORDER_REFERENCE) {
+        if (h->world != 1) return lpbox_fail(LPBOX_E_UNSUPPORTED, "the reference summation order runs on one rank (world = %d)", h->world);
+        if (h->comm || h->ag) return lpbox_fail(LPBOX_E_UNSUPPORTED, "the reference summation order runs on one rank without a transport");
+        if (h->lean) return lpbox_fail(LPBOX_E_UNSUPPORTED, "the comm-lean PCG is not the reference's arithmetic: not available in the reference summation order");
+    }
+    h->ref = mode == LPBOX_ORDER_REFERENCE;
+    return LPBOX_OK;
+}
+
+static int big_set_problem(lpbox_big_t *h, long n_glob, int c0, int n_loc, int l, const int *colptr, const int *rowidx,
+                           const double *b, const double *f, const double *vals);
+
 int lpbox_big_set_problem(lpbox_big_t *h, long n_glob, int c0, int n_loc, int l, const int *colptr, const int *rowidx,
                           const double *b, const double *f) {
+    return big_set_problem(h, n_glob, c0, n_loc, l, colptr, rowidx, b, f, nullptr);
+}
+
+// lpbox_big_set_problem plus the stored values of E in the order of rowidx (NULL: ones).  Any finite value; an explicit zero stays a
+// stored entry; values that are all exactly 1.0 make a unit instance.  A default-order handle takes unit values only.
+int lpbox_big_set_problem_vals(lpbox_big_t *h, long n_glob, int c0, int n_loc, int l, const int *colptr, const int *rowidx,
+                               const double *b, const double *f, const double *vals) {
+    return big_set_problem(h, n_glob, c0, n_loc, l, colptr, rowidx, b, f, vals);
+}
+
+static int big_set_problem(lpbox_big_t *h, long n_glob, int c0, int n_loc, int l, const int *colptr, const int *rowidx,
+                           const double *b, const double *f, const double *vals) {
     if (!h) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
     if (h->uploaded) return lpbox_fail(LPBOX_E_STATE, "problem already uploaded");
     if (n_glob <= 0 || n_loc <= 0 || l <= 0 || c0 < 0 || (long)c0 + n_loc > n_glob || !colptr || !b || colptr[0] != 0)
@@ -413,6 +470,16 @@ int lpbox_big_set_problem(lpbox_big_t *h, long n_glob, int c0, int n_loc, int l,
             if (k > colptr[j] && rowidx[k] <= rowidx[k - 1]) return lpbox_fail(LPBOX_E_BADARG, "row indices must ascend inside a column");
         }
     }
+    bool valued = false;
+    if (vals) {
+        for (int k = 0; k < nnz; k++) {
+            if (!std::isfinite(vals[k])) return lpbox_fail(LPBOX_E_BADARG, "stored value %d of E is not finite", k);
+            if (vals[k] != 1.0) valued = true;
+        }
+        if (valued && !h->ref)
+            return lpbox_fail(LPBOX_E_UNSUPPORTED, "stored values of E other than 1 need the reference summation order: call lpbox_big_set_order(h, LPBOX_ORDER_REFERENCE) first");
+    }
+    h->valued = valued;
     h->n_glob = n_glob; h->c0 = c0; h->n_loc = n_loc; h->l = l; h->nnz = nnz;
     h->cptr.assign(colptr, colptr + n_loc + 1); h->crow.assign(rowidx, rowidx + nnz);
     // Row-side storage, slice-major (lpbox_big_kernels.hip row_sum_sliced): the columns are cut into P slices of SW columns so that
@@ -424,6 +491,7 @@ int lpbox_big_set_problem(lpbox_big_t *h, long n_glob, int c0, int n_loc, int l,
     int P = (int)std::min<long>(((long)n_loc + SW - 1) / SW, 64);
     if (P <= 1) { P = 1; SW = n_loc; } else SW = ((long)n_loc + P - 1) / P;
     if ((size_t)P * (size_t)l + 1 > (size_t)INT32_MAX) { P = 1; SW = n_loc; }
+    if (h->ref) { P = 1; SW = n_loc; }          // reference order: one lane sums the whole row; LPBOX_BIG_SLICE_KB is ignored
     h->P = P;
     h->rptr.assign((size_t)P * l + 1, 0);
     for (int j = 0; j < n_loc; j++) {
@@ -432,10 +500,16 @@ int lpbox_big_set_problem(lpbox_big_t *h, long n_glob, int c0, int n_loc, int l,
     }
     for (size_t i = 0; i < (size_t)P * l; i++) h->rptr[i + 1] += h->rptr[i];
     h->rcol.assign(nnz, 0);
+    h->vals.clear(); h->vcsr_h.clear();
+    if (valued) { h->vals.assign(vals, vals + nnz); h->vcsr_h.assign(nnz, 1.0); }
     std::vector<int> cur(h->rptr.begin(), h->rptr.end() - 1);
     for (int j = 0; j < n_loc; j++) {
         const size_t base = (size_t)(j / SW) * l;
-        for (int k = colptr[j]; k < colptr[j + 1]; k++) h->rcol[cur[base + rowidx[k]]++] = j;
+        for (int k = colptr[j]; k < colptr[j + 1]; k++) {
+            const int pos = cur[base + rowidx[k]]++;
+            h->rcol[pos] = j;
+            if (valued) h->vcsr_h[pos] = vals[k];
+        }
     }
     h->b.assign(b, b + n_loc);
     if (f) h->f.assign(f, f + l); else h->f.assign(l, 1.0);
@@ -446,6 +520,8 @@ int lpbox_big_set_problem(lpbox_big_t *h, long n_glob, int c0, int n_loc, int l,
 int lpbox_big_init(lpbox_big_t *h) {
     if (!h) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
     if (!h->has_problem) return lpbox_fail(LPBOX_E_STATE, "no problem set");
+    if (h->ref && (h->world != 1 || h->comm || h->ag || h->lean))
+        return lpbox_fail(LPBOX_E_UNSUPPORTED, "the reference summation order runs on one rank, without a transport and with the reference's PCG");
     CHK(use_device(h));
     if (!h->uploaded) {
         const int n = h->n_loc, l = h->l;
@@ -475,7 +551,7 @@ int lpbox_big_init(lpbox_big_t *h) {
         if (const char *e = getenv("LPBOX_BIG_EPT")) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4 || v == 8 || v == 16) h->EPT = std::max(v, h->EPT); }   // tuning
         h->G = groups(n, h->EPT);
         h->Gs = std::max(groups(nmax, h->EPT), 1);
-        h->fold = h->Gs <= fold_cap && h->world <= BIG_MAXW && getenv("LPBOX_BIG_NOFOLD") == nullptr;   // LPBOX_BIG_NOFOLD: keep the reduction launches (A/B)
+        h->fold = !h->ref && h->Gs <= fold_cap && h->world <= BIG_MAXW && getenv("LPBOX_BIG_NOFOLD") == nullptr;   // LPBOX_BIG_NOFOLD: keep the reduction launches (A/B)
         for (int r = 0; r < BIG_MAXW; r++) h->Gr[r] = r < h->world ? groups((long)nloc_all[r], h->EPT) : 0;
         h->EPTl = 2; h->Gl = (l + BIG_T * h->EPTl - 1) / (BIG_T * h->EPTl);
         h->Glr = (l + BIG_T - 1) / BIG_T;
@@ -507,6 +583,19 @@ int lpbox_big_init(lpbox_big_t *h) {
             HIPCHK(h->gpart.alloc((size_t)BIG_PH_COUNT * h->world * BIG_NPART * h->Gs));
             HIPCHK(hipMemset(h->gpart.p, 0, sizeof(double) * (size_t)BIG_PH_COUNT * h->world * BIG_NPART * h->Gs));
         }
+        if (h->ref) {
+            HIPCHK(h->stage.alloc((size_t)BIG_REF_NSTAGE * n)); HIPCHK(hipMemset(h->stage.p, 0, sizeof(double) * (size_t)BIG_REF_NSTAGE * n));
+            HIPCHK(h->d_rank.alloc(n)); HIPCHK(h->d_frank.alloc(n)); HIPCHK(h->d_cnt.alloc(2));
+            HIPCHK(hipMemset(h->d_rank.p, 0xff, sizeof(int) * (size_t)n)); HIPCHK(hipMemset(h->d_frank.p, 0xff, sizeof(int) * (size_t)n));
+            HIPCHK(hipMemset(h->d_cnt.p, 0, sizeof(int) * 2));
+            if (h->valued) {
+                const size_t z = (size_t)std::max(h->nnz, 1);
+                HIPCHK(h->d_vcsc.alloc(z)); HIPCHK(h->d_vcsr.alloc(z)); HIPCHK(h->r4v.alloc(z));
+                HIPCHK(hipMemset(h->r4v.p, 0, sizeof(double) * z));
+                HIPCHK(hipMemcpy(h->d_vcsc.p, h->vals.data(), sizeof(double) * (size_t)h->nnz, hipMemcpyHostToDevice));
+                HIPCHK(hipMemcpy(h->d_vcsr.p, h->vcsr_h.data(), sizeof(double) * (size_t)h->nnz, hipMemcpyHostToDevice));
+            }
+        }
         HIPCHK(hipMemcpy(h->d_rptr.p, h->rptr.data(), sizeof(int) * ((size_t)h->P * l + 1), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(h->d_rcol.p, h->rcol.data(), sizeof(int) * (size_t)h->nnz, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(h->d_cptr.p, h->cptr.data(), sizeof(int) * ((size_t)n + 1), hipMemcpyHostToDevice));
@@ -522,8 +611,14 @@ int lpbox_big_init(lpbox_big_t *h) {
     h->n_live_glob = h->n_glob; h->xi_valid = false;
     const BigDev d = h->dev();
     h->parity = 0;
+    if (h->ref) {
+        HIPCHK(bigref_launch_init(d, h->rf(), ref_c1(h->n_glob), h->stream));
+        HIPCHK(bigref_launch_rank(d, h->rf(), 0, h->stream));                       // every variable is live: rank = index
+        HIPCHK(bigref_launch_walk(d, h->rf(), 1, BIG_PH_X, 0, -1, h->stream));      // b.x0 (:727)
+    } else {
     HIPCHK(big_launch_init(d, std::pow((double)h->n_glob, 1.0 / 2), h->stream));   // pow(n, 1/p), p = 2 (LPcpp:427,503), n = ALL variables
     CHK(allreduce(h, d.red + BIG_PH_X * BIG_NPART, 1));
+    }
     HIPCHK(big_launch_init2(d, h->stream));
     ROWS(0);                                                                        // E * x0 for the first y3 (:720)
     HIPCHK(big_launch_z4(d, 1, &h->parity, h->stream));
@@ -562,7 +657,7 @@ static int run_window(lpbox_big *h, const BigDev &d, int iter_end) {
             }
         }
         for (int it = 0; it < batch; it++) CHK(enqueue_iteration(h, d));
-        HIPCHK(big_launch_prep(d, 0, &h->parity, h->stream)); h->launches++;          // finalise the last iteration of the batch
+        HIPCHK(KL(prep, 0, &h->parity, h->stream)); h->launches++;          // finalise the last iteration of the batch
     }
     HIPCHK(hipEventRecord(h->ev1, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -642,12 +737,22 @@ int lpbox_big_iterate_l2f(lpbox_big_t *h, int iter_start, int iter_end, const do
     if (num_global != 0) {
         const long n_live_new = h->n_live_glob - num_global;
         HIPCHK(hipMemcpyAsync(h->newfix.p, nf.data(), nf.size(), hipMemcpyHostToDevice, h->stream));
+        if (h->ref) {
+            HIPCHK(bigref_launch_rank(d, h->rf(), 1, h->stream)); h->launches++;    // rank among the newly fixed
+            HIPCHK(bigref_launch_fix1(d, h->rf(), h->stream)); h->launches++;
+            WALK(1, BIG_PH_X, 1, -1);                                               // fix_obj = b2.x2, redux over the newly fixed
+            ROWS(0);                                                                // q = E2 * x2
+            HIPCHK(bigref_launch_rank(d, h->rf(), 2, h->stream)); h->launches++;    // the live ranks after this fix
+            HIPCHK(bigref_launch_fix2(d, h->rf(), &h->parity, h->stream)); h->launches++;
+            WALK(1, BIG_PH_X, 0, -1);                                               // |x_live|^2
+        } else {
         HIPCHK(big_launch_fix1(d, h->stream)); h->launches++;
         FINX(1);                                                                    // fix_obj = b2.x2
         ROWS(0);                                                                    // q = E2 * x2
         HIPCHK(big_launch_fix2(d, &h->parity, h->stream)); h->launches++;
         FINX(1);                                                                    // |x_live|^2
-        HIPCHK(big_launch_fix3(d, n_live_new, std::pow((double)n_live_new, 1.0 / 2), &h->parity, h->stream)); h->launches++;
+        }
+        HIPCHK(KL(fix3, n_live_new, h->ref ? ref_c1(n_live_new) : std::pow((double)n_live_new, 1.0 / 2), &h->parity, h->stream)); h->launches++;
         if (n_live_new != 0) {
             ROWS(0);                                                                // E * x (live columns) for the first y3
             HIPCHK(big_launch_z4(d, 1, &h->parity, h->stream)); h->launches++;
@@ -725,6 +830,16 @@ int lpbox_big_get_vec(lpbox_big_t *h, const char *name, double *out, long cap) {
     else if (!strcmp(name, "pd")) src = h->pd.p; else if (!strcmp(name, "b")) src = h->db.p;
     else if (!strcmp(name, "f")) { src = h->df.p; len = h->l; }
     else if (!strcmp(name, "z4")) { src = h->z4.p; len = h->l; } else if (!strcmp(name, "Ex")) { src = h->Ex.p; len = h->l; }
+    else if (h->ref && (!strcmp(name, "r4v") || !strcmp(name, "vals"))) {     // per stored entry, in the order of rowidx
+        len = h->nnz;
+        if (cap < len) return lpbox_fail(LPBOX_E_BADARG, "buffer too small");
+        if (!h->valued) {                                                          // a unit instance carries the scalar / ones
+            for (long k = 0; k < len; k++) out[k] = name[0] == 'r' ? h->hst.r4Et : 1.0;
+            return (int)len;
+        }
+        if (len) HIPCHK(hipMemcpy(out, name[0] == 'r' ? h->r4v.p : h->d_vcsc.p, sizeof(double) * (size_t)len, hipMemcpyDeviceToHost));
+        return (int)len;
+    }
     else if (!strcmp(name, "live")) {
         if (cap < len) return lpbox_fail(LPBOX_E_BADARG, "buffer too small");
         std::vector<uint8_t> lv((size_t)len);
@@ -758,13 +873,15 @@ int lpbox_big_check_infeasible(lpbox_big_t *h, int which) {
     for (int ph = 0; ph < h->P; ph++)
         for (int i = 0; i < l; i++)
             for (int k = h->rptr[(size_t)ph * l + i]; k < h->rptr[(size_t)ph * l + i + 1]; k++)
-                if (live[h->rcol[k]]) s[i] += 1.0 * v[h->rcol[k]];
+                if (live[h->rcol[k]]) s[i] += (h->valued ? h->vcsr_h[k] : 1.0) * (1.0 * v[h->rcol[k]]);
     int inf = 0;
     for (int i = 0; i < l; i++) if (!(s[i] <= 1.0)) inf++;          // the reference compares with 1.0, not with f
     return inf;
 }
 
 int lpbox_big_get_scalar(lpbox_big_t *h, const char *name, double *out) {
+    if (h && out && name && !strcmp(name, "order")) { *out = h->ref ? (double)LPBOX_ORDER_REFERENCE : (double)LPBOX_ORDER_DEFAULT; return LPBOX_OK; }
+    if (h && out && name && !strcmp(name, "valued")) { *out = h->valued ? 1.0 : 0.0; return LPBOX_OK; }
     if (!h || !h->inited || !out || !name) return lpbox_fail(LPBOX_E_STATE, "not initialised");
     const BigState &s = h->hst;
     struct { const char *n; double v; } tab[] = {

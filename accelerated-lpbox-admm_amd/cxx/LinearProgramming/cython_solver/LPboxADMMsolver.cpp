@@ -40,6 +40,7 @@ struct LPboxADMMsolver::State {
     std::vector<double> xiters, xsol, xfinal, x_prev;
     bool does_log = false;
     int order = LPBOX_ORDER_DEFAULT;  // summation order of the on-chip kernels (set_order); kept across new problems
+    bool large_ok = false;            // reference order: hand an instance beyond the on-chip kernel to the large-instance path (set_order)
     ~State() { if (big) lpbox_big_destroy(big); if (h) lpbox_destroy(h); }
     std::string data_root() const {
         if (!root.empty()) return root;
@@ -98,11 +99,13 @@ inline void LPboxADMMsolver::set_consistency(int c) { s_->consistency = c; }
 inline void LPboxADMMsolver::set_data_root(const std::string &root) { s_->root = root; }
 inline bool LPboxADMMsolver::on_large_path() const { return s_->big != nullptr; }
 // the opt-in reference summation order; an instance beyond the on-chip kernel then throws at ADMM_lp_iters_init
-// instead of moving to the large-instance path, which sums in an order of its own
-inline void LPboxADMMsolver::set_order(int mode) {
+// unless large_ok is set: then it moves to the large-instance path in the same order, stored values included
+inline void LPboxADMMsolver::set_order(int mode) { set_order(mode, false); }
+inline void LPboxADMMsolver::set_order(int mode, bool large_ok) {
     if (!s_->h) s_->fresh();
     lpbox_ok(lpbox_set_order(s_->h, mode), "lpbox_set_order");
     s_->order = mode;
+    s_->large_ok = large_ok;
 }
 inline int LPboxADMMsolver::get_org_n() { return s_->org_n; }
 
@@ -126,10 +129,11 @@ inline int LPboxADMMsolver::ADMM_lp_iters_init() {
         lpbox_ok(lpbox_get_problem_lp(s.h, 0, &n, &l, &nnz, nullptr, nullptr, nullptr, nullptr), "lpbox_get_problem_lp");
         s.org_n = n; s.l = l;
         bool fits = std::max(n, l) <= LPBOX_ONCHIP_MAX;
-        if (fits || s.order == LPBOX_ORDER_REFERENCE) {
+        const bool ref = s.order == LPBOX_ORDER_REFERENCE, refuse = ref && !s.large_ok;
+        if (fits || refuse) {
             const int rc = lpbox_init(s.h);
             if (rc >= 0) return rc;
-            if (rc != LPBOX_E_TOOLARGE || s.order == LPBOX_ORDER_REFERENCE) lpbox_throw("lpbox_init");
+            if (rc != LPBOX_E_TOOLARGE || refuse) lpbox_throw("lpbox_init");
         }
         // does not fit one CU: the same algorithm on the large-instance path, one rank
         std::vector<int> colptr((size_t)n + 1), rowidx((size_t)std::max(nnz, 1));
@@ -137,6 +141,14 @@ inline int LPboxADMMsolver::ADMM_lp_iters_init() {
         lpbox_ok(lpbox_get_problem_lp(s.h, 0, nullptr, nullptr, nullptr, colptr.data(), rowidx.data(), b.data(), f.data()), "lpbox_get_problem_lp");
         s.big = lpbox_big_create(0, 1, 0);
         if (!s.big) lpbox_throw("lpbox_big_create");
+        if (ref && s.does_log)
+            throw std::runtime_error("ADMM_lp_iters_init failed: the iteration log is not available on the large-instance path in the reference summation order");
+        if (ref) {
+            std::vector<double> vals((size_t)std::max(nnz, 1), 1.0);
+            lpbox_ok(lpbox_get_problem_lp_vals(s.h, 0, vals.data()), "lpbox_get_problem_lp_vals");
+            lpbox_ok(lpbox_big_set_order(s.big, LPBOX_ORDER_REFERENCE), "lpbox_big_set_order");
+            lpbox_ok(lpbox_big_set_problem_vals(s.big, n, 0, n, l, colptr.data(), rowidx.data(), b.data(), f.data(), vals.data()), "lpbox_big_set_problem_vals");
+        } else
         lpbox_ok(lpbox_big_set_problem(s.big, n, 0, n, l, colptr.data(), rowidx.data(), b.data(), f.data()), "lpbox_big_set_problem");
         lpbox_destroy(s.h); s.h = nullptr;
     }

@@ -52,7 +52,12 @@ public:
     bool on_large_path() const;
     long long outer_iterations();                             // lpbox_get_counters
     int stop_reason(int *plain_iter_plus1 = nullptr);         // lpbox_get_stop: 0 none, 1 y1_y2, 2 obj_std, 3 PCG alpha < 0, 4 all fixed
-    void set_order(int mode);                                 // lpbox_set_order: LPBOX_ORDER_DEFAULT / LPBOX_ORDER_REFERENCE, before ADMM_lp_iters_init
+    // lpbox_set_order: LPBOX_ORDER_DEFAULT / LPBOX_ORDER_REFERENCE, before ADMM_lp_iters_init.  large_ok: in the reference order an instance
+    // beyond the on-chip kernel goes to the large-instance path in that order (lpbox_big_set_order) instead of being refused
+    // (an overload rather than a defaulted argument: the one-argument declaration stays as callers and tests/test_lp_ref_order_api.py
+    // know it, character for character; set_order(mode) is set_order(mode, false))
+    void set_order(int mode);
+    void set_order(int mode, bool large_ok);
 
 private:
     struct State;

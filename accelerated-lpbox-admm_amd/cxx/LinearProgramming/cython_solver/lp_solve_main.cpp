@@ -3,7 +3,8 @@
 // convergence, infeasible-constraint count, wall-clock).  Adds a machine-readable RESULT line for the tests.
 //   usage: lp_solve <i> <k> <j> [max_iters=20000] [window=0] [print_info=0] [does_log=0] [order=0]
 // order = 1 chooses the reference summation order before the file is read, the order that accepts instance files whose stored values
-// are not all 1.
+// are not all 1; order = 2 chooses it with the large-instance opt-in (set_order(LPBOX_ORDER_REFERENCE, true)): an instance beyond the
+// on-chip kernel is then solved on the large-instance path in that order instead of being refused.
 // window > 0 runs the early-fixing entry point in windows of that many iterations without fixing anything (exercises
 // ADMM_lp_iters_l2f / get_x_iters_d from C++); window < 0 runs the rule-based early fixing ADMM_lp_iters_fix over [0, max_iters).
 #include <chrono>
@@ -23,7 +24,8 @@ int main(int argc, char **argv) {
         const auto t0 = std::chrono::steady_clock::now();
         LPboxADMMsolver solver(print_info);
         solver.set_does_log(does_log);
-        if (order) solver.set_order(order);
+        if (order == 2) solver.set_order(LPBOX_ORDER_REFERENCE, true);
+        else if (order) solver.set_order(order);
         solver.readFile(i, k, j);
         solver.ADMM_lp_iters_init();
         int ret = 0;

@@ -105,6 +105,8 @@ SYMBOLS = {
     "lpbox_big_rccl_init": (C.c_int, [C.c_void_p, C.c_void_p]),
     "lpbox_big_set_problem": (C.c_int, [C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_int, _ip, _ip, _dp, C.c_void_p]),
     "lpbox_big_set_pcg_mode": (C.c_int, [C.c_void_p, C.c_int]),
+    "lpbox_big_set_order": (C.c_int, [C.c_void_p, C.c_int]),
+    "lpbox_big_set_problem_vals": (C.c_int, [C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_int, _ip, _ip, _dp, C.c_void_p, C.c_void_p]),
     "lpbox_big_init": (C.c_int, [C.c_void_p]),
     "lpbox_big_iterate": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "lpbox_big_set_record": (C.c_int, [C.c_void_p, C.c_int]),
@@ -184,6 +186,7 @@ class LpboxError(RuntimeError):
 
 E_TOOLARGE = -9          # include/lpbox_hip.h: LPBOX_E_TOOLARGE
 E_STATE = -3             # LPBOX_E_STATE
+E_UNSUPPORTED = -7       # LPBOX_E_UNSUPPORTED
 E_NODEVICE = -6          # LPBOX_E_NODEVICE
 
 

@@ -32,8 +32,14 @@ def _dev_tensor(ptr, count):
 
 
 class BigLp:
-    def __init__(self, problem, rank=0, world=1, device=0, use_torch_stream=None, transport=None, pcg_mode="reference"):
-        """problem: dict(n, l, colptr, rowidx, b[, f]) of the WHOLE instance (CSC, 0/1 pattern, b already negated)."""
+    def __init__(self, problem, rank=0, world=1, device=0, use_torch_stream=None, transport=None, pcg_mode="reference", order="default"):
+        """problem: dict(n, l, colptr, rowidx, b[, f][, vals]) of the WHOLE instance (CSC, b already negated).
+
+        order="reference": the reference's summation order (lpbox_big_set_order; one rank, no transport, the reference's PCG), bit-exact
+        against the oracle in ORDER_EIGEN; only then may problem["vals"] (the stored values of E in the order of rowidx) differ from 1."""
+        if order not in ("default", "reference"):
+            raise ValueError("order must be 'default' or 'reference'")
+        self.order = order
         self._L = _lib.load()
         self.rank, self.world = int(rank), int(world)
         n, l = int(problem["n"]), int(problem["l"])
@@ -79,7 +85,16 @@ class BigLp:
         if f is not None:
             f = np.ascontiguousarray(f, np.float64)
             fp = f.ctypes.data_as(C.c_void_p)
-        check(self._L.lpbox_big_set_problem(self._h, n, self.c0, self.c1 - self.c0, l, colptr, rowidx, b, fp), "lpbox_big_set_problem")
+        if order == "reference":                             # after the transport: the library refuses the combination, either call order
+            check(self._L.lpbox_big_set_order(self._h, 1), "lpbox_big_set_order")
+        vals = problem.get("vals")
+        if vals is None:
+            check(self._L.lpbox_big_set_problem(self._h, n, self.c0, self.c1 - self.c0, l, colptr, rowidx, b, fp), "lpbox_big_set_problem")
+        else:
+            vals = np.ascontiguousarray(np.asarray(vals, np.float64)[lo:hi])
+            check(self._L.lpbox_big_set_problem_vals(self._h, n, self.c0, self.c1 - self.c0, l, colptr, rowidx, b, fp,
+                                                     vals.ctypes.data_as(C.c_void_p)), "lpbox_big_set_problem_vals")
+        self._nnz = int(colptr[-1])
         if pcg_mode not in ("reference", "lean"):
             raise ValueError("pcg_mode must be 'reference' or 'lean'")
         if pcg_mode == "lean":       # opt-in comm-lean PCG: not the reference's arithmetic (lpbox_big_set_pcg_mode in include/lpbox_hip.h)
@@ -132,7 +147,7 @@ class BigLp:
         return out
 
     def vec(self, name):
-        out = np.zeros(max(self.c1 - self.c0, self.l))
+        out = np.zeros(max(self.c1 - self.c0, self.l, self._nnz if name in ("r4v", "vals") else 1))
         k = check(self._L.lpbox_big_get_vec(self._h, name.encode(), out, len(out)), "lpbox_big_get_vec")
         return out[:k].copy()
 

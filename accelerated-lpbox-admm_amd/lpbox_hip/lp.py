@@ -13,7 +13,7 @@ import time
 import numpy as np
 
 from . import _lib, files
-from ._lib import E_TOOLARGE, LpboxError, check  # noqa: F401
+from ._lib import E_TOOLARGE, E_UNSUPPORTED, LpboxError, check  # noqa: F401
 
 STOP_NAMES = {0: None, 1: "y1_y2", 2: "obj_std", 3: "pcg_alpha_negative", 4: "all_fixed"}
 
@@ -374,9 +374,9 @@ class _LargeInstance:
     B = 1
     can_record = True        # the plain loop's per-iteration dump (print_info 2/3): lpbox_big_set_record stages the iterates on the device
 
-    def __init__(self, problem, device=None):
+    def __init__(self, problem, device=None, order="default"):
         from .big import BigLp
-        self._g = BigLp(problem, device=0 if device is None else int(device))
+        self._g = BigLp(problem, device=0 if device is None else int(device), order=order)
         self._org_n = int(problem["n"])
         self._l = int(problem["l"])
 
@@ -493,9 +493,14 @@ class PyLPboxADMMsolver:
     order = "default"
 
     # not in the pyx: the opt-in reference summation order (LpBatch.set_order), chosen before solve_init
-    def set_order(self, mode="default"):
+    # large_ok=True: an instance beyond the on-chip limit (or one that overflows the CU's LDS) goes to the large-instance path in the
+    # same order, stored values included; the default keeps the refusal (LPBOX_E_TOOLARGE)
+    large_ok = False
+
+    def set_order(self, mode="default", large_ok=False):
         self._small().set_order(mode)
         self.order = mode
+        self.large_ok = bool(large_ok)
 
     # LP pyx:16-17
     def read_File(self, i, k, j):
@@ -516,9 +521,10 @@ class PyLPboxADMMsolver:
         if isinstance(self._b, LpBatch):
             P = self._b.get_problem(0)
             fits = max(P["n"], P["l"]) <= ONCHIP_MAX
-            if self.order == "reference":                  # the large-instance path sums in its own order: refuse rather than switch
+            if self.order == "reference" and not self.large_ok:   # the large-instance path is an opt-in in this order: refuse rather than switch
                 if not fits:
-                    err = LpboxError("reference summation order: max(n, l) = %d exceeds the on-chip kernel's %d" % (max(P["n"], P["l"]), ONCHIP_MAX))
+                    err = LpboxError("reference summation order: max(n, l) = %d exceeds the on-chip kernel's %d (set_order('reference', large_ok=True) "
+                                     "hands such an instance to the large-instance path)" % (max(P["n"], P["l"]), ONCHIP_MAX))
                     err.code = E_TOOLARGE
                     raise err
                 return self._b.solve_init()
@@ -528,8 +534,12 @@ class PyLPboxADMMsolver:
                 except LpboxError as e:                    # fits the register slots but not the CU's 160 KiB of LDS (very dense E)
                     if e.code != E_TOOLARGE:
                         raise
+            if self.order == "reference" and self.write_log:      # (either way to the large path: beyond the slots, or beyond a CU's LDS)
+                err = LpboxError("the iteration log is not available on the large-instance path in the reference summation order")
+                err.code = E_UNSUPPORTED
+                raise err
             small = self._b                                # does not fit one CU: same algorithm on the multi-kernel path
-            self._b = _LargeInstance(P)
+            self._b = _LargeInstance(P, order=self.order)
             small.close()
         return self._b.solve_init()
 

@@ -332,6 +332,22 @@ int lpbox_big_rccl_unique_id(void *out128);                    /* ncclGetUniqueI
 int lpbox_big_rccl_init(lpbox_big_t *h, const void *unique_id128);   /* ncclCommInitRank(world, id, rank) on the handle's device */
 int lpbox_big_set_problem(lpbox_big_t *h, long n_glob, int c0, int n_loc, int l, const int *colptr, const int *rowidx,
                           const double *b, const double *f);
+/* OPT-IN: the reference's summation order on this path (lpbox_set_order's LPBOX_ORDER_REFERENCE beyond the on-chip limit; DESIGN.md
+ * section 21).  Every dot product / norm over the live variables follows Eigen's redux over the live variables in ascending original
+ * index, the fix objective the same redux over the variables fixed by the call; rows and columns of E are summed by one lane in
+ * ascending order (one column slice: LPBOX_BIG_SLICE_KB is ignored).  Bit-exact against oracle/lpbox_oracle.c in LPO_ORDER_EIGEN; sqrt
+ * where the reference calls pow(v, 1/2), as on chip.  Call it before lpbox_big_set_problem (LPBOX_E_STATE later).  One rank only:
+ * world != 1, a transport (lpbox_big_set_allgather, lpbox_big_rccl_init) or the comm-lean PCG give LPBOX_E_UNSUPPORTED, whichever of
+ * the two calls comes first.  lpbox_big_get_scalar(h, "order") reports the mode and "valued" whether the problem stores a value
+ * other than 1.0 (both also before lpbox_big_init). */
+int lpbox_big_set_order(lpbox_big_t *h, int mode);
+/* lpbox_big_set_problem plus the stored values of E in the order of rowidx (NULL = ones).  Reference order: any finite value (an
+ * explicit zero stays a stored entry; a non-finite value is LPBOX_E_BADARG); values that are all exactly 1.0 make a unit instance.
+ * Default order: any value other than 1.0 is LPBOX_E_UNSUPPORTED (the message names lpbox_big_set_order).  lpbox_big_get_vec then
+ * also serves "vals" and "r4v" (rho4_E_transpose per stored entry), both in the order of rowidx; lpbox_big_check_infeasible
+ * multiplies by the stored value. */
+int lpbox_big_set_problem_vals(lpbox_big_t *h, long n_glob, int c0, int n_loc, int l, const int *colptr, const int *rowidx,
+                               const double *b, const double *f, const double *vals);
 /* Opt-in, NOT the reference's arithmetic and outside the parity claim (like lpbox_set_x_update): the PCG's step length from
  * p.Mp = dI (p.p) + r4Et (q.q), q = E p, instead of the dot product p.(M p) of LPcpp:300 -- the p.p partials ride with the q exchange, the column
  * product and the vector updates become one kernel: 3 instead of 4 RCCL operations and 2 instead of 3 launches per PCG iteration.  Call before

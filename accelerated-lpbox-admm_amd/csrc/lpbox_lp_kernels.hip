@@ -843,12 +843,24 @@ __global__ void __launch_bounds__(T) lp_window_kernel(LpBatchDev bd, int iter_st
                 expr_ready = 1;
             }
             if (it != 0 && rhoUpdated) {
+                double c_before = 0.0;
+                if constexpr (DIRECT) c_before = dI / r4Et;
                 const double inc = rcr * (prev_rho1 + prev_rho2);
                 const double inc4 = rcr * prev_rho4;
                 dI += inc;
 #pragma unroll
                 for (int s = 0; s < EPT; s++) { double v = pd.get(s); v += inc; v += inc4 * Esq(s); pd.set(s, v); }
                 r4Et = learning_fact * r4Et;                          // rho4_E_transpose *= learning_fact (:864)
+                if constexpr (DIRECT) {
+                    // H and W hold for c = dI / r4Et.  The schedule scales both by learning_fact, so c moves by rounding only -- except
+                    // after a fix made while a rho update was pending (the double count): from then on dI carries an offset that
+                    // is not scaled, c changes with every update (1e-4 relative at the first) and the saved inverse would solve another
+                    // system.  Rebuilt when c moved by more than 1e-9 relative (uniform: every thread holds the same scalars).  The plain
+                    // schedule moves c by rounding only, 9 orders below that, over the 800 updates of a 20 000-iteration run
+                    // (tests/test_direct_x_update.py::test_plain_schedule_keeps_c_far_below_the_rebuild_threshold).
+                    const double c_after = dI / r4Et;
+                    if (fabs(c_after - c_before) > 1e-9 * c_before) h_valid = 0;
+                }
             }
             const double r4 = r4Et;
 #ifdef LPBOX_KO_NOMUL
@@ -891,7 +903,8 @@ __global__ void __launch_bounds__(T) lp_window_kernel(LpBatchDev bd, int iter_st
                 // host) and G rows (the rest, dense index gdir).  a I + r E_D^T E_D is block diagonal with blocks a I + r 1 1^T: its
                 // inverse is Q / a, Q v = v - E_D^T W E_D v, W = diag(1 / (c + m_i)), c = a / r.  Woodbury over the G rows:
                 //     x = Q (rhs - E_G^T H E_G Q rhs) / a,   H = (c I + E_G Q E_G^T)^-1  (|G| x |G|, in LDS).
-                // c is constant while rho1, rho2, rho4 are scaled together (LPcpp:951-970): H and W are built once per instance and fix.
+                // c is constant while rho1, rho2, rho4 are scaled together (LPcpp:951-970): H and W are built once per instance and fix,
+                // and again at a rho update that moves c (after the double count of a fix with a pending update, see the refresh above).
                 const int nG = bd.dng[inst], HLD = bd.HLD;
                 // Q v for this thread's variable: sigma = E v by rows, D rows publish w * sigma (G rows 0), the column sum picks it up
                 auto apply_Q = [&](double vin) {

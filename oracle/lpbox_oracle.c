@@ -144,6 +144,7 @@ struct lpo {
 
     /* LPh:199-262 */
     csc_t E, orgE, Et, r4Et;       /* *E_ptr, *org_E_ptr, E_transpose, rho4_E_transpose */
+    double r4s;                    /* the scalar of rho4_E_transpose as the kernels carry it: rho4 at update_expression, times learning_fact per update */
     double *b, *f;                 /* *b_ptr, *f_ptr (current problem) */
     int n, l, org_n;
     double *x, *y1, *y2, *z1, *z2, *y3, *z4;
@@ -537,6 +538,7 @@ static void update_expression(lpo_t *o) {
     csc_transpose(&o->Et, &o->E);                          /* :2292 */
     csc_copy(&o->r4Et, &o->Et);                            /* :2293 rho4_E_transpose = rho4 * E_transpose */
     for (int k = 0; k < o->r4Et.nnz; k++) o->r4Et.val[k] = o->rho4 * o->Et.val[k];
+    o->r4s = o->rho4;
     for (int j = 0; j < n; j++) {                          /* :2336-2343 zero triplets, diagonal += rho1+rho2 */
         double d = 0.0;
         d += o->rho1 + o->rho2;
@@ -651,9 +653,11 @@ static int conjugate_gradient(lpo_t *o, const double *rhs, double *x, int *iters
 /*   the Woodbury identity over the G rows then gives                                           */
 /*       x = Q (rhs - E_G^T H E_G Q rhs) / a,      H = (c I + E_G Q E_G^T)^-1   (|G| x |G|).     */
 /* c is constant while rho1, rho2, rho4 are scaled together (LPcpp:951-970), so H and W are     */
-/* built once, at the first x-update after init or after a fix, H by in-place Gauss-Jordan      */
-/* without pivoting (the matrix is SPD).  This restatement follows the kernel's operation order */
-/* so that kernel and oracle agree bit for bit; the reference has nothing to compare it with.   */
+/* built at the first x-update after init or after a fix -- and again at a rho update that      */
+/* moves c (only after the double count of a fix with a pending update, see admm_iteration) --, */
+/* H by in-place Gauss-Jordan without pivoting (the matrix is SPD).  This restatement follows   */
+/* the kernel's operation order so that kernel and oracle agree bit for bit; the reference has  */
+/* nothing to compare it with.                                                                  */
 /* ------------------------------------------------------------------------------------------ */
 static void direct_Q(lpo_t *o, const double *v, double *out) {       /* out = Q v (vectors over the live variables) */
     const int l = o->l, n = o->n;
@@ -683,8 +687,7 @@ static void direct_build(lpo_t *o) {
     o->dgrow = (int *)realloc(o->dgrow, sizeof(int) * (size_t)(nG + 1));
     for (int i = 0; i < l; i++) if (o->dir_g[i] >= 0) o->dgrow[o->dir_g[i]] = i;
     double *H = o->H, *wv = o->dq, *qw = o->dq + n;
-    const double r4 = o->r4Et.nnz > 0 ? o->r4Et.val[0] / o->Et.val[0] : o->rho4;
-    const double c = o->Dd[0] / r4;
+    const double c = o->Dd[0] / o->r4s;                              /* the kernel's dI / r4Et */
     for (int j = 0; j < n; j++) wv[j] = 1.0;
     spmv_E(o, wv, o->dsig);                                          /* m_i: live variables of row i */
     for (int i = 0; i < l; i++) o->dw[i] = 1.0 / (c + o->dsig[i]);
@@ -872,12 +875,24 @@ static int admm_iteration(lpo_t *o, int iter, int iter_start, int l2f, int *ret,
     if (iter == 0) update_expression(o);                      /* :831-842 / :1390-1391 */
 
     if (iter != 0 && o->rhoUpdated) {                         /* :851-866 / :1393-1406 */
+        const double c_before = (o->x_update == 1 && n > 0) ? o->Dd[0] / o->r4s : 0.0;
         double inc = o->rho_change_ratio * (o->prev_rho1 + o->prev_rho2);
         for (int j = 0; j < n; j++) o->Dd[j] += inc;
         for (int j = 0; j < n; j++) o->pd[j] += inc;
         double inc4 = o->rho_change_ratio * o->prev_rho4;
         for (int j = 0; j < n; j++) o->pd[j] += inc4 * o->Esq[j];
         for (int k = 0; k < o->r4Et.nnz; k++) o->r4Et.val[k] = o->learning_fact * o->r4Et.val[k];
+        o->r4s = o->learning_fact * o->r4s;
+        if (o->x_update == 1 && n > 0) {
+            /* direct mode: H and W hold for c = dI / r4Et.  The schedule scales both by learning_fact, so c moves by rounding only --
+             * except after a fix made while a rho update was pending (the double count): from then on dI carries an offset
+             * that is not scaled, c changes with every update (1e-4 relative at the first), and the saved inverse would solve another
+             * system.  Rebuilt when c moved by more than 1e-9 relative; the same rule and the same scalars as the kernel.  (The plain
+             * schedule moves c by at most 2.3e-16 relative per update over the 800 updates of a 20 000-iteration run:
+             * tests/test_direct_x_update.py::test_plain_schedule_keeps_c_far_below_the_rebuild_threshold.) */
+            const double c_after = o->Dd[0] / o->r4s;
+            if (fabs(c_after - c_before) > 1e-9 * c_before) o->H_valid = 0;
+        }
     }
 
     /* rhs  :872-878 / :1413-1422 */

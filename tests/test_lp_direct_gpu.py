@@ -61,7 +61,9 @@ def test_plain_windows_and_full_solve_bit_exact_vs_mirror():
 
 def test_l2f_windows_with_fixes_rebuild_the_inverse():
     """The early-fixing loop (LP/trainer.py:216-252 shape) on the direct mode: every fix removes columns of E, the kernel rebuilds its
-    inverse inside the next window and stays bit-identical to the mirror; windows without a fix reload the saved inverse."""
+    inverse inside the next window and stays bit-identical to the mirror; windows without a fix reload the saved inverse.  The fix at
+    iteration 100 meets a pending rho update (the double count): from there c = dI / r4Et moves at every rho update, and the
+    update at iteration 125, in the middle of a window, makes kernel and mirror rebuild the inverse."""
     insts = lp_instances("lp_100_500_seed0.npz")[4:7]
     b, os_ = _pair(insts)
     B = len(insts)

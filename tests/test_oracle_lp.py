@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+import lp_steplock as S
 from helpers import GOLDEN, lp_instances, make_oracle, scripted_fix_vec
 from oracle import oracle as O
 from oracle.lpbox_numpy import NumpyLpBox
@@ -136,9 +137,6 @@ def test_early_fix_bookkeeping_c_vs_numpy():
     vec, num = np.zeros(I["n"]), 0
     for w in range(12):
         rc = c.solve_iter_l2f(w * 100, (w + 1) * 100, vec, num)
-        if w >= 1:
-            # feed numpy the C oracle's state so that chaos cannot separate them: compare only one window after the fix
-            pass
         xit = c.get_x_iters_2d(100)
         vec, num = scripted_fix_vec(xit)
         if num > 10:
@@ -165,6 +163,22 @@ def test_early_fix_bookkeeping_c_vs_numpy():
     fixed = np.setdiff1d(np.arange(I["n"]), p.left_idx)
     xs = c2.get_x_sol().ravel()
     assert set(np.unique(xs[fixed])) <= {0.0, 1.0}
+    # feed numpy the C oracle's state so that chaos cannot separate them: the same script step-locked
+    case = steplocked_across_fix(I, fix_it=(w + 1) * 100, vec=vec, num=num)
+    assert case.checked == 21 and case.fixed == num and np.array_equal(np.sort(case.members[0].left_idx), p.left_idx)
+
+
+def steplocked_across_fix(I, fix_it, vec, num, before=20):
+    """The oracle driven one iteration at a time up to fix_it, the fix (vec, num) applied there and one iteration run, with the
+    restatement step-locked to it (tests/lp_steplock.py).  The last `before` iterations ahead of the fix and the one after it are held
+    to the restatement's own rounding spread: the shrunken problem, the pending rho update on top of update_expression's fresh values
+    and the iterates after the fix.  (The earlier iterations only carry the restatement's own rho schedule and objective history there;
+    tests/test_lp_steplock.py compares them.)"""
+    o = make_oracle(I)
+    case = S.Case(I, S.OracleSubject(o), "bookkeeping", check_from=fix_it - before)
+    S.run_cases(S.OracleGroup([o]), [case], S.l2f_steps(0, fix_it) + S.l2f_steps(fix_it, fix_it + 1, (vec, num)))
+    S.assert_clean([case])
+    return case
 
 
 def test_all_fixed_and_bad_vec():

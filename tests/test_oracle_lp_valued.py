@@ -1,11 +1,9 @@
 """Pins the yardstick of the valued LP kernels independently: the C oracle in Eigen order with stored values against the numpy
-restatement (oracle/lpbox_numpy.py), whose E is replaced by the valued matrix -- it computes Esq_diag and every product from E
-generically.  The restatement sums in numpy's own order, so agreement is to rounding: over the iterations before the first differing
+restatement (oracle/lpbox_numpy.py) given the same values (vals=) -- it computes Esq_diag and every product from the stored entries.  The restatement sums in numpy's own order, so agreement is to rounding: over the iterations before the first differing
 PCG count, |dx| <= 1e-3 max(1, |x|inf), the PCG's own exit tolerance.  (Where the very first x-update already stops one PCG iteration
 apart -- the two residuals straddle the exit test -- there is no such prefix and the draw pins nothing; each draw prints its prefix.)  CPU only; passes with or without the valued kernels."""
 import numpy as np
 import pytest
-import scipy.sparse as sp
 
 from helpers import common_prefix, lp_instances
 from oracle.lpbox_numpy import NumpyLpBox
@@ -15,9 +13,7 @@ ITERS = 40
 
 
 def restatement(I):
-    s = NumpyLpBox(I["n"], I["l"], I["colptr"], I["rowidx"], I["b"])
-    s.E = sp.csc_matrix((I["vals"], I["rowidx"], I["colptr"]), shape=(I["l"], I["n"]))
-    s.orgE = s.E.copy()
+    s = NumpyLpBox(I["n"], I["l"], I["colptr"], I["rowidx"], I["b"], vals=I["vals"])
     s.solve_init()
     return s
 

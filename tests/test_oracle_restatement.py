@@ -1,7 +1,8 @@
 """CPU tests: the C oracles of the generic BQP (oracle/bqp_oracle.c) and of the segmentation loops (oracle/seg_oracle.c) against the
 independent numpy restatement oracle/bqp_numpy.py, written from the reference source alone.
 
-Tolerance rule (as for the LP path, tests/test_oracle_lp.py): over the prefix of outer iterations where the PCG iteration counts of
+Tolerance rule (NOT the LP path's: along an LP trajectory the two oracle orders agree by luck at iteration 0 and B collapses, so the LP
+path is held step by step to a bound from the restatement's own rounding spread, tests/lp_steplock.py): over the prefix of outer iterations where the PCG iteration counts of
 both oracle orders and of the restatement agree, every compared vector and scalar is within B of the restatement, B = 10 x the
 oracle's own Eigen-order vs GPU-order spread at that point plus 1e-12 max(1, |v|).  Each prefix must hold a rho / gamma update that
 has reached the matrix, the y3 / z3 / z4 updates of its type and a std_obj evaluation."""

@@ -47,6 +47,7 @@ struct lpbox_bqp : GenHostProblem {
     int G = 0, Gm = 0, Gl = 0, EPT = 2, EPTm = 2, EPTl = 2, kmax = 12, parity = 0;
     bool adaptive = true;
     double kernel_ms = 0.0; long long launches = 0;
+    long long pcg_resumes = 0;   // GEN_HALT_PCG_MORE seen by the loop of the last lpbox_bqp_solve
     // launch-bound inner loop: GEN_ITERS_PER_GRAPH outer iterations captured once per (PCG launch count, start parity) and replayed
     std::map<std::pair<int, int>, hipGraphExec_t> gexec; std::vector<hipGraph_t> graphs;
     long long graph_launches = 0;
@@ -156,6 +157,7 @@ lpbox_bqp_t *lpbox_bqp_create(int device) {
     memset(&h->hst, 0, sizeof(h->hst));
     lpbox_bqp_preset(h, 0);
     if (getenv("LPBOX_BQP_NOGRAPH")) h->use_graph = false;
+    if (const char *e = getenv("LPBOX_BQP_KMAX")) { int v = atoi(e); if (v >= 1 && v <= 1000) { h->kmax = v; h->adaptive = false; } }
     return h;
 }
 
@@ -223,7 +225,11 @@ int lpbox_bqp_solve(lpbox_bqp_t *h, int *iterations) {                          
         h->uploaded = true;
     }
     const GenDev d = h->dev();
-    h->parity = 0; h->kernel_ms = 0; h->launches = 0;
+    h->parity = 0; h->kernel_ms = 0; h->launches = 0; h->pcg_resumes = 0;
+    // a PCG of at most pcg_maxiters iterations is complete after this many resumes of 16 launch groups: a chain that asks for more is
+    // broken, and the loop returns an error instead of resuming for ever
+    const int resume_limit = h->prm.pcg_maxiters / 16 + 2;
+    int resumed = 0;                                                                // resumes since an outer iteration last completed
     HIPCHK(hipEventRecord(h->ev0, h->stream));
     HIPCHK(gen_launch_init(d, std::pow((double)n, 1.0 / 2), h->dx0.p, h->stream));    // std::pow(n, 1.0 / p), p = 2 (SEGcpp:556)
     HIPCHK(gen_launch_init2(d, h->stream));
@@ -232,6 +238,9 @@ int lpbox_bqp_solve(lpbox_bqp_t *h, int *iterations) {                          
     for (;;) {
         CHK(read_state(h));
         if (h->hst.halt == GEN_HALT_PCG_MORE) {
+            if (++resumed > resume_limit)
+                return lpbox_fail(LPBOX_E_STATE, "iteration %d: the PCG is still halted at k = %d after %d resumes in a row", h->hst.iter, h->hst.pcg_k, resumed - 1);
+            h->pcg_resumes++;
             HIPCHK(gen_launch_resume(d, 0, &h->parity, h->stream));
             CHK(enqueue_pcg(h, d, 16));
             CHK(enqueue_tail(h, d));
@@ -239,6 +248,7 @@ int lpbox_bqp_solve(lpbox_bqp_t *h, int *iterations) {                          
             continue;
         }
         if (h->hst.halt != GEN_HALT_NONE) break;
+        resumed = 0;
         const int remaining = h->prm.max_iters - h->hst.iter;
         if (remaining <= 0 && !h->hst.have_prev) break;
         if (h->adaptive && h->hst.outer_total > 0) h->kmax = std::max(3, h->hst.pcg_max + 1);      // one spare PCG launch group; the halt-and-resume path covers a miss
@@ -288,6 +298,7 @@ int lpbox_bqp_get_scalar(lpbox_bqp_t *h, const char *name, double *out) {
         {"cur_obj", s.cur_obj}, {"best_bin_obj", s.best_bin_obj}, {"obj_val", s.obj_val}, {"iters", (double)s.iter}, {"stop", (double)s.stop},
         {"total_pcg", (double)s.pcg_total}, {"outer_total", (double)s.outer_total}, {"last_pcg", (double)s.last_pcg},
         {"kernel_ms", h->kernel_ms}, {"launches", (double)h->launches}, {"threads", (double)GEN_T}, {"chunk", (double)(GEN_T * h->EPT)},
+        {"pcg_resumes", (double)h->pcg_resumes}, {"kmax", (double)h->kmax},
     };
     for (auto &e : tab) if (!strcmp(e.n, name)) { *out = e.v; return LPBOX_OK; }
     return lpbox_fail(LPBOX_E_BADARG, "unknown scalar '%s'", name);

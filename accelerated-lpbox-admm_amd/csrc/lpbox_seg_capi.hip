@@ -28,6 +28,9 @@ struct Buf {
 constexpr int ITERS_PER_GRAPH = 4;
 static_assert(ITERS_PER_GRAPH % 2 == 0, "an iteration is an odd number of launches: an even count keeps the ping-pong parity");
 constexpr int SEG_KMAX_LIMIT = 24;
+// A PCG of at most SEG_PCG_MAXITERS iterations is complete after this many resumes of 16 pairs whatever kmax was: a chain that asks for
+// more is broken, and the host loops return an error instead of resuming for ever.
+constexpr int SEG_RESUME_LIMIT = SEG_PCG_MAXITERS / 16 + 2;
 }  // namespace
 
 struct SegSolver {
@@ -49,6 +52,7 @@ struct SegSolver {
     hipGraph_t graph[SEG_KMAX_LIMIT + 1][2] = {}; hipGraphExec_t gexec[SEG_KMAX_LIMIT + 1][2] = {};
     bool adaptive = true;
     double kernel_ms = 0.0; long long launches = 0;
+    long long pcg_resumes = 0;   // SEG_HALT_PCG_MORE seen by the host loops on this handle's state since solve_init
     Buf<int> d_ecol, d_left;
     Buf<uint8_t> d_rowlen;
     int ell_w = 0;
@@ -310,19 +314,26 @@ int run_window(SegSolver *s, int iter_end) {
     // there one late problem stalls all).
     static const int kmargin = getenv("LPBOX_SEG_KMARGIN") ? std::max(0, atoi(getenv("LPBOX_SEG_KMARGIN"))) : 0;
     HIPCHK(hipEventRecord(s->ev0, s->stream));
+    int resumed = 0;                                                       // resumes since an outer iteration last completed
     for (;;) {
         int rc = read_state(s);
         if (rc) return rc;
         if (s->hst.halt == SEG_HALT_PCG_MORE) {
+            if (++resumed > SEG_RESUME_LIMIT)
+                return lpbox_fail(LPBOX_E_STATE, "iteration %d: the PCG is still halted at k = %d after %d resumes in a row", s->hst.iter, s->hst.pcg_k, resumed - 1);
+            s->pcg_resumes++;
             HIPCHK(seg_enqueue_pcg_more(s->dev(), 16, &s->parity, s->stream));
             s->launches += 34;
             if (s->adaptive) s->kmax = std::min(SEG_KMAX_LIMIT, std::max(s->kmax, s->hst.pcg_k + 4));
             continue;
         }
         if (s->hst.halt != SEG_HALT_NONE) break;
+        resumed = 0;
         const int remaining = iter_end - s->hst.iter;
         if (remaining <= 0 && !s->hst.have_prev) break;
-        if (s->adaptive && s->hst.outer_total > 0) s->kmax = std::min(SEG_KMAX_LIMIT, std::max(2, s->hst.pcg_max + kmargin));
+        // (pcg_max == 0: no PCG completed in the previous batch -- it only finalised an iteration that had been resumed -- so there is
+        //  nothing to track and kmax stays; it used to fall to 2 here, and the next window began with a halt)
+        if (s->adaptive && s->hst.outer_total > 0 && s->hst.pcg_max > 0) s->kmax = std::min(SEG_KMAX_LIMIT, std::max(2, s->hst.pcg_max + kmargin));
         HIPCHK(seg_launch_copy(s->dev(), 1, &s->parity, s->stream));       // pcg_max = 0 for the coming batch
         HIPCHK(seg_enqueue_prep(s->dev(), &s->parity, s->stream));         // head of the batch (inside it post + yrhs do prep's work)
         s->launches += 2;
@@ -363,18 +374,21 @@ int batch_reset_handle(SegSolver *s) {
     s->left_idx.resize(s->n);
     for (int k = 0; k < s->n; k++) s->left_idx[k] = k;
     s->left_stale = false; s->dleft_valid = false; s->win_serial++;
+    s->pcg_resumes = 0;
     return LPBOX_OK;
 }
 
 // The lockstep chain of a batch (devs = device array of B descriptors, the window already set): iterations up to iter_end for every
 // problem, each on its own control state -- one that has stopped, is all fixed or whose PCG has converged falls through, a
-// SEG_HALT_PCG_MORE on any problem resumes the chain.  hs[B] receives the final states; *kmax carries the adaptive launch count.
+// SEG_HALT_PCG_MORE on any problem resumes the chain.  hs[B] receives the final states; *kmax carries the adaptive launch count;
+// resumes[B] is raised for every problem whose own state showed the halt at a resume.
 int batch_run_chain(const SegDev *devs, SegState *dstates, int B, int Gmax, int iter_end, int *parity, int *kmax, bool adaptive,
-                    SegState *hs, long long *launches, hipStream_t st) {
+                    SegState *hs, long long *launches, long long *resumes, hipStream_t st) {
     // spare (matvec, update) pairs per iteration beyond the largest PCG count any problem showed in the previous batch of iterations: 0, as
     // in the single-problem chain (a miss halts that problem's PCG and the chain resumes it).  Measured, 100 problems at 10^4 nodes, fastest
     // / median of five runs: margin 2 119 / 120 ms, margin 1 111 / 112 ms, margin 0 108 / 108 ms; 16 problems 46 -> 41 ms.
     static const int bmargin = getenv("LPBOX_SEG_KMARGIN") ? std::max(0, atoi(getenv("LPBOX_SEG_KMARGIN"))) : 0;
+    std::vector<int> resumed(B, 0);                                 // per problem: resumes since one of its outer iterations last completed
     for (;;) {
         HIPCHK(segb_collect_states(devs, B, *parity, dstates, st));
         HIPCHK(hipMemcpyAsync(hs, dstates, sizeof(SegState) * (size_t)B, hipMemcpyDeviceToHost, st));
@@ -383,11 +397,21 @@ int batch_run_chain(const SegDev *devs, SegState *dstates, int B, int Gmax, int 
         int remaining = 0, pcg_max = 0, pcg_k = 0;
         for (int i = 0; i < B; i++) {
             const SegState &h = hs[i];
-            if (h.halt == SEG_HALT_PCG_MORE) { more = true; pcg_k = std::max(pcg_k, h.pcg_k); continue; }
+            if (h.halt == SEG_HALT_PCG_MORE) {
+                if (++resumed[i] > SEG_RESUME_LIMIT)
+                    return lpbox_fail(LPBOX_E_STATE, "problem %d of the batch, iteration %d: the PCG is still halted at k = %d after %d resumes in a row", i, h.iter, h.pcg_k, resumed[i] - 1);
+                resumes[i]++; more = true; pcg_k = std::max(pcg_k, h.pcg_k);
+                continue;
+            }
+            resumed[i] = 0;
             if (h.halt != SEG_HALT_NONE) continue;
             const int rem = iter_end - h.iter;
             if (rem <= 0 && !h.have_prev) continue;
-            any_run = true; remaining = std::max(remaining, rem); pcg_max = std::max(pcg_max, h.outer_total > 0 ? h.pcg_max : *kmax - bmargin);
+            // (pcg_max == 0: this problem completed no PCG in the previous batch, which only finalised a resumed iteration or was not
+            //  its own: nothing to track, it votes for the kmax in use -- it used to vote 0, and a window after one whose last iteration
+            //  had been resumed began at kmax = 2, with a halt of every problem)
+            any_run = true; remaining = std::max(remaining, rem);
+            pcg_max = std::max(pcg_max, h.outer_total > 0 && h.pcg_max > 0 ? h.pcg_max : *kmax - bmargin);
         }
         if (more) {                                                 // some PCG ran out of launches: resume it (the others fall through)
             HIPCHK(segb_enqueue_pcg_more(devs, B, Gmax, 16, parity, st));
@@ -475,7 +499,7 @@ int segc_init(SegSolver *s) {
     s->left_idx.resize(s->n);
     for (int i = 0; i < s->n; i++) s->left_idx[i] = i;
     s->left_stale = false; s->dleft_valid = false; s->win_serial++;
-    s->xi_valid = false; s->parity = 0;
+    s->xi_valid = false; s->parity = 0; s->pcg_resumes = 0;
     HIPCHK(seg_launch_init(s->dev(), std::pow((double)s->n, 1.0 / 2), s->stream));    // pow(n, 1/p), p = 2 (SEGcpp:557,670)
     rc = read_state(s);
     if (rc) return rc;
@@ -534,11 +558,12 @@ int segc_legacy_batch(SegSolver **ss, int B, int *energies) {
     std::vector<SegState> hs(B);
     int parity = 0, kmax = s0->kmax;
     long long launches = 0;
+    std::vector<long long> resumes(B, 0);
     HIPCHK(hipEventRecord(s0->ev0, st));
     HIPCHK(segb_launch_init(devs.p, B, Gmax, st));
     HIPCHK(segb_launch_set_window(devs.p, B, 0, SEG_MAX_ITERS, 0, &parity, st));
     launches += 2;
-    if ((rc = batch_run_chain(devs.p, dstates.p, B, Gmax, SEG_MAX_ITERS, &parity, &kmax, s0->adaptive, hs.data(), &launches, st))) return rc;
+    if ((rc = batch_run_chain(devs.p, dstates.p, B, Gmax, SEG_MAX_ITERS, &parity, &kmax, s0->adaptive, hs.data(), &launches, resumes.data(), st))) return rc;
     HIPCHK(hipEventRecord(s0->ev1, st));
     HIPCHK(hipStreamSynchronize(st));
     float ms = 0.f;
@@ -546,6 +571,7 @@ int segc_legacy_batch(SegSolver **ss, int B, int *energies) {
     for (int i = 0; i < B; i++) {
         SegSolver *s = ss[i];
         s->hst = hs[i]; s->parity = parity; s->rec_cols = 0; s->xi_valid = false; s->inited = true;
+        s->pcg_resumes += resumes[i];
         if (energies) energies[i] = (int)(s->hst.cur_obj + s->c);     // :1379
     }
     s0->kernel_ms += ms; s0->launches += launches;
@@ -730,6 +756,7 @@ int segc_debug_scalar(SegSolver *s, const char *name, double *out) {
         {"rho1", h.rho1}, {"gamma", h.gamma_val}, {"cur_obj", h.cur_obj}, {"std_obj", h.std_obj}, {"cvg1", h.cvg1}, {"cvg2", h.cvg2},
         {"obj_val", h.obj_val}, {"best_bin_obj", h.best_bin_obj}, {"c", s->c}, {"last_pcg", (double)h.last_pcg}, {"iter", (double)h.iter},
         {"matrix_as_diagonals", s->dia ? 1.0 : 0.0}, {"ell_width", (double)s->ell_w},
+        {"pcg_resumes", (double)s->pcg_resumes}, {"kmax", (double)s->kmax},
     };
     for (auto &e : tab) if (!strcmp(e.n, name)) { *out = e.v; return LPBOX_OK; }
     return lpbox_fail(LPBOX_E_BADARG, "unknown scalar '%s'", name);
@@ -906,8 +933,9 @@ int segb_window(lpbox_seg_batch *b, int iter_start, int iter_end, bool score_for
     if (any) { HIPCHK(segb_launch_compact(b->devs.p, b->aux.p, b->par.p, A, st)); launches++; }
 
     std::vector<SegState> hs(A);
+    std::vector<long long> resumes(A, 0);
     int kmax = b->kmax;
-    if ((rc = batch_run_chain(b->devs.p, b->dstates.p, A, Gmax, iter_end, &parity, &kmax, b->ss[0]->adaptive, hs.data(), &launches, st))) return rc;
+    if ((rc = batch_run_chain(b->devs.p, b->dstates.p, A, Gmax, iter_end, &parity, &kmax, b->ss[0]->adaptive, hs.data(), &launches, resumes.data(), st))) return rc;
     b->kmax = kmax;
     HIPCHK(hipEventRecord(b->ev1, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -917,6 +945,7 @@ int segb_window(lpbox_seg_batch *b, int iter_start, int iter_end, bool score_for
         SegSolver *s = b->ss[act[k]];
         s->hst = hs[k]; s->parity = parity; s->rec_cols = 0;
         s->xi_rows = live[k] - applied[k]; s->last_ws = ws; s->xi_valid = true; s->win_serial++;
+        s->pcg_resumes += resumes[k];
         if (score_form && applied[k]) s->left_stale = true;          // fixed on the device: the host list follows on demand
         else if (applied[k]) s->left_idx.swap(kept[k]);
         s->xi_left_idx.clear();

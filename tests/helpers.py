@@ -388,6 +388,14 @@ def banded_seg_problem(n, seed=0, fourth_offset=False):
                 b=rs.randint(-40, 40, n).astype(float), c=0.0, rows=1, cols=n)
 
 
+def scaled_seg_problem(P, s):
+    """P with every stored value of A multiplied by s (b, c and the shape as they are): 2A + (rho1 + rho2) I is the worse conditioned
+    the larger s, so the PCG of an outer iteration runs the longer (tests/test_chain_resume_cases.py pins the counts)."""
+    Q = dict(P)
+    Q["vals"] = np.asarray(P["vals"], np.float64) * s
+    return Q
+
+
 def synthetic_gray(rows, cols, seed=0):
     """A blocky grayscale image with noise (uint8), fast at any size."""
     rs = np.random.RandomState(seed)

@@ -27,6 +27,7 @@ struct lpbox_bqp_batch {
     int device = 0, count = 0;
     std::vector<BatchProblem> prob;
     bool uploaded = false, solved = false;
+    bool ref = false;                        // LPBOX_ORDER_REFERENCE: the REF kernels, c1 through libm's pow
     int nmax = 0, mmax = 0, lmax = 0, slots = 2, window = GENB_DEFAULT_WINDOW;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -42,6 +43,13 @@ int batch_device(lpbox_bqp_batch *h) {
     if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) return lpbox_fail(LPBOX_E_NODEVICE, "no HIP device available");
     HIPCHK(hipSetDevice(h->device));
     return LPBOX_OK;
+}
+// c1 = pow(n, 1/p), p = 2 (SEGcpp:556) through libm's pow, as the reference and the oracle call it: with the literal exponent the compiler
+// may turn the call into sqrt, and glibc's pow is not correctly rounded.  Reference order only (as ref_c1 of lpbox_big_capi.hip); no
+// n <= GENB_MAXDIM tells the two apart, the default order keeps the expression it has always had.
+double ref_c1(int n) {
+    volatile double e = 1.0 / 2;
+    return std::pow((double)n, e);
 }
 void release(lpbox_bqp_batch *h) {
     if (h->ipool) (void)hipFree(h->ipool);
@@ -95,7 +103,7 @@ int upload(lpbox_bqp_batch *h) {
         GenbProb &g = h->hprob[i];
         const int *I = h->ipool; double *D = h->dpool;
         g.n = p.n; g.m = p.m; g.l = p.l; g.eq = p.m > 0; g.ineq = p.l > 0; g.prm = p.prm;
-        g.c1 = std::pow((double)p.n, 1.0 / 2);                                        // std::pow(n, 1.0 / p), p = 2 (SEGcpp:556)
+        g.c1 = h->ref ? ref_c1(p.n) : std::pow((double)p.n, 1.0 / 2);                 // std::pow(n, 1.0 / p), p = 2 (SEGcpp:556)
         g.aptr = I + o.aptr; g.aidx = I + o.aidx; g.adiag = I + o.adiag; g.aval = D + o.aval; g.tmval = D + o.tmval;
         g.Cr = GenCsr{I + o.crp, I + o.cri, D + o.crv}; g.Cc = GenCsr{I + o.ccp, I + o.cci, D + o.ccv}; g.Cc_sv = D + o.ccsv;
         g.Er = GenCsr{I + o.erp, I + o.eri, D + o.erv}; g.Ec = GenCsr{I + o.ecp, I + o.eci, D + o.ecv}; g.Ec_sv = D + o.ecsv;
@@ -173,6 +181,15 @@ int lpbox_bqp_batch_set_problem(lpbox_bqp_batch_t *h, int idx, int n, const int 
     return LPBOX_OK;
 }
 
+int lpbox_bqp_batch_set_order(lpbox_bqp_batch_t *h, int mode) {
+    if (!h) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
+    if (mode != LPBOX_ORDER_DEFAULT && mode != LPBOX_ORDER_REFERENCE)
+        return lpbox_fail(LPBOX_E_BADARG, "unknown order %d (LPBOX_ORDER_DEFAULT or LPBOX_ORDER_REFERENCE)", mode);
+    h->ref = mode == LPBOX_ORDER_REFERENCE;
+    h->uploaded = false; h->solved = false;                  // c1 of the descriptors follows the order
+    return LPBOX_OK;
+}
+
 int lpbox_bqp_batch_solve(lpbox_bqp_batch_t *h, int *iterations) {                 // ADMM_bqp SEGcpp:1384-1832, every problem of the batch
     if (!h) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
     for (int i = 0; i < h->count; i++) if (!h->prob[i].set) return lpbox_fail(LPBOX_E_STATE, "no problem set at index %d", i);
@@ -182,12 +199,18 @@ int lpbox_bqp_batch_solve(lpbox_bqp_batch_t *h, int *iterations) {              
         HIPCHK(hipEventCreate(&h->ev0)); HIPCHK(hipEventCreate(&h->ev1));
     }
     if (!h->uploaded) CHK(upload(h));
+    if (h->ref) {                                            // the staging rows of the reference order must fit beside the gathered vectors
+        const size_t lds = genb_lds_bytes(h->nmax, h->mmax, h->lmax, true);
+        if (lds + GENB_STATIC_LDS > GENB_LDS_LIMIT)
+            return lpbox_fail(LPBOX_E_UNSUPPORTED, "reference order: the batch needs %zu B of LDS per workgroup (n <= %d, m <= %d, l <= %d), more than "
+                              "%d B", lds + GENB_STATIC_LDS, h->nmax, h->mmax, h->lmax, GENB_LDS_LIMIT);
+    }
     h->kernel_ms = 0; h->launches = 0; h->solved = false;
     h->hst.assign(h->count, GenState());
     HIPCHK(hipEventRecord(h->ev0, h->stream));
-    HIPCHK(genb_launch_init(h->dprob, h->dst, h->count, h->slots, h->stream)); h->launches++;
+    HIPCHK(genb_launch_init(h->dprob, h->dst, h->count, h->slots, h->nmax, h->ref, h->stream)); h->launches++;
     for (;;) {
-        HIPCHK(genb_launch_window(h->dprob, h->dst, h->count, h->slots, h->window, h->nmax, h->mmax, h->lmax, h->stream)); h->launches++;
+        HIPCHK(genb_launch_window(h->dprob, h->dst, h->count, h->slots, h->window, h->nmax, h->mmax, h->lmax, h->ref, h->stream)); h->launches++;
         HIPCHK(hipMemcpyAsync(h->hst.data(), h->dst, sizeof(GenState) * (size_t)h->count, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
         bool all = true;
@@ -224,7 +247,7 @@ int lpbox_bqp_batch_get_scalar(lpbox_bqp_batch_t *h, int idx, const char *name, 
     if (!h || !h->solved || !out || !name) return lpbox_fail(LPBOX_E_STATE, "not solved");
     struct { const char *n; double v; } wide[] = {
         {"kernel_ms", h->kernel_ms}, {"launches", (double)h->launches}, {"threads", (double)GEN_T}, {"chunk", (double)(GEN_T * 2)},
-        {"window", (double)h->window}, {"slots", (double)h->slots},
+        {"window", (double)h->window}, {"slots", (double)h->slots}, {"order", (double)(h->ref ? LPBOX_ORDER_REFERENCE : LPBOX_ORDER_DEFAULT)},
     };
     for (auto &e : wide) if (!strcmp(e.n, name)) { *out = e.v; return LPBOX_OK; }
     CHK(check_index(h, idx, false));

@@ -12,9 +12,14 @@
 // Placement: the gathered vectors (the PCG direction / y1 / x, C v, E v) live in LDS; the PCG state of a thread's elements (x, r, p,
 // 1/diag, M p, z) in registers; the ADMM state between outer iterations and all matrices in the problem's slice of the pooled global
 // arrays, where each element is read and written by its owner thread only (L2 traffic once per outer iteration, not per PCG step).
+// REF = true (lpbox_bqp_batch_set_order(LPBOX_ORDER_REFERENCE)): the same kernels with every sum over a
+// problem's n elements in the reference's order instead -- Eigen's redux over the n terms in index order (lpbox_eigen_redux.h): the
+// terms go to staging rows in LDS between the gathered vector and C v, and four lanes per value walk them.  Rows, columns and every other
+// expression are shared with the default order, whose code is what it was (the `if constexpr (!REF)` branches).
 #include "lpbox_genb.h"
 #include "lpbox_dev_common.h"
 #include "lpbox_gen_dev.h"
+#include "lpbox_eigen_redux.h"
 
 #include <float.h>
 
@@ -62,16 +67,19 @@ template <typename F>
 __device__ __forceinline__ void for_rows(int rows, F f) { for (int i = threadIdx.x; i < rows; i += T) f(i); }
 
 // ---- SEGcpp:1430-1560: x = y1 = y2 = best = x0, the matrix 2A + (rho1+rho2) I, the scaled transposes, the Jacobi diagonal, cost(x0)
-template <int SL>
+template <int SL, bool REF>
 __global__ void __launch_bounds__(T) genb_init_kernel(const GenbProb *probs, GenState *states) {
+    extern __shared__ double lds[];                          // REF: [res ER_RES][2 staging rows of er_stride(n)]; otherwise none
     __shared__ double red[2 * RED_MAXV * RED_MAXW];
     constexpr int GC = SL / 2;
-    int parity = 0;
+    [[maybe_unused]] int parity = 0;
     const int tid = threadIdx.x;
     const GenbProb P = probs[blockIdx.x];
     const double rho = P.prm.initial_rho;
     const double *x0 = P.x0;
-    double pc[2 * GC];
+    [[maybe_unused]] double *const stage = lds + ER_RES;
+    [[maybe_unused]] const int sst = er_stride(P.n);
+    [[maybe_unused]] double pc[2 * GC];
 #pragma unroll
     for (int k = 0; k < 2 * GC; k++) pc[k] = 0.0;
 #pragma unroll
@@ -97,11 +105,13 @@ __global__ void __launch_bounds__(T) genb_init_kernel(const GenbProb *probs, Gen
             P.pdiag[j] = pd; P.dinv[j] = 1.0;
             const double ax = gen_sparse_dot(P.aidx, P.aval, P.aptr[j], P.aptr[j + 1], [x0](int c) { return x0[c]; });   // best_bin_obj = cost(x0) (:1560)
             c0 = xj * ax; c1v = P.b[j] * xj;
+            if constexpr (REF) { stage[j] = c0; stage[sst + j] = c1v; }
         }
-        pc[s / 2] = pc[s / 2] + c0; pc[GC + s / 2] = pc[GC + s / 2] + c1v;
+        if constexpr (!REF) { pc[s / 2] = pc[s / 2] + c0; pc[GC + s / 2] = pc[GC + s / 2] + c1v; }
     }
     double o[2];
-    reduce_chunks<2, GC>(pc, o, red, parity);
+    if constexpr (REF) er_reduce<2>(stage, sst, P.n, lds, o);
+    else reduce_chunks<2, GC>(pc, o, red, parity);
     if (P.eq) for_rows(P.m, [&](int i) { P.z3[i] = 0.0; });
     if (P.ineq) for_rows(P.l, [&](int i) { P.z4[i] = 0.0; P.y3[i] = 0.0; P.fy[i] = 0.0; P.Ex[i] = csr_dot(P.Er, P.Er.val, i, x0); });   // E x0 for the first y3
     if (tid == 0) {
@@ -115,19 +125,22 @@ __global__ void __launch_bounds__(T) genb_init_kernel(const GenbProb *probs, Gen
 }
 
 // ---- at most `window` outer iterations of ADMM_bqp (SEGcpp:1596-1794) for the problem of this workgroup
-template <int SL>
+template <int SL, bool REF>
 __global__ void __launch_bounds__(T) genb_window_kernel(const GenbProb *probs, GenState *states, int window, int npad, int mmax) {
     extern __shared__ double lds[];
     __shared__ double red[2 * RED_MAXV * RED_MAXW];
     __shared__ GenState S;
     constexpr int GC = SL / 2;
-    int parity = 0;
+    [[maybe_unused]] int parity = 0;
     const int tid = threadIdx.x;
     GenState *gst = states + blockIdx.x;
     if (gst->halt) return;                                   // a halted problem is not touched again
     const GenbProb P = probs[blockIdx.x];
     const GenParams &prm = P.prm;
-    double *g = lds, *qC = lds + npad, *qE = lds + npad + mmax;
+    // REF: the totals and ER_MAXV staging rows sit between g and C v
+    [[maybe_unused]] double *const res = lds + npad, *const stage = res + ER_RES;
+    [[maybe_unused]] const int sst = er_stride(npad);
+    double *g = lds, *qC = REF ? stage + ER_MAXV * sst : lds + npad, *qE = qC + mmax;
     const int n = P.n, type = (P.eq ? 1 : 0) | (P.ineq ? 2 : 0);
     const bool rows = P.eq || P.ineq;
     if (tid == 0) S = *gst;
@@ -156,17 +169,19 @@ __global__ void __launch_bounds__(T) genb_window_kernel(const GenbProb *probs, G
         // ---- ||x + z2/rho2 - 1/2||^2 (:1603-1606, :553-558)
         double c2;
         {
-            double pa[GC], o[1];
+            [[maybe_unused]] double pa[GC];
+            double o[1];
 #pragma unroll
             for (int k = 0; k < GC; k++) pa[k] = 0.0;
 #pragma unroll
             for (int s = 0; s < SL; s++) {
                 const int j = s * T + tid;
                 double c = 0.0;
-                if (j < n) { const double u = gen_y2_centre(P.x[j], P.z2[j], rho2); c = u * u; }
-                pa[s / 2] = pa[s / 2] + c;
+                if (j < n) { const double u = gen_y2_centre(P.x[j], P.z2[j], rho2); c = u * u; if constexpr (REF) stage[j] = c; }
+                if constexpr (!REF) pa[s / 2] = pa[s / 2] + c;
             }
-            reduce_chunks<1, GC>(pa, o, red, parity);
+            if constexpr (REF) er_reduce<1>(stage, sst, n, res, o);
+            else reduce_chunks<1, GC>(pa, o, red, parity);
             c2 = 2 * sqrt(o[0]);
         }
 
@@ -230,7 +245,8 @@ __global__ void __launch_bounds__(T) genb_window_kernel(const GenbProb *probs, G
         double threshold = 0.0, absNew = 0.0;
         bool done = false;
         {
-            double pb[3 * GC], o[3];
+            [[maybe_unused]] double pb[3 * GC];
+            double o[3];
 #pragma unroll
             for (int k = 0; k < 3 * GC; k++) pb[k] = 0.0;
 #pragma unroll
@@ -244,10 +260,12 @@ __global__ void __launch_bounds__(T) genb_window_kernel(const GenbProb *probs, G
                     const double pp = dv[s] * rr;
                     xt[s] = g[j]; r[s] = rr; p[s] = pp;
                     c0 = rhs[s] * rhs[s]; c1r = rr * rr; c2r = rr * pp;
+                    if constexpr (REF) { stage[j] = c0; stage[sst + j] = c1r; stage[2 * sst + j] = c2r; }
                 }
-                pb[s / 2] = pb[s / 2] + c0; pb[GC + s / 2] = pb[GC + s / 2] + c1r; pb[2 * GC + s / 2] = pb[2 * GC + s / 2] + c2r;
+                if constexpr (!REF) { pb[s / 2] = pb[s / 2] + c0; pb[GC + s / 2] = pb[GC + s / 2] + c1r; pb[2 * GC + s / 2] = pb[2 * GC + s / 2] + c2r; }
             }
-            reduce_chunks<3, GC>(pb, o, red, parity);
+            if constexpr (REF) er_reduce<3>(stage, sst, n, res, o);
+            else reduce_chunks<3, GC>(pb, o, red, parity);
             if (o[0] == 0) {                                                      // rhs == 0: x := 0 (:424-430)
                 done = true;
 #pragma unroll
@@ -269,21 +287,22 @@ __global__ void __launch_bounds__(T) genb_window_kernel(const GenbProb *probs, G
             if (rows) { rows_of_g(); __syncthreads(); }
             double o1[1], o2[2];
             {
-                double pc[GC];
+                [[maybe_unused]] double pc[GC];
 #pragma unroll
                 for (int q = 0; q < GC; q++) pc[q] = 0.0;
 #pragma unroll
                 for (int s = 0; s < SL; s++) {                                    // tmp = M p, p.tmp (:447-448)
                     const int j = s * T + tid;
                     double c = 0.0;
-                    if (j < n) { Mp[s] = expr_row(j); c = p[s] * Mp[s]; }
-                    pc[s / 2] = pc[s / 2] + c;
+                    if (j < n) { Mp[s] = expr_row(j); c = p[s] * Mp[s]; if constexpr (REF) stage[j] = c; }
+                    if constexpr (!REF) pc[s / 2] = pc[s / 2] + c;
                 }
-                reduce_chunks<1, GC>(pc, o1, red, parity);
+                if constexpr (REF) er_reduce<1>(stage, sst, n, res, o1);
+                else reduce_chunks<1, GC>(pc, o1, red, parity);
             }
             const double alpha = absNew / o1[0];
             {
-                double pd2[2 * GC];
+                [[maybe_unused]] double pd2[2 * GC];
 #pragma unroll
                 for (int q = 0; q < 2 * GC; q++) pd2[q] = 0.0;
 #pragma unroll
@@ -297,10 +316,12 @@ __global__ void __launch_bounds__(T) genb_window_kernel(const GenbProb *probs, G
                         const double zz = dv[s] * rr;
                         xt[s] = x; r[s] = rr; z[s] = zz;
                         a = rr * rr; b2 = rr * zz;
+                        if constexpr (REF) { stage[j] = a; stage[sst + j] = b2; }
                     }
-                    pd2[s / 2] = pd2[s / 2] + a; pd2[GC + s / 2] = pd2[GC + s / 2] + b2;
+                    if constexpr (!REF) { pd2[s / 2] = pd2[s / 2] + a; pd2[GC + s / 2] = pd2[GC + s / 2] + b2; }
                 }
-                reduce_chunks<2, GC>(pd2, o2, red, parity);
+                if constexpr (REF) er_reduce<2>(stage, sst, n, res, o2);
+                else reduce_chunks<2, GC>(pd2, o2, red, parity);
             }
             k++;
             if (o2[0] < threshold || k >= prm.pcg_maxiters) done = true;         // :453-456, :445
@@ -327,7 +348,8 @@ __global__ void __launch_bounds__(T) genb_window_kernel(const GenbProb *probs, G
         __syncthreads();
         double o[7];
         {
-            double e[7 * GC];
+            [[maybe_unused]] double e[7 * GC];
+            [[maybe_unused]] double late[SL][3];                                   // REF: the terms of sums 4..6, staged in a second round
 #pragma unroll
             for (int q = 0; q < 7 * GC; q++) e[q] = 0.0;
 #pragma unroll
@@ -341,10 +363,23 @@ __global__ void __launch_bounds__(T) genb_window_kernel(const GenbProb *probs, G
                     const double d1 = x - y1, d2 = x - y2, xb = x >= 0.5 ? 1.0 : 0.0;
                     v[0] = x * x; v[1] = d1 * d1; v[2] = d2 * d2; v[3] = x * ax; v[4] = b * x; v[5] = xb * axb; v[6] = b * xb;
                 }
+                if constexpr (REF) {
+                    if (j < n) { stage[j] = v[0]; stage[sst + j] = v[1]; stage[2 * sst + j] = v[2]; stage[3 * sst + j] = v[3]; }
+                    late[s][0] = v[4]; late[s][1] = v[5]; late[s][2] = v[6];
+                } else {
 #pragma unroll
-                for (int q = 0; q < 7; q++) e[q * GC + s / 2] = e[q * GC + s / 2] + v[q];
+                    for (int q = 0; q < 7; q++) e[q * GC + s / 2] = e[q * GC + s / 2] + v[q];
+                }
             }
-            reduce_chunks<7, GC>(e, o, red, parity);
+            if constexpr (REF) {                                                    // seven sums, ER_MAXV rows: two rounds
+                er_reduce<4>(stage, sst, n, res, o);
+#pragma unroll
+                for (int s = 0; s < SL; s++) {
+                    const int j = s * T + tid;
+                    if (j < n) { stage[j] = late[s][0]; stage[sst + j] = late[s][1]; stage[2 * sst + j] = late[s][2]; }
+                }
+                er_reduce<3>(stage, sst, n, res, o + 4);
+            } else reduce_chunks<7, GC>(e, o, red, parity);
         }
         // ---- z3 += gamma rho3 (C x - d) (:1736), z4 += gamma rho4 (E x + y3 - f) (:1739); Ex = E x for the next y3
         const double g3 = gamma * rho3, g4 = gamma * rho4;
@@ -384,20 +419,49 @@ __global__ void __launch_bounds__(T) genb_window_kernel(const GenbProb *probs, G
 // ---------------------------------------------------------------------------------------------------------------------
 static inline int genb_pad(int n) { return (n + 1) & ~1; }
 
-size_t genb_lds_bytes(int nmax, int mmax, int lmax) { return sizeof(double) * ((size_t)genb_pad(nmax) + (size_t)mmax + (size_t)lmax); }
+// default order: the gathered vectors.  Reference order: also the totals and ER_MAXV staging rows of the largest n
+size_t genb_lds_bytes(int nmax, int mmax, int lmax, bool ref) {
+    size_t d = (size_t)genb_pad(nmax) + (size_t)mmax + (size_t)lmax;
+    if (ref) d += ER_RES + (size_t)ER_MAXV * er_stride(genb_pad(nmax));
+    return sizeof(double) * d;
+}
 
-hipError_t genb_launch_init(const GenbProb *probs, GenState *st, int count, int slots, hipStream_t s) {
-    if (slots == 2) hipLaunchKernelGGL(genb_init_kernel<2>, dim3(count), dim3(T), 0, s, probs, st);
-    else if (slots == 4) hipLaunchKernelGGL(genb_init_kernel<4>, dim3(count), dim3(T), 0, s, probs, st);
-    else hipLaunchKernelGGL(genb_init_kernel<8>, dim3(count), dim3(T), 0, s, probs, st);
+// above 64 KB of dynamic LDS a launch needs the function attribute (reference order with a large n + m + l only)
+template <typename K>
+static hipError_t genb_allow_lds(K kernel, size_t lds) {
+    if (lds <= 64 * 1024) return hipSuccess;
+    return hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+}
+
+hipError_t genb_launch_init(const GenbProb *probs, GenState *st, int count, int slots, int nmax, bool ref, hipStream_t s) {
+    if (ref) {
+        const size_t lds = sizeof(double) * (ER_RES + (size_t)2 * er_stride(nmax));       // at most 33 KB
+        if (slots == 2) hipLaunchKernelGGL((genb_init_kernel<2, true>), dim3(count), dim3(T), lds, s, probs, st);
+        else if (slots == 4) hipLaunchKernelGGL((genb_init_kernel<4, true>), dim3(count), dim3(T), lds, s, probs, st);
+        else hipLaunchKernelGGL((genb_init_kernel<8, true>), dim3(count), dim3(T), lds, s, probs, st);
+        return hipGetLastError();
+    }
+    if (slots == 2) hipLaunchKernelGGL((genb_init_kernel<2, false>), dim3(count), dim3(T), 0, s, probs, st);
+    else if (slots == 4) hipLaunchKernelGGL((genb_init_kernel<4, false>), dim3(count), dim3(T), 0, s, probs, st);
+    else hipLaunchKernelGGL((genb_init_kernel<8, false>), dim3(count), dim3(T), 0, s, probs, st);
     return hipGetLastError();
 }
 
-hipError_t genb_launch_window(const GenbProb *probs, GenState *st, int count, int slots, int window, int nmax, int mmax, int lmax, hipStream_t s) {
-    const size_t lds = genb_lds_bytes(nmax, mmax, lmax);
+hipError_t genb_launch_window(const GenbProb *probs, GenState *st, int count, int slots, int window, int nmax, int mmax, int lmax, bool ref,
+                              hipStream_t s) {
+    const size_t lds = genb_lds_bytes(nmax, mmax, lmax, ref);
     const int npad = genb_pad(nmax);
-    if (slots == 2) hipLaunchKernelGGL(genb_window_kernel<2>, dim3(count), dim3(T), lds, s, probs, st, window, npad, mmax);
-    else if (slots == 4) hipLaunchKernelGGL(genb_window_kernel<4>, dim3(count), dim3(T), lds, s, probs, st, window, npad, mmax);
-    else hipLaunchKernelGGL(genb_window_kernel<8>, dim3(count), dim3(T), lds, s, probs, st, window, npad, mmax);
+    if (ref) {
+        hipError_t e = slots == 2 ? genb_allow_lds(genb_window_kernel<2, true>, lds) : slots == 4 ? genb_allow_lds(genb_window_kernel<4, true>, lds)
+                                                                                                   : genb_allow_lds(genb_window_kernel<8, true>, lds);
+        if (e != hipSuccess) return e;
+        if (slots == 2) hipLaunchKernelGGL((genb_window_kernel<2, true>), dim3(count), dim3(T), lds, s, probs, st, window, npad, mmax);
+        else if (slots == 4) hipLaunchKernelGGL((genb_window_kernel<4, true>), dim3(count), dim3(T), lds, s, probs, st, window, npad, mmax);
+        else hipLaunchKernelGGL((genb_window_kernel<8, true>), dim3(count), dim3(T), lds, s, probs, st, window, npad, mmax);
+        return hipGetLastError();
+    }
+    if (slots == 2) hipLaunchKernelGGL((genb_window_kernel<2, false>), dim3(count), dim3(T), lds, s, probs, st, window, npad, mmax);
+    else if (slots == 4) hipLaunchKernelGGL((genb_window_kernel<4, false>), dim3(count), dim3(T), lds, s, probs, st, window, npad, mmax);
+    else hipLaunchKernelGGL((genb_window_kernel<8, false>), dim3(count), dim3(T), lds, s, probs, st, window, npad, mmax);
     return hipGetLastError();
 }

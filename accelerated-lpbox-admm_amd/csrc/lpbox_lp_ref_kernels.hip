@@ -19,6 +19,7 @@
 // Built with -ffp-contract=off like the rest of the library.  The one known deviation from the reference: the std stop test takes
 // sqrt where the reference calls pow(v, 1/2) (glibc pow is not correctly rounded; the oracle counts the disagreements).
 #include "lpbox_lp.h"
+#include "lpbox_eigen_redux.h"
 
 #include <float.h>
 
@@ -49,34 +50,8 @@ struct RefLds {
     }
 };
 
-// Eigen's redux_impl<scalar_sum_op, ..., LinearVectorizedTraversal, NoUnrolling> with Packet2d over a[0 .. size), run by the four
-// lanes c = 0..3 of a group: lane c carries accumulator c (p0a, p0b, p1a, p1b).  Every lane of the group returns the sum.
-__device__ __forceinline__ double eigen_walk(const double *a, int size, int c) {
-    if (size >= 4) {
-        const int ae2 = size & ~3;
-        double acc = a[c];
-        int k = 4 + c;
-        for (; k + 28 < ae2; k += 32) {                      // eight loads in flight, then the eight dependent additions in order
-            double v[8];
-#pragma unroll
-            for (int q = 0; q < 8; q++) v[q] = a[k + 4 * q];
-#pragma unroll
-            for (int q = 0; q < 8; q++) acc = acc + v[q];
-        }
-        for (; k < ae2; k += 4) acc = acc + a[k];
-        acc = acc + __shfl_xor(acc, 2, 4);                   // p0a + p1a (lanes 0, 2), p0b + p1b (lanes 1, 3)
-        if (size & 2) acc = acc + a[ae2 + (c & 1)];          // the left-over pair
-        double res = acc + __shfl_xor(acc, 1, 4);            // predux: p0a + p0b
-        if (size & 1) res = res + a[size - 1];
-        return res;
-    }
-    if (size >= 2) {
-        double res = a[0] + a[1];
-        if (size == 3) res = res + a[2];
-        return res;
-    }
-    return size == 1 ? a[0] : 0.0;
-}
+// (the walk itself -- Eigen's redux with Packet2d over a[0 .. size), one accumulator per lane of a group of four -- is er_walk of
+// lpbox_eigen_redux.h, shared with the BQP batch)
 
 // NR (<= 16) reductions of `size` staged products each (buffer k at stage + k * sst); every thread receives the sums.  The barrier on
 // entry publishes the products, the one on exit the results (and frees the staging buffers for the next reduction).
@@ -87,7 +62,7 @@ __device__ __forceinline__ void eigen_reduce(const double *stage, int sst, int s
     const int tid = threadIdx.x;
     if (tid < 4 * NR) {
         const int g = tid >> 2;
-        const double r = eigen_walk(stage + (size_t)g * sst, size, tid & 3);
+        const double r = er_walk(stage + (size_t)g * sst, size, tid & 3);
         if ((tid & 3) == 0) res[g] = r;
     }
     __syncthreads();

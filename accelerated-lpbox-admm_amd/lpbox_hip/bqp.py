@@ -139,6 +139,13 @@ def ADMM_bqp_linear_eq_and_uneq(n, A, b, x0, m, C_, d, l, E, f, **kw):
 
 # ---- many small problems at once (max(n, m, l) <= 2048 each): one persistent workgroup per problem ---------------------------------
 BATCH_MAX_DIM = 2048
+ORDERS = {"default": 0, "reference": 1}            # LPBOX_ORDER_DEFAULT, LPBOX_ORDER_REFERENCE
+
+
+def _order_mode(name):
+    if name not in ORDERS:
+        raise ValueError("summation order must be 'default' or 'reference'")
+    return ORDERS[name]
 
 
 def _per_problem(value, count, what):
@@ -167,9 +174,11 @@ class BqpBatch:
     """A batch of independent small BQPs solved together; every problem gives the bits `BqpSolver` gives for it alone.
 
     problems: a sequence of dicts with the keys n, A, b, x0 and optionally C, d, E, f (CSR triples or scipy.sparse matrices).
-    presets / params: None, a single value, or one per problem; the default preset follows the constraints present."""
+    presets / params: None, a single value, or one per problem; the default preset follows the constraints present.
+    order: "default", or "reference" (see `set_order`)."""
 
-    def __init__(self, problems, presets=None, params=None, device=0):
+    def __init__(self, problems, presets=None, params=None, device=0, order="default"):
+        mode = _order_mode(order)
         problems = list(problems)
         if not problems:
             raise ValueError("BqpBatch: no problems")
@@ -193,6 +202,9 @@ class BqpBatch:
         try:
             for i, P in enumerate(problems):
                 self._set(i, P, presets[i], params[i])
+            self.order = "default"
+            if mode:
+                self.set_order(order)
         except Exception:
             self.close()
             raise
@@ -227,6 +239,15 @@ class BqpBatch:
             check(self._L.lpbox_bqp_batch_set_params(self._h, i, np.ascontiguousarray(params, np.float64)), "lpbox_bqp_batch_set_params")
         self.dims.append((n, m, l))
 
+    def set_order(self, name="default"):
+        """Summation order of the batch kernels, chosen at any time before a solve.  "default": the kernels' own reduction tree, the
+        bits of `BqpSolver`.  "reference": an opt-in that associates every sum over a problem's n elements as the reference's Eigen path
+        does -- the reference's iterates, iteration counts and binary answers, except that the std stop test
+        takes sqrt where the reference calls pow(v, 1/2); each reduction becomes a sequential walk, so a PCG step costs more."""
+        mode = _order_mode(name)
+        check(self._L.lpbox_bqp_batch_set_order(self._h, mode), "lpbox_bqp_batch_set_order")
+        self.order = name
+
     def close(self):
         if getattr(self, "_h", None):
             self._L.lpbox_bqp_batch_destroy(self._h)
@@ -259,7 +280,8 @@ class BqpBatch:
 
 
 def solve_many(problems, **kw):
-    """Solve a sequence of small problems in one batch; a list of the dicts the ADMM_bqp_* entry points return."""
+    """Solve a sequence of small problems in one batch; a list of the dicts the ADMM_bqp_* entry points return.
+    Keywords are those of `BqpBatch` (presets, params, device, order)."""
     s = BqpBatch(problems, **kw)
     its = s.solve()
     out = []

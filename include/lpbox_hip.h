@@ -410,7 +410,19 @@ int lpbox_bqp_batch_set_problem(lpbox_bqp_batch_t *h, int idx, int n, const int 
                                 int l, const int *Ep, const int *Ei, const double *Ev, const double *f);
 int lpbox_bqp_batch_solve(lpbox_bqp_batch_t *h, int *iterations);                  /* ADMM_bqp (:1384-1832) for every problem, each to its own stop; iterations[count] may be NULL; LPBOX_E_STATE while an index is unset */
 int lpbox_bqp_batch_get_vec(lpbox_bqp_batch_t *h, int idx, const char *name, double *out, long cap);   /* the names of lpbox_bqp_get_vec */
-int lpbox_bqp_batch_get_scalar(lpbox_bqp_batch_t *h, int idx, const char *name, double *out);          /* the names of lpbox_bqp_get_scalar per problem; batch-wide (idx ignored): "kernel_ms","launches","threads","chunk","window","slots" */
+int lpbox_bqp_batch_get_scalar(lpbox_bqp_batch_t *h, int idx, const char *name, double *out);          /* the names of lpbox_bqp_get_scalar per problem; batch-wide (idx ignored): "kernel_ms","launches","threads","chunk","window","slots","order" */
+/* OPT-IN: the summation order of the batch kernels, LPBOX_ORDER_DEFAULT / LPBOX_ORDER_REFERENCE as for lpbox_set_order.  DEFAULT (the
+ * default) = the kernels' own reduction tree, bit for bit lpbox_bqp_solve and the oracle run in that association.  REFERENCE = every sum
+ * over the n elements of a problem (the dot products and squared norms of the PCG, of the y2 projection, of the stop tests and of
+ * compute_cost) associated as the reference's Eigen 3.3.8 SSE2 redux associates it: four accumulators over the index order, then the
+ * left-over pair, then the odd last element -- bit for bit oracle/bqp_oracle.c in its Eigen order on every vector and scalar, except
+ * that the std stop test takes sqrt where the reference calls pow(v, 1/2) ("std_obj" within 2 ulps).  Rows and columns are summed in
+ * the reference's order in both modes.  What it costs: each reduction becomes a strictly sequential walk of n / 4 dependent additions
+ * by four lanes (two walks per PCG step) instead of a tree, and four staging rows of LDS per workgroup (about 32 n bytes for the batch's
+ * largest n; DESIGN.md section 14.2 holds the plan and the measurements: 1.4 to 1.5 times the default order's kernel time); a batch whose LDS need exceeds one workgroup's 160 KB -> LPBOX_E_UNSUPPORTED
+ * from lpbox_bqp_batch_solve.  Allowed at any time before a solve; marks the batch as not solved.  "threads" and "chunk" keep their values
+ * (they describe the default order).  Unknown mode -> LPBOX_E_BADARG.  lpbox_bqp_* (one problem per handle) has no such mode. */
+int lpbox_bqp_batch_set_order(lpbox_bqp_batch_t *h, int mode);
 
 #ifdef __cplusplus
 }

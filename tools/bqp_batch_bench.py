@@ -9,8 +9,14 @@ REPEATS times and the medians are reported.  A full-length loop over the constra
 launch-bound chain per problem), so --loop-count N runs the loop over the first N problems only; the line then holds the measured
 time of those N and the time scaled to COUNT, and says so.  One JSON line per workload, appended to profiles/bqp_batch_bench.jsonl.
 
+--order reference measures what the reference's summation order costs (BqpBatch(order="reference")) instead:
+the batch in reference order and the batch in the default order alternate REPEATS times in one process, and the single-thread CPU
+oracle in its Eigen order (oracle/bqp_oracle.c, what the mode reproduces) solves the first --oracle-count N problems on the same host
+(default: all; the line holds the measured time of those N, the time scaled to COUNT, and whether the mode's x has the oracle's bits
+on them).  Lines go to profiles/bqp_batch_ref_bench.jsonl.
+
 usage: python tools/bqp_batch_bench.py [--count 256] [--repeats 3] [--loop-count N] [--workloads constrained,unconstrained]
-                                       [--cache FILE.npz] [--out FILE.jsonl]"""
+                                       [--order {default,reference}] [--oracle-count N] [--cache FILE.npz] [--out FILE.jsonl]"""
 import json
 import os
 import statistics
@@ -41,7 +47,11 @@ REPEATS = int(_opt("--repeats", 3))
 LOOP_COUNT = int(_opt("--loop-count", 0)) or COUNT
 WORKLOADS = _opt("--workloads", "constrained,unconstrained").split(",")
 CACHE = _opt("--cache")
-OUT = _opt("--out", os.path.join(ROOT, "profiles", "bqp_batch_bench.jsonl"))
+ORDER = _opt("--order", "default")
+if ORDER not in ("default", "reference"):
+    sys.exit("--order: default or reference")
+ORACLE_COUNT = int(_opt("--oracle-count", 0)) or COUNT
+OUT = _opt("--out", os.path.join(ROOT, "profiles", "bqp_batch_ref_bench.jsonl" if ORDER == "reference" else "bqp_batch_bench.jsonl"))
 SHAPES = {"constrained": (400, 25, 20), "unconstrained": (2000, 0, 0)}
 KEYS = ("A", "C", "E")
 
@@ -80,15 +90,17 @@ def problems_of(workload):
     return out
 
 
-def run_batch(problems):
+def run_batch(problems, order="default", keep=None):
     from lpbox_hip.bqp import BqpBatch
-    B = BqpBatch(problems)
+    B = BqpBatch(problems, order=order) if order != "default" else BqpBatch(problems)
     t0 = time.perf_counter()
     its = B.solve()
     wall = time.perf_counter() - t0
+    keep = LOOP_COUNT if keep is None else keep
+    pcgs = np.array([B.scalar(i, "total_pcg") for i in range(B.count)])
     r = dict(wall_s=wall, kernel_ms=B.scalar(0, "kernel_ms"), iters=its.copy(), launches=B.scalar(0, "launches"),
-             slots=B.scalar(0, "slots"), window=B.scalar(0, "window"), x=[B.vec(i, "x") for i in range(min(LOOP_COUNT, len(problems)))],
-             pcg=sum(B.scalar(i, "total_pcg") for i in range(B.count)))
+             slots=B.scalar(0, "slots"), window=B.scalar(0, "window"), x=[B.vec(i, "x") for i in range(min(keep, len(problems)))],
+             pcg=pcgs.sum(), pcg_max=pcgs.max())
     B.close()
     return r
 
@@ -105,7 +117,57 @@ def run_loop(problems):
     return r
 
 
+def run_oracle(problems):
+    """The single-thread CPU oracle in the reference's (Eigen) order; the handles are built before the clock starts."""
+    from oracle import oracle as O
+    os_ = [O.BqpOracle(P) for P in problems]
+    t0 = time.perf_counter()
+    its = [o.solve() for o in os_]
+    wall = time.perf_counter() - t0
+    return dict(wall_s=wall, iters=np.array(its), x=[o.vec("x") for o in os_], pcg=sum(o.scalar("total_pcg") for o in os_))
+
+
+def main_reference():
+    med = statistics.median
+    for w in WORKLOADS:
+        problems = problems_of(w)
+        sub = problems[:ORACLE_COUNT]
+        run_batch(problems[:2], "reference")                      # warm-up: library load, first launch of either order
+        run_batch(problems[:2])
+        rs, ds = [], []
+        for _ in range(REPEATS):
+            rs.append(run_batch(problems, "reference", keep=len(sub)))
+            ds.append(run_batch(problems, keep=0))
+        o = run_oracle(sub)
+        same = all(np.array_equal(a.view(np.uint64), b.view(np.uint64)) for a, b in zip(rs[-1]["x"], o["x"])) and \
+            np.array_equal(rs[-1]["iters"][:len(sub)], o["iters"])
+        r_wall, r_ker = med(r["wall_s"] for r in rs), med(r["kernel_ms"] for r in rs)
+        d_wall, d_ker = med(r["wall_s"] for r in ds), med(r["kernel_ms"] for r in ds)
+        ri, di = rs[-1]["iters"], ds[-1]["iters"]
+        scaled = o["wall_s"] * len(problems) / len(sub)
+        row = dict(workload=w, order="reference", shape=SHAPES[w], problems=len(problems), repeats=REPEATS, slots=int(rs[-1]["slots"]),
+                   window=int(rs[-1]["window"]), launches=int(rs[-1]["launches"]),
+                   iters_min=int(ri.min()), iters_max=int(ri.max()), iters_sum=int(ri.sum()), pcg_sum=int(rs[-1]["pcg"]), pcg_max=int(rs[-1]["pcg_max"]),
+                   batch_wall_s=round(r_wall, 4), batch_kernel_ms=round(r_ker, 2), batch_wall_s_all=[round(r["wall_s"], 4) for r in rs],
+                   us_per_iteration_slowest_problem=round(1e3 * r_ker / max(int(ri.max()), 1), 2),
+                   us_per_pcg_step_longest_problem=round(1e3 * r_ker / max(int(rs[-1]["pcg_max"]), 1), 2),
+                   default_iters_max=int(di.max()), default_iters_sum=int(di.sum()), default_pcg_sum=int(ds[-1]["pcg"]), default_pcg_max=int(ds[-1]["pcg_max"]),
+                   default_wall_s=round(d_wall, 4), default_kernel_ms=round(d_ker, 2), default_wall_s_all=[round(r["wall_s"], 4) for r in ds],
+                   default_us_per_iteration_slowest_problem=round(1e3 * d_ker / max(int(di.max()), 1), 2),
+                   default_us_per_pcg_step_longest_problem=round(1e3 * d_ker / max(int(ds[-1]["pcg_max"]), 1), 2),
+                   ratio_reference_to_default_kernel=round(r_ker / d_ker, 3), ratio_reference_to_default_wall=round(r_wall / d_wall, 3),
+                   oracle_problems=len(sub), oracle_wall_s=round(o["wall_s"], 4), oracle_iters_sum=int(o["iters"].sum()),
+                   oracle_us_per_iteration=round(1e6 * o["wall_s"] / max(int(o["iters"].sum()), 1), 2),
+                   oracle_wall_s_scaled_to_all=round(scaled, 4), oracle_scaled=len(sub) != len(problems),
+                   ratio_oracle_to_batch=round(scaled / r_wall, 2), same_bits_as_oracle=bool(same))
+        print(json.dumps(row), flush=True)
+        with open(OUT, "a") as f:
+            f.write(json.dumps(row) + "\n")
+
+
 def main():
+    if ORDER == "reference":
+        return main_reference()
     for w in WORKLOADS:
         problems = problems_of(w)
         sub = problems[:LOOP_COUNT]

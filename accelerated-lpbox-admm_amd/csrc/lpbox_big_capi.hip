@@ -479,6 +479,8 @@ static int big_set_problem(lpbox_big_t *h, long n_glob, int c0, int n_loc, int l
         if (valued && !h->ref)
             return lpbox_fail(LPBOX_E_UNSUPPORTED, "stored values of E other than 1 need the reference summation order: call lpbox_big_set_order(h, LPBOX_ORDER_REFERENCE) first");
     }
+    for (int j = 0; j < n_loc; j++)              // as lpbox_set_problem_lp: a non-finite objective entry never reaches the device
+        if (!std::isfinite(b[j])) return lpbox_fail(LPBOX_E_BADARG, "b has a non-finite entry (local index %d, global %ld)", j, (long)c0 + j);
     h->valued = valued;
     h->n_glob = n_glob; h->c0 = c0; h->n_loc = n_loc; h->l = l; h->nnz = nnz;
     h->cptr.assign(colptr, colptr + n_loc + 1); h->crow.assign(rowidx, rowidx + nnz);

@@ -347,6 +347,10 @@ int set_instance(lpbox_t *h, int idx, int n, int l, int nnz, const int *colptr, 
             }
         }
     }
+    // the objective vector: a NaN in b would run every x-update to the PCG cap for up to 2e4 outer iterations (the reference accepts it
+    // and computes garbage; a deliberate deviation).  Subnormals, zeros and either sign are ordinary values.
+    for (int j = 0; j < n; j++)
+        if (!std::isfinite(b[j])) return fail(LPBOX_E_BADARG, "b has a non-finite entry (index %d)", j);
     LpInstance &I = h->inst[idx];
     I.n = n; I.l = l; I.nnz = nnz;
     I.dir_g.clear();                  // lpbox_get_direct_rows may have answered for the problem that was here

@@ -64,7 +64,10 @@ void     lpbox_destroy(lpbox_t *h);
  * LPBOX_E_UNSUPPORTED.  After lpbox_set_order(h, LPBOX_ORDER_REFERENCE) any finite value is accepted (negative, zero and tiny ones
  * included: an explicit zero stays a stored entry, as in the reference's readSparseMat, LPcpp:2416-2444); a non-finite value ->
  * LPBOX_E_BADARG.  The same holds for the two file readers below, which negate the values for k == 2 and sum duplicate triplets as
- * the reference does.  Values that are all exactly 1.0 make a unit instance. */
+ * the reference does.  Values that are all exactly 1.0 make a unit instance.
+ * b may hold any FINITE values: either sign, zeros, subnormals, any scale whose squares do not overflow.  A NaN
+ * or an infinity in b -> LPBOX_E_BADARG with the index in lpbox_last_error(), here and in the two file readers, before any device
+ * call.  A deliberate deviation: the reference accepts such a vector and computes garbage (a NaN runs every x-update to the PCG cap). */
 int lpbox_set_problem_lp(lpbox_t *h, int idx, int n, int l, int nnz, const int *colptr, const int *rowidx,
                          const double *vals, const double *b, const double *f);
 /* LP pxd:9 `void readFile(int,int,int)` (LPcpp:2446-2545) with the two paths explicit; k as in the reference. */
@@ -330,6 +333,8 @@ int lpbox_big_set_stream(lpbox_big_t *h, void *hip_stream);
 int lpbox_big_set_allgather(lpbox_big_t *h, lpbox_allgather_fn fn, void *user);
 int lpbox_big_rccl_unique_id(void *out128);                    /* ncclGetUniqueId: 128 bytes, returns 128 */
 int lpbox_big_rccl_init(lpbox_big_t *h, const void *unique_id128);   /* ncclCommInitRank(world, id, rank) on the handle's device */
+/* b (this rank's n_loc entries, already negated) must be finite, as for lpbox_set_problem_lp: a NaN or an infinity is LPBOX_E_BADARG
+ * with the local and global index in lpbox_last_error(), from lpbox_big_set_problem and lpbox_big_set_problem_vals alike. */
 int lpbox_big_set_problem(lpbox_big_t *h, long n_glob, int c0, int n_loc, int l, const int *colptr, const int *rowidx,
                           const double *b, const double *f);
 /* OPT-IN: the reference's summation order on this path (lpbox_set_order's LPBOX_ORDER_REFERENCE beyond the on-chip limit; DESIGN.md

@@ -14,7 +14,10 @@ The subject must be within B(v) of the natural float64 member for x, z1, z2, z4 
 consistent with the restatement's recorded residualNorm2 / threshold: ratio[k-1] >= 1 - B and ratio[k] < 1 + B.  Quantities that do not
 depend on the iterate (rho*, prev_rho*, gamma, dI, rho4Et, rhoUpdated, sum_fix_obj, pd, f, b) are held to 1e-12 max(1, |v|); the ones
 computed from x (std_obj, cur_obj, best_bin_obj, obj_val, cvg1, cvg2) to B of their own ensemble spread; integers and index sets exactly.
-DESIGN.md section 22."""
+A scalar that is NaN in the natural float64 member AND in the subject (std_obj = 0 / 0 when the objective vector is zero) counts as
+agreement and is counted in Case.nan_agreed; a NaN on one side alone is a violation.  A call that returns 1 without a stop reason (the
+fix left a remainder of norm < 1e-3, LPcpp:1223) does not end a case: its window and the following ones are compared like any other.
+DESIGN.md sections 22 and 24."""
 import copy
 import os
 import sys
@@ -232,6 +235,7 @@ class Case:
         self.check_from = check_from           # steps before it drive the restatement but are compared by another test
         self.violations, self.done, self.first = [], False, True
         self.checked = self.weak = 0
+        self.nan_agreed = 0                    # scalars that were NaN in the restatement's natural member and in the subject alike
         self.pre, self.post = [0, 0], [0, 0]   # [checked, weak] before the first fix of this case's steps / after it
         self.worst = self.loo = 0.0            # subject / spread and leave-one-out member / spread of the others, largest seen
         self.hist = []                         # the subject's x after every l2f step since the last fix
@@ -243,7 +247,7 @@ class Case:
         assert np.array_equal(view.vec("x"), self.view.vec("x")) and view.totals() == self.view.totals(), "fork: the subjects differ"
         c = copy.copy(self)
         c.members, c.hist, c.view, c.tag = copy.deepcopy(self.members), list(self.hist), view, tag
-        c.violations, c.checked, c.weak, c.worst, c.loo, c.pre, c.post = [], 0, 0, 0.0, 0.0, [0, 0], [0, 0]
+        c.violations, c.checked, c.weak, c.worst, c.loo, c.pre, c.post, c.nan_agreed = [], 0, 0, 0.0, 0.0, [0, 0], [0, 0], 0
         return c
 
     def bad(self, it, msg):
@@ -293,7 +297,8 @@ class Case:
             ok = False
         if nat.stop is not None:
             self.stop_at = (a + max(ran - 1, 0), nat.stop)
-        if not ok or nat.n == 0 or ret or nat.ret:
+        # ret = 1 without a stop reason is the return after a fix that left a remainder of almost zero norm (LPcpp:1223): the window goes on
+        if not ok or nat.n == 0 or ((ret or nat.ret) and nat.stop is not None):
             self.done = True
         if not ok or nat.n == 0 or ran == 0:
             return
@@ -333,6 +338,9 @@ class Case:
                 continue
             A = np.array([float(getattr(m, _ATTR.get(name, name))) for m in ms])
             B = _floor(A[:1]) + (c * (A.max() - A.min()) if name in ITERATE_SCALARS else 0.0)
+            if np.isnan(A[0]) and np.isnan(got):   # 0/0 on both sides (std_obj with an objective of zero); a NaN on one side alone stays a violation
+                self.nan_agreed += 1
+                continue
             if not abs(got - A[0]) <= B:
                 self.bad(it, f"{name}: subject {got!r}, restatement {A[0]!r}, B = {B:.3e}")
         # ---- the PCG exit: the subject's count against the restatement's residuals ----

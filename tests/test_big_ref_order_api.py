@@ -99,6 +99,33 @@ def test_stored_values(L):
     L.lpbox_big_destroy(h)
 
 
+def test_non_finite_objective_entry_is_a_bad_argument(L):
+    """b is checked on the host like the stored values, by both entry points and in both orders; a subnormal, a
+    zero and 1e300 are values like any other."""
+    n, l, cp, ri, b = tiny()
+    ones = np.ones(4)
+    for order in (0, 1):
+        for bad in (np.nan, np.inf, -np.inf):
+            for with_vals in (False, True):
+                h = create(L)
+                assert L.lpbox_big_set_order(h, order) == 0
+                v = b.copy()
+                v[1] = bad
+                # a shard that starts at global column 5 of 9: the message carries both indices
+                rc = (L.lpbox_big_set_problem_vals(h, 9, 5, n, l, cp, ri, v, None, ones.ctypes.data_as(C.c_void_p)) if with_vals
+                      else L.lpbox_big_set_problem(h, 9, 5, n, l, cp, ri, v, None))
+                assert rc == E_BADARG, (order, bad, with_vals)
+                msg = L.lpbox_last_error()
+                assert b"local index 1" in msg and b"global 6" in msg, msg
+                ok = np.array([-1e-310, 0.0, 1e300])
+                assert L.lpbox_big_set_problem(h, n, 0, n, l, cp, ri, ok, None) == 0       # the refused call left the handle usable
+                L.lpbox_big_destroy(h)
+        h = create(L)
+        assert L.lpbox_big_set_order(h, order) == 0
+        assert L.lpbox_big_set_problem_vals(h, n, 0, n, l, cp, ri, np.array([5e-324, -0.0, -1e300]), None, ones.ctypes.data_as(C.c_void_p)) == 0
+        L.lpbox_big_destroy(h)
+
+
 def test_dropin_class_keeps_the_refusal_by_default():
     from lpbox_hip.lp import PyLPboxADMMsolver
     s = PyLPboxADMMsolver(0)

@@ -36,6 +36,7 @@ def run_batch(insts, tags, order=None, x_update="pcg", slots=None, ceiling=None)
     S.run_cases(g, cases, STEPS)
     report(cases, ceiling)
     b.close()
+    return cases
 
 
 def run_big(P, tag, ceiling=None, **kw):

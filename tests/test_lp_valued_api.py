@@ -64,6 +64,46 @@ def test_non_finite_value_is_a_bad_argument():
             assert e.value.code == -2, (order, bad)            # LPBOX_E_BADARG
 
 
+def test_non_finite_objective_entry_is_a_bad_argument(tmp_path):
+    """b is checked on the host like vals: NaN and either infinity are refused with the index, before any device
+    call, by lpbox_set_problem_lp and by both file readers; a subnormal, a zero and 1e300 are values like any other."""
+    from lpbox_hip.lp import LpBatch, LpboxError
+    I = lp_instances("lp_20_60_seed0.npz")[0]
+    pc, pb, _, _, _ = oracle_read(3)
+    price = np.loadtxt(pb)
+    d = tmp_path / "instance" / "3_7"
+    d.mkdir(parents=True)
+    (d / "instance_1_C.txt").write_text(open(pc).read())
+    for order in ("default", "reference"):
+        for bad in (np.nan, np.inf, -np.inf):
+            b = LpBatch(batch=1, order=order)
+            v = I["b"].copy()
+            v[17] = bad
+            with pytest.raises(LpboxError, match=r"index 17\b") as e:
+                b.set_problem(0, I["n"], I["l"], I["colptr"], I["rowidx"], v)
+            assert e.value.code == -2, (order, bad)            # LPBOX_E_BADARG
+            b.set_problem(0, I["n"], I["l"], I["colptr"], I["rowidx"], I["b"])         # the refused call left the handle usable
+            p = price.copy()
+            p[2] = bad
+            (d / "instance_1_b.txt").write_text("".join("%r\n" % float(x) for x in p))
+            b = LpBatch(batch=1, order="reference")            # the fixture stores values other than 1
+            for call in (lambda: b.read_files(0, pc, str(d / "instance_1_b.txt"), 3), lambda: b.read_file(0, 1, 3, 7, str(tmp_path))):
+                with pytest.raises(LpboxError, match=r"index 2\b") as e:
+                    call()
+                assert e.value.code == -2, (order, bad)
+        b = LpBatch(batch=1, order=order)
+        v = I["b"].copy()
+        v[:6] = [5e-324, -1e-310, 0.0, -0.0, 1e300, -1e300]
+        b.set_problem(0, I["n"], I["l"], I["colptr"], I["rowidx"], v)
+        assert bits_equal(b.get_problem(0)["b"], v)
+    p = price.copy()
+    p[:4] = [1e-310, 0.0, 1e300, 5e-324]
+    (d / "instance_1_b.txt").write_text("".join("%r\n" % float(x) for x in p))
+    b = LpBatch(batch=1, order="reference")
+    b.read_file(0, 1, 3, 7, str(tmp_path))
+    assert bits_equal(b.get_problem(0)["b"], -p)
+
+
 def test_all_ones_is_a_unit_instance():
     from lpbox_hip.lp import LpBatch
     I = lp_instances("lp_20_60_seed0.npz")[0]

@@ -1,10 +1,12 @@
 // lpbox_big_capi.hip -- host side + C-ABI of the LARGE-instance LP path (lpbox_big_* in include/lpbox_hip.h):
 // one LP, variable-sharded over ranks (one process per GPU).  The library launches the kernels; where the algorithm needs a
 // sum over all variables it calls the caller-supplied all-reduce (RCCL through torch.distributed in lpbox_hip/big.py) on
-// the same HIP stream.  With one rank no collective is issued.
+// the same HIP stream.  With one rank no collective is issued.  The host loop of the launch chain is chain_run of lpbox_host.h with the
+// rules of lpbox_chain.h (CHAIN_RULES_BIG); the graph cache, the device buffer, the timer and the error-check macros are there too.
 #include "../../include/lpbox_hip.h"
 #include "lpbox_big.h"
 #include "lpbox_capi_internal.h"
+#include "lpbox_host.h"
 
 #include <rccl/rccl.h>     // types only: the library is dlopen'ed (no link dependency; a process that has torch loaded shares torch's copy)
 #include <dlfcn.h>
@@ -12,23 +14,11 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <map>
-#include <utility>
 #include <vector>
 
-#define HIPCHK(expr)                                                                                         \
-    do {                                                                                                     \
-        hipError_t e_ = (expr);                                                                              \
-        if (e_ != hipSuccess) return lpbox_fail(LPBOX_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
 namespace {
-template <typename Tp>
-struct Buf {
-    Tp *p = nullptr; size_t count = 0;
-    hipError_t alloc(size_t c) { release(); count = c; return c ? hipMalloc((void **)&p, c * sizeof(Tp)) : hipSuccess; }
-    void release() { if (p) (void)hipFree(p); p = nullptr; count = 0; }
-};
+static_assert(BIG_HALT_NONE == CHAIN_HALT_NONE && BIG_HALT_PCG_MORE == CHAIN_HALT_PCG_MORE, "lpbox_chain.h reads BigState::halt");
+static_assert(CHAIN_RULES_BIG.pcg_cap == LP_PCG_MAXITERS, "the resume limit follows the PCG cap of the kernels");
 // RCCL entry points, resolved at run time
 struct RcclApi {
     void *lib = nullptr;
@@ -72,40 +62,38 @@ struct lpbox_big {
     std::vector<double> b, f;
     bool has_problem = false, uploaded = false, inited = false, own_stream = false;
     hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    StreamTimer timer;
     lpbox_allgather_fn ag = nullptr; void *ag_user = nullptr;   // exchange through the caller (tests: gloo) ...
     ncclComm_t comm = nullptr;                                  // ... or through RCCL, driven from here (no Python in the loop)
     long q_cap = 0;                                             // doubles allocated behind q (l rounded up to a multiple of world)
-    // launch-bound inner loop: BIG_ITERS_PER_GRAPH outer iterations captured once per (PCG launch count, start parity) and replayed
-    std::map<std::pair<int, int>, hipGraphExec_t> gexec; std::vector<hipGraph_t> graphs;
-    long long graph_launches = 0, graph_collectives = 0;       // of ONE replay (measured while capturing)
+    // launch-bound inner loop: two outer iterations captured once per (PCG launch count, start parity) and replayed
+    GraphCache graphs;
     bool use_graph = true;
-    int G = 0, Gl = 0, EPT = 2, EPTl = 2, P = 1, Glr = 0, kmax = 28, parity = 0;
+    ChainController chain{CHAIN_RULES_BIG};                     // kmax; margin: LPBOX_BIG_KMARGIN
+    int G = 0, Gl = 0, EPT = 2, EPTl = 2, P = 1, Glr = 0, parity = 0;
     bool fold = false; int Gs = 0, Gr[BIG_MAXW] = {0};        // folded reductions (BigDev::fold): partial stride, workgroups of every rank
-    Buf<double> gpart;                                          // W > 1, folded: the gathered partials [phase][rank][nv][Gs]
+    DevBuf<double> gpart;                                          // W > 1, folded: the gathered partials [phase][rank][nv][Gs]
     bool lean = false;                                          // lpbox_big_set_pcg_mode(LPBOX_PCG_COMM_LEAN), before lpbox_big_init
     int Gq = 0, Gqs = 0, Gqr[BIG_MAXW] = {0};                   // q.q partials: of this rank, stride, of every rank (BigDev::Gq)
-    Buf<double> lsmall, gsmall;
-    bool adaptive = true;
-    int kmargin = 1;                                            // spare PCG launch groups beyond the largest count of the previous batch (LPBOX_BIG_KMARGIN)
+    DevBuf<double> lsmall, gsmall;
     double kernel_ms = 0.0; long long launches = 0, collectives = 0;
-    Buf<int> d_rptr, d_rcol, d_cptr, d_crow;
-    Buf<double> x, y1, y2, z1, z2, db, pd, dinv, rhs, r, z, tmp, p0, p1, gsrc, y3, z4, df, Ex, q, part, red, xt, xhist, xi_out, gath, flag;
-    Buf<uint8_t> live, newfix;
-    Buf<double2> zp, fz;
-    Buf<int> d_live_idx;
+    DevBuf<int> d_rptr, d_rcol, d_cptr, d_crow;
+    DevBuf<double> x, y1, y2, z1, z2, db, pd, dinv, rhs, r, z, tmp, p0, p1, gsrc, y3, z4, df, Ex, q, part, red, xt, xhist, xi_out, gath, flag;
+    DevBuf<uint8_t> live, newfix;
+    DevBuf<double2> zp, fz;
+    DevBuf<int> d_live_idx;
     std::vector<int> left_idx, xi_left;   // local indices of the live variables (now / as of the last l2f window)
     long n_live_glob = 0;                 // live variables over all ranks
     int ws_cap = 0, xi_rows = 0;
     bool xi_valid = false;
     bool record = false, xi_plain = false;   // lpbox_big_set_record: the plain loop stages every iterate; the last staged window came from it
-    Buf<BigState> st;
+    DevBuf<BigState> st;
     BigState hst;
     // reference-order mode (lpbox_big_set_order): one rank, one column slice, no folded reductions; see BigRef in lpbox_big.h
     bool ref = false, valued = false;
     std::vector<double> vals, vcsr_h;     // stored values of E in the order of crow / rcol (empty: a unit instance)
-    Buf<double> d_vcsc, d_vcsr, r4v, stage;
-    Buf<int> d_rank, d_frank, d_cnt;
+    DevBuf<double> d_vcsc, d_vcsr, r4v, stage;
+    DevBuf<int> d_rank, d_frank, d_cnt;
 
     BigRef rf() const {
         BigRef r;
@@ -130,13 +118,6 @@ struct lpbox_big {
 };
 
 namespace {
-
-int use_device(lpbox_big *h) {
-    int cnt = 0;
-    if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) return lpbox_fail(LPBOX_E_NODEVICE, "no HIP device available");
-    HIPCHK(hipSetDevice(h->device));
-    return LPBOX_OK;
-}
 
 // In-place sum of `count` doubles at ptr over all ranks with a FIXED association: element i = ((c0[i] + c1[i]) + c2[i]) + ...
 // in rank order, whatever the transport -- so a W-rank run is reproducible and comparable bit for bit with the oracle's model of
@@ -187,7 +168,6 @@ int agree_ok(lpbox_big *h, bool ok_here) {
     return tot == 0.0 ? LPBOX_OK : -1;
 }
 
-#define CHK(expr) do { int rc_ = (expr); if (rc_ < 0) return rc_; } while (0)
 // c1 = pow(n, 1/p), p = 2 (LPcpp:427,503) through libm's pow, as the reference and the oracle call it: with the literal exponent the
 // compiler turns the call into sqrt, and glibc's pow is not correctly rounded (n = 2921: one ulp apart).  Reference order only; the
 // default order keeps the expression it has always had.
@@ -290,7 +270,7 @@ int enqueue_iteration(lpbox_big *h, const BigDev &d) {
     ROWS(0);
     HIPCHK(KL(resid, &h->parity, h->stream)); h->launches++;
     FIN(3, BIG_PH_B);
-    CHK(enqueue_pcg(h, d, h->kmax));
+    CHK(enqueue_pcg(h, d, h->chain.kmax));
     return enqueue_tail(h, d);
 }
 
@@ -301,34 +281,20 @@ int read_state(lpbox_big *h) {
 }
 
 // An outer iteration is 8 + 3*kmax launches that flip the state ping-pong, so two iterations return to the parity they started
-// from: one hipGraph = BIG_ITERS_PER_GRAPH iterations per (kmax, start parity).  The caller's all-gather callback cannot be
+// from: chain_run captures one hipGraph of two iterations per (kmax, start parity).  The caller's all-gather callback cannot be
 // captured (it runs host code at enqueue time); RCCL operations and the single-rank chain can.
-constexpr int BIG_ITERS_PER_GRAPH = 2;
-int ensure_graph(lpbox_big *h, const BigDev &d, hipGraphExec_t *out) {
-    const auto key = std::make_pair(h->kmax, h->parity);
-    auto it = h->gexec.find(key);
-    if (it != h->gexec.end()) { *out = it->second; return LPBOX_OK; }
-    const int par0 = h->parity;
-    const long long l0 = h->launches, c0 = h->collectives;
-    hipGraph_t g = nullptr;
-    HIPCHK(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-    int rc = LPBOX_OK;
-    for (int i = 0; i < BIG_ITERS_PER_GRAPH && rc >= 0; i++) rc = enqueue_iteration(h, d);
-    const hipError_t e2 = hipStreamEndCapture(h->stream, &g);
-    h->graph_launches = h->launches - l0; h->graph_collectives = h->collectives - c0;
-    h->launches = l0; h->collectives = c0;
-    if (rc < 0 || e2 != hipSuccess || h->parity != par0) {
-        h->parity = par0;
-        if (g) (void)hipGraphDestroy(g);
-        return rc < 0 ? rc : lpbox_fail(LPBOX_E_HIP, "graph capture failed: %s", hipGetErrorString(e2));
+struct BigChainOps {
+    lpbox_big *h; const BigDev &d;
+    int read_state(ChainView &v) { CHK(::read_state(h)); v = chain_view(h->hst); return LPBOX_OK; }
+    int resume_pcg() {
+        HIPCHK(big_launch_resume(d, 0, &h->parity, h->stream));
+        CHK(enqueue_pcg(h, d, CHAIN_PAIRS_PER_RESUME));
+        return enqueue_tail(h, d);
     }
-    hipGraphExec_t ex = nullptr;
-    HIPCHK(hipGraphInstantiate(&ex, g, nullptr, nullptr, 0));
-    h->graphs.push_back(g);
-    h->gexec[key] = ex;
-    *out = ex;
-    return LPBOX_OK;
-}
+    int batch_head() { HIPCHK(big_launch_resume(d, 1, &h->parity, h->stream)); return LPBOX_OK; }
+    int enqueue(int n) { for (int it = 0; it < n; it++) CHK(enqueue_iteration(h, d)); return LPBOX_OK; }
+    int finalize() { HIPCHK(KL(prep, 0, &h->parity, h->stream)); h->launches++; return LPBOX_OK; }
+};
 
 }  // namespace
 
@@ -340,7 +306,7 @@ lpbox_big_t *lpbox_big_create(int rank, int world, int device) {
     h->rank = rank; h->world = world; h->device = device;
     memset(&h->hst, 0, sizeof(h->hst));
     if (getenv("LPBOX_BIG_NOGRAPH")) h->use_graph = false;                        // eager launches (profilers that dislike graphs)
-    if (const char *e = getenv("LPBOX_BIG_KMAX")) { int v = atoi(e); if (v >= 1 && v <= 1000) { h->kmax = v; h->adaptive = false; } }
+    if (const char *e = getenv("LPBOX_BIG_KMAX")) { int v = atoi(e); if (v >= 1 && v <= 1000) h->chain.force_kmax(v); }
     return h;
 }
 
@@ -348,18 +314,9 @@ void lpbox_big_destroy(lpbox_big_t *h) {
     if (!h) return;
     if (h->uploaded) (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    h->d_rptr.release(); h->d_rcol.release(); h->d_cptr.release(); h->d_crow.release();
-    for (Buf<double> *bp : {&h->x, &h->y1, &h->y2, &h->z1, &h->z2, &h->db, &h->pd, &h->dinv, &h->rhs, &h->r, &h->z, &h->tmp, &h->p0, &h->p1,
-                            &h->gsrc, &h->y3, &h->z4, &h->df, &h->Ex, &h->q, &h->part, &h->red, &h->xt, &h->xhist, &h->xi_out, &h->gath, &h->flag, &h->gpart, &h->lsmall, &h->gsmall})
-        bp->release();
-    for (auto &kv : h->gexec) (void)hipGraphExecDestroy(kv.second);
-    for (hipGraph_t g : h->graphs) (void)hipGraphDestroy(g);
+    h->graphs.clear();
     if (h->comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(h->comm);
-    for (Buf<double> *bp : {&h->d_vcsc, &h->d_vcsr, &h->r4v, &h->stage}) bp->release();
-    h->d_rank.release(); h->d_frank.release(); h->d_cnt.release();
-    h->st.release(); h->live.release(); h->newfix.release(); h->d_live_idx.release(); h->zp.release(); h->fz.release();
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
+    h->timer.destroy();
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
@@ -418,7 +375,7 @@ int lpbox_big_rccl_init(lpbox_big_t *h, const void *unique_id128) {
     if (h->inited) return lpbox_fail(LPBOX_E_STATE, "the communicator must be created before solve_init");
     int rc = rccl_load();
     if (rc < 0) return rc;
-    rc = use_device(h);
+    rc = use_device(h->device);
     if (rc < 0) return rc;
     ncclUniqueId id;
     memcpy(&id, unique_id128, sizeof(id));
@@ -524,7 +481,7 @@ int lpbox_big_init(lpbox_big_t *h) {
     if (!h->has_problem) return lpbox_fail(LPBOX_E_STATE, "no problem set");
     if (h->ref && (h->world != 1 || h->comm || h->ag || h->lean))
         return lpbox_fail(LPBOX_E_UNSUPPORTED, "the reference summation order runs on one rank, without a transport and with the reference's PCG");
-    CHK(use_device(h));
+    CHK(use_device(h->device));
     if (!h->uploaded) {
         const int n = h->n_loc, l = h->l;
         if (!h->stream) { HIPCHK(hipStreamCreate(&h->stream)); h->own_stream = true; }
@@ -557,14 +514,14 @@ int lpbox_big_init(lpbox_big_t *h) {
         for (int r = 0; r < BIG_MAXW; r++) h->Gr[r] = r < h->world ? groups((long)nloc_all[r], h->EPT) : 0;
         h->EPTl = 2; h->Gl = (l + BIG_T * h->EPTl - 1) / (BIG_T * h->EPTl);
         h->Glr = (l + BIG_T - 1) / BIG_T;
-        if (const char *e = getenv("LPBOX_BIG_KMARGIN")) h->kmargin = std::max(0, atoi(e));
-        HIPCHK(hipEventCreate(&h->ev0)); HIPCHK(hipEventCreate(&h->ev1));
+        if (const char *e = getenv("LPBOX_BIG_KMARGIN")) h->chain.rules.margin = std::max(0, atoi(e));
+        HIPCHK(h->timer.create());
         HIPCHK(h->d_rptr.alloc((size_t)h->P * l + 1)); HIPCHK(h->d_rcol.alloc(h->nnz)); HIPCHK(h->d_cptr.alloc((size_t)n + 1)); HIPCHK(h->d_crow.alloc(h->nnz));
-        for (Buf<double> *bp : {&h->x, &h->y1, &h->y2, &h->z1, &h->z2, &h->db, &h->pd, &h->dinv, &h->rhs, &h->r, &h->z, &h->tmp, &h->p0, &h->p1, &h->gsrc, &h->xt})
+        for (DevBuf<double> *bp : {&h->x, &h->y1, &h->y2, &h->z1, &h->z2, &h->db, &h->pd, &h->dinv, &h->rhs, &h->r, &h->z, &h->tmp, &h->p0, &h->p1, &h->gsrc, &h->xt})
             HIPCHK(bp->alloc(n));
         HIPCHK(h->live.alloc(n)); HIPCHK(h->newfix.alloc(n)); HIPCHK(h->d_live_idx.alloc(n)); HIPCHK(h->zp.alloc(n));
         HIPCHK(hipMemset(h->newfix.p, 0, (size_t)n));
-        for (Buf<double> *bp : {&h->y3, &h->z4, &h->df, &h->Ex}) HIPCHK(bp->alloc(l));
+        for (DevBuf<double> *bp : {&h->y3, &h->z4, &h->df, &h->Ex}) HIPCHK(bp->alloc(l));
         HIPCHK(h->fz.alloc(l));
         HIPCHK(h->q.alloc((size_t)h->q_cap)); HIPCHK(hipMemset(h->q.p, 0, sizeof(double) * (size_t)h->q_cap));
         HIPCHK(h->part.alloc((size_t)BIG_PH_COUNT * BIG_NPART * h->Gs)); HIPCHK(h->red.alloc(BIG_PH_COUNT * BIG_NPART)); HIPCHK(h->st.alloc(2));
@@ -630,41 +587,10 @@ int lpbox_big_init(lpbox_big_t *h) {
 }
 
 static int run_window(lpbox_big *h, const BigDev &d, int iter_end) {
-    HIPCHK(hipEventRecord(h->ev0, h->stream));
-    for (;;) {
-        CHK(read_state(h));
-        if (h->hst.halt == BIG_HALT_PCG_MORE) {
-            HIPCHK(big_launch_resume(d, 0, &h->parity, h->stream));
-            CHK(enqueue_pcg(h, d, 16));
-            CHK(enqueue_tail(h, d));
-            if (h->adaptive) h->kmax = std::max(h->kmax, h->hst.pcg_k + 8);
-            continue;
-        }
-        if (h->hst.halt != BIG_HALT_NONE) break;
-        const int remaining = iter_end - h->hst.iter;
-        if (remaining <= 0 && !h->hst.have_prev) break;
-        if (h->adaptive && h->hst.outer_total > 0) h->kmax = std::max(4, h->hst.pcg_max + h->kmargin);
-        HIPCHK(big_launch_resume(d, 1, &h->parity, h->stream));
-        int batch = std::min(std::max(remaining, 0), 16);
-        if (h->use_graph && !h->ag && batch >= BIG_ITERS_PER_GRAPH) {
-            hipGraphExec_t ex = nullptr;
-            if (ensure_graph(h, d, &ex) < 0) {          // a transport that cannot be captured: go on with eager launches for good
-                h->use_graph = false;
-                (void)hipGetLastError();
-            } else {
-                for (; batch >= BIG_ITERS_PER_GRAPH; batch -= BIG_ITERS_PER_GRAPH) {
-                    HIPCHK(hipGraphLaunch(ex, h->stream));
-                    h->launches += h->graph_launches; h->collectives += h->graph_collectives;
-                }
-            }
-        }
-        for (int it = 0; it < batch; it++) CHK(enqueue_iteration(h, d));
-        HIPCHK(KL(prep, 0, &h->parity, h->stream)); h->launches++;          // finalise the last iteration of the batch
-    }
-    HIPCHK(hipEventRecord(h->ev1, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+    HIPCHK(h->timer.start(h->stream));
+    CHK(chain_run(h->chain, h->graphs, ChainIo{h->stream, h->parity, h->launches, h->collectives, h->use_graph, !h->ag}, iter_end, BigChainOps{h, d}));
+    double ms = 0.0;
+    HIPCHK(h->timer.stop_sync(h->stream, &ms));
     h->kernel_ms += ms;
     return LPBOX_OK;
 }
@@ -672,7 +598,7 @@ static int run_window(lpbox_big *h, const BigDev &d, int iter_end) {
 int lpbox_big_iterate(lpbox_big_t *h, int iter_start, int iter_end, int *ret) {     // ADMM_lp_iters LPcpp:766-1095
     if (!h) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
     if (!h->inited) return lpbox_fail(LPBOX_E_STATE, "solve_init has not been called");
-    CHK(use_device(h));
+    CHK(use_device(h->device));
     const int ws = iter_end - iter_start;
     const bool rec = h->record && ws > 0;
     if (rec) {
@@ -681,8 +607,7 @@ int lpbox_big_iterate(lpbox_big_t *h, int iter_start, int iter_end, int *ret) { 
         if (h->ws_cap < ws || !h->xhist.p) {
             HIPCHK(hipStreamSynchronize(h->stream));
             HIPCHK(h->xhist.alloc((size_t)ws * h->n_loc));
-            for (auto &kv : h->gexec) (void)hipGraphExecDestroy(kv.second);         // the captured launches carry the old buffer
-            h->gexec.clear();
+            h->graphs.clear();                                                      // the captured launches carry the old buffer
             h->ws_cap = ws;
         }
         HIPCHK(hipMemsetAsync(h->xhist.p, 0, sizeof(double) * (size_t)h->ws_cap * h->n_loc, h->stream));
@@ -705,7 +630,7 @@ int lpbox_big_iterate_l2f(lpbox_big_t *h, int iter_start, int iter_end, const do
     const int ws = iter_end - iter_start;
     if (ws > LP_XITERS_COLS) return lpbox_fail(LPBOX_E_BADARG, "window of %d iterations exceeds the %d columns of x_iters (LPcpp:1113)", ws, LP_XITERS_COLS);
     if (num_global < 0 || num_global > h->n_live_glob) return lpbox_fail(LPBOX_E_BADARG, "fix count %ld outside [0,%ld]", num_global, h->n_live_glob);
-    CHK(use_device(h));
+    CHK(use_device(h->device));
     const int n_live_loc = (int)h->left_idx.size();
     std::vector<uint8_t> nf;
     std::vector<int> keep;
@@ -730,8 +655,7 @@ int lpbox_big_iterate_l2f(lpbox_big_t *h, int iter_start, int iter_end, const do
     if (ws > 0 && (h->ws_cap < ws || !h->xhist.p)) {
         HIPCHK(hipStreamSynchronize(h->stream));
         HIPCHK(h->xhist.alloc((size_t)ws * h->n_loc));
-        for (auto &kv : h->gexec) (void)hipGraphExecDestroy(kv.second);         // the captured launches carry the old window buffer
-        h->gexec.clear();
+        h->graphs.clear();                                                      // the captured launches carry the old window buffer
         h->ws_cap = ws;
     }
     const BigDev d = h->dev();
@@ -782,7 +706,7 @@ int lpbox_big_get_x_iters_device(lpbox_big_t *h, int ws, void **dev_ptr, int *ro
     if (!h->xi_valid) return lpbox_fail(LPBOX_E_STATE, "solve_iter_l2f has not been called");
     const int ws_max = h->xi_plain ? h->ws_cap : LP_XITERS_COLS;                 // a recorded plain call may be longer than an l2f window
     if (ws <= 0 || ws > ws_max) return lpbox_fail(LPBOX_E_BADARG, "ws = %d outside (0,%d]", ws, ws_max);
-    CHK(use_device(h));
+    CHK(use_device(h->device));
     const size_t need = (size_t)std::max(h->xi_rows, 1) * ws;
     if (h->xi_out.count < need) { HIPCHK(hipStreamSynchronize(h->stream)); HIPCHK(h->xi_out.alloc(need)); }
     HIPCHK(big_launch_pack_xiters(h->dev(), h->d_live_idx.p, h->xi_rows, ws, h->xi_out.p, h->stream));
@@ -803,7 +727,7 @@ int lpbox_big_get_x_iters(lpbox_big_t *h, int ws, double *out) {
 // binary solution of this rank's variables: fixed ones at their value, live ones rounded (get_x_sol, LPcpp:1648-1666)
 int lpbox_big_get_x_sol(lpbox_big_t *h, double *out_local) {
     if (!h || !h->inited || !out_local) return lpbox_fail(LPBOX_E_STATE, "not initialised");
-    CHK(use_device(h));
+    CHK(use_device(h->device));
     std::vector<uint8_t> lv(h->n_loc);
     HIPCHK(hipMemcpy(out_local, h->x.p, sizeof(double) * (size_t)h->n_loc, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(lv.data(), h->live.p, (size_t)h->n_loc, hipMemcpyDeviceToHost));
@@ -819,14 +743,14 @@ int lpbox_big_cal_obj(lpbox_big_t *h, double *out) {                            
 
 int lpbox_big_get_x(lpbox_big_t *h, double *out_local) {
     if (!h || !h->inited || !out_local) return lpbox_fail(LPBOX_E_STATE, "not initialised");
-    CHK(use_device(h));
+    CHK(use_device(h->device));
     HIPCHK(hipMemcpy(out_local, h->x.p, sizeof(double) * (size_t)h->n_loc, hipMemcpyDeviceToHost));
     return h->n_loc;
 }
 
 int lpbox_big_get_vec(lpbox_big_t *h, const char *name, double *out, long cap) {
     if (!h || !h->inited || !out || !name) return lpbox_fail(LPBOX_E_STATE, "not initialised");
-    CHK(use_device(h));
+    CHK(use_device(h->device));
     const double *src = nullptr; long len = h->n_loc;
     if (!strcmp(name, "x")) src = h->x.p; else if (!strcmp(name, "z1")) src = h->z1.p; else if (!strcmp(name, "z2")) src = h->z2.p;
     else if (!strcmp(name, "pd")) src = h->pd.p; else if (!strcmp(name, "b")) src = h->db.p;
@@ -858,7 +782,7 @@ int lpbox_big_get_vec(lpbox_big_t *h, const char *name, double *out, long cap) {
 int lpbox_big_check_infeasible(lpbox_big_t *h, int which) {
     if (!h || !h->inited) return lpbox_fail(LPBOX_E_STATE, "not initialised");
     if (h->world != 1) return lpbox_fail(LPBOX_E_UNSUPPORTED, "the infeasibility counts need every column: one rank only");
-    CHK(use_device(h));
+    CHK(use_device(h->device));
     const int n = h->n_loc, l = h->l;
     std::vector<double> v(n);
     std::vector<uint8_t> live(n, 1);
@@ -891,7 +815,8 @@ int lpbox_big_get_scalar(lpbox_big_t *h, const char *name, double *out) {
         {"cur_obj", s.cur_obj}, {"best_bin_obj", s.best_bin_obj}, {"cvg1", s.cvg1}, {"cvg2", s.cvg2}, {"obj_val", s.obj_val},
         {"iter", (double)s.iter}, {"outer_total", (double)s.outer_total}, {"pcg_total", (double)s.pcg_total}, {"last_pcg", (double)s.last_pcg},
         {"sum_fix_obj", s.sum_fix_obj}, {"fix_obj", s.fix_obj}, {"c1", s.c1}, {"ret", (double)s.ret}, {"n_live", (double)h->n_live_glob},
-        {"stop", (double)s.stop}, {"plain_iter_p1", (double)s.plain_iter_p1}, {"kmax", (double)h->kmax},
+        {"stop", (double)s.stop}, {"plain_iter_p1", (double)s.plain_iter_p1}, {"kmax", (double)h->chain.kmax}, {"pcg_resumes", (double)h->chain.pcg_resumes}, {"kmax_kept", (double)h->chain.kept},
+        {"graph_revisits", (double)h->graphs.revisits},
         {"launches", (double)h->launches}, {"collectives", (double)h->collectives}, {"kernel_ms", h->kernel_ms},
         {"threads", (double)BIG_T}, {"chunk", (double)(BIG_T * h->EPT)}, {"groups", (double)h->G}, {"row_slices", (double)h->P}, {"folded_reductions", h->fold ? 1.0 : 0.0}, {"pcg_comm_lean", h->lean ? 1.0 : 0.0},
         {"row_chunk", (double)((h->world > 1 || h->comm) ? BIG_T : (h->P > 1 ? BIG_T : BIG_T * h->EPTl))},

@@ -1,6 +1,7 @@
 // lpbox_capi.hip -- the C-ABI of liblpbox_hip.so (include/lpbox_hip.h): handle management, host-side index
 // bookkeeping of early fixing, instance readers and result getters.  All solver arithmetic runs in the HIP kernels of
-// lpbox_lp_kernels.hip; there is no CPU fallback.
+// lpbox_lp_kernels.hip; there is no CPU fallback.  The error-check macros, use_device, the device buffer and the stream timer are those of
+// lpbox_host.h, shared with the other host files.
 //
 // Reference citations: LPcpp = LinerProgramming/LinearProgramming/cython_solver/LPboxADMMsolver.cpp,
 //                      LPh   = .../cython_solver/LPboxADMMsolver.h, pxd = .../cython_solver/LPboxADMMsolver.pxd
@@ -8,6 +9,7 @@
 #include "lpbox_lp.h"
 #include "lpbox_lp_layout.h"
 #include "lpbox_capi_internal.h"
+#include "lpbox_host.h"
 #include "lpbox_policy.h"
 
 #include <algorithm>
@@ -24,16 +26,6 @@ thread_local std::string g_err;
 thread_local int g_device = 0;
 thread_local int g_status = 0;        // the code that came with g_err
 
-int fail(int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_err = buf; g_status = code;
-    return code;
-}
-
 }  // namespace
 
 int lpbox_fail(int code, const char *fmt, ...) {
@@ -47,12 +39,6 @@ int lpbox_fail(int code, const char *fmt, ...) {
 }
 
 namespace {
-
-#define HIPCHK(expr)                                                                                   \
-    do {                                                                                               \
-        hipError_t e_ = (expr);                                                                        \
-        if (e_ != hipSuccess) return fail(LPBOX_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
 
 struct LpInstance {
     int n = 0, l = 0, nnz = 0;
@@ -68,22 +54,6 @@ struct LpInstance {
     std::vector<int> xi_left_idx;      // live map at the time of the last l2f call (rows of x_iters)
     int xi_rows = 0;
     bool set = false;
-};
-
-template <typename Tp>
-struct DevBuf {
-    Tp *p = nullptr;
-    size_t count = 0;
-    hipError_t alloc(size_t c) {
-        release();
-        count = c;
-        if (c == 0) return hipSuccess;
-        return hipMalloc((void **)&p, c * sizeof(Tp));
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr; count = 0;
-    }
 };
 
 }  // namespace
@@ -104,7 +74,7 @@ struct lpbox_solver {
     size_t lds = 0, lds_direct = 0;
     bool log_on = false; int log_rows = 0; DevBuf<double> logbuf; int log_cap = 0;   // lpbox_set_log: records of the last plain call
     hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    StreamTimer timer;
     double kernel_ms = 0.0;
     long long launches = 0;
     DevBuf<int> rs_ptr, cs_ptr, hs_ptr, isc, ctl, left_idx, xi_rows;
@@ -154,15 +124,8 @@ namespace {
 bool valid_handle(lpbox_t *h) { return h != nullptr && h->B > 0; }
 
 int check_idx(lpbox_t *h, int idx) {
-    if (!valid_handle(h)) return fail(LPBOX_E_BADHANDLE, "bad handle");
-    if (idx < 0 || idx >= h->B) return fail(LPBOX_E_BADARG, "instance index %d out of range [0,%d)", idx, h->B);
-    return LPBOX_OK;
-}
-
-int use_device(lpbox_t *h) {
-    int cnt = 0;
-    if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) return fail(LPBOX_E_NODEVICE, "no HIP device available");
-    HIPCHK(hipSetDevice(h->device));
+    if (!valid_handle(h)) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
+    if (idx < 0 || idx >= h->B) return lpbox_fail(LPBOX_E_BADARG, "instance index %d out of range [0,%d)", idx, h->B);
     return LPBOX_OK;
 }
 
@@ -188,7 +151,7 @@ int size_lds(lpbox_t *h, int big) {
     const bool ref = h->order == LPBOX_ORDER_REFERENCE;
     h->lds = ref ? lp_ref_lds_bytes(g.NS, g.LS, g.ZS) : lp_window_lds_bytes(g.T, g.NS, g.LS, g.ZS);
     if (ref && !lp_ref_supported(g.T, g.EPT))
-        return fail(LPBOX_E_TOOLARGE, "reference order: instance with max(n,l)=%d exceeds the on-chip kernel (%d threads x %d slots)", big, g.T, g.EPT);
+        return lpbox_fail(LPBOX_E_TOOLARGE, "reference order: instance with max(n,l)=%d exceeds the on-chip kernel (%d threads x %d slots)", big, g.T, g.EPT);
     h->vals_in_lds = false;
     if (h->valued) {
         // the values (CSR order, CSC order) and rho4_E_transpose sit in LDS where they fit next to the index sets, else in global memory;
@@ -197,7 +160,7 @@ int size_lds(lpbox_t *h, int big) {
         h->vals_in_lds = h->opt.ref_vals >= 0 ? h->opt.ref_vals == 1 : with_vals <= 160 * 1024;
         if (h->vals_in_lds) h->lds = with_vals;
     }
-    if (h->lds > 160 * 1024) return fail(LPBOX_E_TOOLARGE, "instance needs %zu B of LDS (> 160 KiB per CU)", h->lds);
+    if (h->lds > 160 * 1024) return lpbox_fail(LPBOX_E_TOOLARGE, "instance needs %zu B of LDS (> 160 KiB per CU)", h->lds);
     return LPBOX_OK;
 }
 
@@ -206,17 +169,17 @@ int size_lds(lpbox_t *h, int big) {
 int plan(lpbox_t *h) {
     if (h->planned) return LPBOX_OK;
     for (int i = 0; i < h->B; i++)
-        if (!h->inst[i].set) return fail(LPBOX_E_STATE, "instance %d has no problem (call read_File / set_problem first)", i);
+        if (!h->inst[i].set) return lpbox_fail(LPBOX_E_STATE, "instance %d has no problem (call read_File / set_problem first)", i);
     int nmax = 0, lmax = 0, zmax = 0;
     for (auto &I : h->inst) { nmax = std::max(nmax, I.n); lmax = std::max(lmax, I.l); zmax = std::max(zmax, I.nnz); }
     const bool ref = h->order == LPBOX_ORDER_REFERENCE;
     h->opt = lp_layout_options_from_env();
     std::string why;
     int rc = lp_choose_geometry(nmax, lmax, zmax, ref, h->opt, &h->geo, &why);
-    if (rc) return fail(rc, "%s", why.c_str());
+    if (rc) return lpbox_fail(rc, "%s", why.c_str());
     h->valued = false;
     for (auto &I : h->inst) h->valued = h->valued || !I.vals.empty();
-    if (h->valued && !ref) return fail(LPBOX_E_UNSUPPORTED, "E has stored values != 1; only the reference order carries them (lpbox_set_order)");
+    if (h->valued && !ref) return lpbox_fail(LPBOX_E_UNSUPPORTED, "E has stored values != 1; only the reference order carries them (lpbox_set_order)");
     rc = size_lds(h, std::max(nmax, lmax));
     if (rc) return rc;
     int caps[3];
@@ -242,19 +205,13 @@ std::vector<Tp> pooled(const lpbox_t *h, std::vector<Tp> LpInstanceLayout::*tabl
     return pool;
 }
 
-template <typename Tp>
-hipError_t to_device(DevBuf<Tp> &d, const std::vector<Tp> &v) {
-    hipError_t e = d.alloc(v.size());
-    return e != hipSuccess ? e : hipMemcpy(d.p, v.data(), v.size() * sizeof(Tp), hipMemcpyHostToDevice);
-}
-
 // Create the stream, allocate the batch and copy the planned layout and the problem data to the device.
 int upload(lpbox_t *h) {
     if (h->finalized) return LPBOX_OK;
-    int rc = use_device(h);
+    int rc = use_device(h->device);
     if (rc) return rc;
     if (!h->stream) HIPCHK(hipStreamCreate(&h->stream));
-    if (!h->ev0) { HIPCHK(hipEventCreate(&h->ev0)); HIPCHK(hipEventCreate(&h->ev1)); }
+    HIPCHK(h->timer.create());
     const size_t B = h->B, NS = h->geo.NS, LS = h->geo.LS, ZS = h->geo.ZS;
     HIPCHK(h->x.alloc(B * NS)); HIPCHK(h->z1.alloc(B * NS)); HIPCHK(h->z2.alloc(B * NS)); HIPCHK(h->pd.alloc(B * NS));
     HIPCHK(h->live.alloc(B * NS)); HIPCHK(h->newfix.alloc(B * NS));
@@ -265,15 +222,15 @@ int upload(lpbox_t *h) {
 #ifdef LPBOX_STAMPS
     HIPCHK(h->stamps.alloc(B * 16)); HIPCHK(hipMemset(h->stamps.p, 0, B * 16 * sizeof(unsigned long long)));
 #endif
-    HIPCHK(to_device(h->rs_ptr, pooled(h, &LpInstanceLayout::rs_ptr, NS + 1, 0)));
-    HIPCHK(to_device(h->cs_ptr, pooled(h, &LpInstanceLayout::cs_ptr, NS + 1, 0)));
-    HIPCHK(to_device(h->hs_ptr, pooled(h, &LpInstanceLayout::hs_ptr, NS + 1, 0)));
-    HIPCHK(to_device(h->rs_col, pooled(h, &LpInstanceLayout::rs_col, ZS, (uint16_t)0)));
-    HIPCHK(to_device(h->cs_row, pooled(h, &LpInstanceLayout::cs_row, ZS, (uint16_t)0)));
-    HIPCHK(to_device(h->rid, pooled(h, &LpInstanceLayout::rid, NS, (uint16_t)0xFFFF)));
-    HIPCHK(to_device(h->rgl, pooled(h, &LpInstanceLayout::rgl, NS, (uint16_t)0)));
-    HIPCHK(to_device(h->rmeta, pooled(h, &LpInstanceLayout::rmeta, NS, (uint16_t)0x10)));
-    HIPCHK(to_device(h->cmeta, pooled(h, &LpInstanceLayout::cmeta, NS, (uint16_t)0)));
+    HIPCHK(h->rs_ptr.upload(pooled(h, &LpInstanceLayout::rs_ptr, NS + 1, 0)));
+    HIPCHK(h->cs_ptr.upload(pooled(h, &LpInstanceLayout::cs_ptr, NS + 1, 0)));
+    HIPCHK(h->hs_ptr.upload(pooled(h, &LpInstanceLayout::hs_ptr, NS + 1, 0)));
+    HIPCHK(h->rs_col.upload(pooled(h, &LpInstanceLayout::rs_col, ZS, (uint16_t)0)));
+    HIPCHK(h->cs_row.upload(pooled(h, &LpInstanceLayout::cs_row, ZS, (uint16_t)0)));
+    HIPCHK(h->rid.upload(pooled(h, &LpInstanceLayout::rid, NS, (uint16_t)0xFFFF)));
+    HIPCHK(h->rgl.upload(pooled(h, &LpInstanceLayout::rgl, NS, (uint16_t)0)));
+    HIPCHK(h->rmeta.upload(pooled(h, &LpInstanceLayout::rmeta, NS, (uint16_t)0x10)));
+    HIPCHK(h->cmeta.upload(pooled(h, &LpInstanceLayout::cmeta, NS, (uint16_t)0)));
     // the problem data: b and the live mask by storage position, f by row id
     std::vector<int> h_isc(B * NI_COUNT, 0);
     std::vector<uint8_t> h_live(B * NS, 0);
@@ -291,10 +248,10 @@ int upload(lpbox_t *h) {
         h_isc[i * NI_COUNT + NI_ACTIVE] = 1;
         h_c1[i] = std::pow((double)I.n, 1.0 / 2);     // std::pow(n, 1.0/p), p = projection_lp = 2 (LPcpp:427,503)
     }
-    HIPCHK(to_device(h->b, h_b)); HIPCHK(to_device(h->live_init, h_live)); HIPCHK(to_device(h->f_org, h_f));
-    HIPCHK(to_device(h->isc, h_isc)); HIPCHK(to_device(h->c1_init, h_c1));
+    HIPCHK(h->b.upload(h_b)); HIPCHK(h->live_init.upload(h_live)); HIPCHK(h->f_org.upload(h_f));
+    HIPCHK(h->isc.upload(h_isc)); HIPCHK(h->c1_init.upload(h_c1));
     if (h->valued) {
-        HIPCHK(to_device(h->vr, h_vr)); HIPCHK(to_device(h->vc, h_vc));
+        HIPCHK(h->vr.upload(h_vr)); HIPCHK(h->vc.upload(h_vc));
         HIPCHK(h->r4v.alloc(B * ZS)); HIPCHK(hipMemset(h->r4v.p, 0, B * ZS * sizeof(double)));
     }
     HIPCHK(hipMemset(h->ctl.p, 0, B * 4 * sizeof(int)));
@@ -310,16 +267,16 @@ int plan_and_upload(lpbox_t *h) {
 }
 
 int run_window(lpbox_t *h, int iter_start, int iter_end, int l2f, bool log = false) {
-    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    HIPCHK(h->timer.start(h->stream));
     LpBatchDev bd = h->dev();
     if (log) { bd.logbuf = h->logbuf.p; bd.log_cap = h->log_cap; }
     if (h->order == LPBOX_ORDER_REFERENCE) HIPCHK(lp_ref_launch_window(bd, h->ref_vals(), h->geo.EPT, h->lds, iter_start, iter_end, l2f, h->stream));
     else HIPCHK(lp_launch_window(bd, h->geo.T, h->geo.EPT, h->direct ? h->lds_direct : h->lds, iter_start, iter_end, l2f, h->stream, h->direct, log));
-    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    HIPCHK(h->timer.stop(h->stream));
     int rc = refresh_scalars(h);     // synchronises the stream
     if (rc) return rc;
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+    double ms = 0.0;
+    HIPCHK(h->timer.read(&ms));
     h->kernel_ms += ms;
     h->launches++;
     return LPBOX_OK;
@@ -327,21 +284,21 @@ int run_window(lpbox_t *h, int iter_start, int iter_end, int l2f, bool log = fal
 
 int set_instance(lpbox_t *h, int idx, int n, int l, int nnz, const int *colptr, const int *rowidx, const double *vals,
                  const double *b, const double *f) {
-    if (h->planned) return fail(LPBOX_E_STATE, "layout already planned (lpbox_init or a layout getter was called); create a new handle to change the problem");
-    if (n <= 0 || l <= 0 || nnz < 0 || !colptr || (!rowidx && nnz) || !b) return fail(LPBOX_E_BADARG, "bad problem arguments");
-    if (n == l) return fail(LPBOX_E_UNSUPPORTED, "n == l: the reference's aliased sparse product is ill-defined here (LPcpp:103-107,150)");
-    if (colptr[0] != 0 || colptr[n] != nnz) return fail(LPBOX_E_BADARG, "colptr does not span nnz");
+    if (h->planned) return lpbox_fail(LPBOX_E_STATE, "layout already planned (lpbox_init or a layout getter was called); create a new handle to change the problem");
+    if (n <= 0 || l <= 0 || nnz < 0 || !colptr || (!rowidx && nnz) || !b) return lpbox_fail(LPBOX_E_BADARG, "bad problem arguments");
+    if (n == l) return lpbox_fail(LPBOX_E_UNSUPPORTED, "n == l: the reference's aliased sparse product is ill-defined here (LPcpp:103-107,150)");
+    if (colptr[0] != 0 || colptr[n] != nnz) return lpbox_fail(LPBOX_E_BADARG, "colptr does not span nnz");
     // validate everything BEFORE touching the instance (a rejected call leaves it as it was) and before reading rowidx / vals through colptr
     bool valued = false;
     for (int j = 0; j < n; j++) {
-        if (colptr[j] < 0 || colptr[j + 1] < colptr[j] || colptr[j + 1] > nnz) return fail(LPBOX_E_BADARG, "colptr not monotone inside [0, nnz]");
+        if (colptr[j] < 0 || colptr[j + 1] < colptr[j] || colptr[j + 1] > nnz) return lpbox_fail(LPBOX_E_BADARG, "colptr not monotone inside [0, nnz]");
         for (int k = colptr[j]; k < colptr[j + 1]; k++) {
-            if (rowidx[k] < 0 || rowidx[k] >= l) return fail(LPBOX_E_BADARG, "row index out of range");
-            if (k > colptr[j] && rowidx[k] <= rowidx[k - 1]) return fail(LPBOX_E_BADARG, "row indices must ascend inside a column");
-            if (vals && !std::isfinite(vals[k])) return fail(LPBOX_E_BADARG, "E has a non-finite stored value (column %d, row %d)", j, rowidx[k]);
+            if (rowidx[k] < 0 || rowidx[k] >= l) return lpbox_fail(LPBOX_E_BADARG, "row index out of range");
+            if (k > colptr[j] && rowidx[k] <= rowidx[k - 1]) return lpbox_fail(LPBOX_E_BADARG, "row indices must ascend inside a column");
+            if (vals && !std::isfinite(vals[k])) return lpbox_fail(LPBOX_E_BADARG, "E has a non-finite stored value (column %d, row %d)", j, rowidx[k]);
             if (vals && vals[k] != 1.0) {
                 if (h->order != LPBOX_ORDER_REFERENCE)
-                    return fail(LPBOX_E_UNSUPPORTED, "E has a stored value %g != 1; the default-order LP kernels hold E implicitly as a 0/1 pattern "
+                    return lpbox_fail(LPBOX_E_UNSUPPORTED, "E has a stored value %g != 1; the default-order LP kernels hold E implicitly as a 0/1 pattern "
                                 "(call lpbox_set_order(LPBOX_ORDER_REFERENCE) first: the reference-order kernels carry stored values)", vals[k]);
                 valued = true;
             }
@@ -350,7 +307,7 @@ int set_instance(lpbox_t *h, int idx, int n, int l, int nnz, const int *colptr, 
     // the objective vector: a NaN in b would run every x-update to the PCG cap for up to 2e4 outer iterations (the reference accepts it
     // and computes garbage; a deliberate deviation).  Subnormals, zeros and either sign are ordinary values.
     for (int j = 0; j < n; j++)
-        if (!std::isfinite(b[j])) return fail(LPBOX_E_BADARG, "b has a non-finite entry (index %d)", j);
+        if (!std::isfinite(b[j])) return lpbox_fail(LPBOX_E_BADARG, "b has a non-finite entry (index %d)", j);
     LpInstance &I = h->inst[idx];
     I.n = n; I.l = l; I.nnz = nnz;
     I.dir_g.clear();                  // lpbox_get_direct_rows may have answered for the problem that was here
@@ -417,14 +374,14 @@ int lpbox_device_count(void) {
 
 int lpbox_set_device(int device) {
     int cnt = lpbox_device_count();
-    if (device < 0 || device >= cnt) return fail(LPBOX_E_NODEVICE, "device %d not available (%d visible)", device, cnt);
+    if (device < 0 || device >= cnt) return lpbox_fail(LPBOX_E_NODEVICE, "device %d not available (%d visible)", device, cnt);
     g_device = device;
     return LPBOX_OK;
 }
 
 lpbox_t *lpbox_create(int flavour, int batch, int print_info) {
     if (batch <= 0 || (flavour != LPBOX_FLAVOUR_LP && flavour != LPBOX_FLAVOUR_SEG) || (flavour == LPBOX_FLAVOUR_SEG && batch != 1)) {
-        fail(LPBOX_E_BADARG, "lpbox_create: unsupported flavour %d or batch %d", flavour, batch);
+        lpbox_fail(LPBOX_E_BADARG, "lpbox_create: unsupported flavour %d or batch %d", flavour, batch);
         return nullptr;
     }
     lpbox_t *h = new lpbox_solver();
@@ -439,22 +396,14 @@ void lpbox_destroy(lpbox_t *h) {
     if (h->seg) { segc_destroy(h->seg); delete h; return; }
     if (h->finalized) (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    h->rs_ptr.release(); h->cs_ptr.release(); h->hs_ptr.release(); h->cmeta.release(); h->isc.release(); h->ctl.release(); h->left_idx.release(); h->xi_rows.release();
-    h->rs_col.release(); h->cs_row.release(); h->rid.release(); h->rmeta.release(); h->rgl.release(); h->live_init.release();
-    h->x.release(); h->z1.release(); h->z2.release(); h->b.release(); h->pd.release(); h->z4.release(); h->f.release();
-    h->f_org.release(); h->dsc.release(); h->hist.release(); h->dctl.release(); h->c1_init.release(); h->xhist.release();
-    h->vr.release(); h->vc.release(); h->r4v.release();
-    h->row_off.release(); h->first_row.release(); h->fix_counts.release(); h->fix_codes.release();
-    h->xi_out.release(); h->live.release(); h->newfix.release(); h->stamps.release(); h->logbuf.release(); h->Hinv.release(); h->rdir.release(); h->dng.release();
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
+    h->timer.destroy();
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
 
 int lpbox_set_problem_lp(lpbox_t *h, int idx, int n, int l, int nnz, const int *colptr, const int *rowidx,
                          const double *vals, const double *b, const double *f) {
-    if (valid_handle(h) && h->seg) return fail(LPBOX_E_STATE, "this entry point belongs to the LP flavour");
+    if (valid_handle(h) && h->seg) return lpbox_fail(LPBOX_E_STATE, "this entry point belongs to the LP flavour");
     int rc = check_idx(h, idx);
     if (rc) return rc;
     return set_instance(h, idx, n, l, nnz, colptr, rowidx, vals, b, f);
@@ -462,23 +411,23 @@ int lpbox_set_problem_lp(lpbox_t *h, int idx, int n, int l, int nnz, const int *
 
 // readSparseMat LPcpp:2416-2444, readDenseVec :2407-2414, readFile :2446-2545
 int lpbox_read_files_lp(lpbox_t *h, int idx, const char *path_C, const char *path_b, int k) {
-    if (valid_handle(h) && h->seg) return fail(LPBOX_E_STATE, "this entry point belongs to the LP flavour");
+    if (valid_handle(h) && h->seg) return lpbox_fail(LPBOX_E_STATE, "this entry point belongs to the LP flavour");
     int rc = check_idx(h, idx);
     if (rc) return rc;
-    if (!path_C || !path_b) return fail(LPBOX_E_BADARG, "null path");
+    if (!path_C || !path_b) return lpbox_fail(LPBOX_E_BADARG, "null path");
     FILE *fc = fopen(path_C, "r");
-    if (!fc) return fail(LPBOX_E_IO, "cannot open %s", path_C);
+    if (!fc) return lpbox_fail(LPBOX_E_IO, "cannot open %s", path_C);
     struct Trip { int r, c; double v; };
     std::vector<Trip> t;
     int row, col, max_row = 0, max_col = 0;
     double val;
     while (fscanf(fc, "%d,%d,%lf\n", &row, &col, &val) == 3) {
-        if (row < 1 || col < 1) { fclose(fc); return fail(LPBOX_E_IO, "%s: indices are 1-based", path_C); }
+        if (row < 1 || col < 1) { fclose(fc); return lpbox_fail(LPBOX_E_IO, "%s: indices are 1-based", path_C); }
         max_row = std::max(max_row, row); max_col = std::max(max_col, col);
         t.push_back({row - 1, col - 1, k == 2 ? -1.0 * val : val});      // :2436-2439
     }
     fclose(fc);
-    if (t.empty()) return fail(LPBOX_E_IO, "%s: no 'row,col,val' triplets", path_C);
+    if (t.empty()) return lpbox_fail(LPBOX_E_IO, "%s: no 'row,col,val' triplets", path_C);
     // setFromTriplets (:2441-2443): column-major, sorted rows, duplicates summed
     std::vector<int> colptr(max_col + 1, 0);
     for (auto &e : t) colptr[e.c + 1]++;
@@ -498,10 +447,10 @@ int lpbox_read_files_lp(lpbox_t *h, int idx, const char *path_C, const char *pat
         cp[j + 1] = (int)rowidx.size();
     }
     FILE *fb = fopen(path_b, "r");
-    if (!fb) return fail(LPBOX_E_IO, "cannot open %s", path_b);
+    if (!fb) return lpbox_fail(LPBOX_E_IO, "cannot open %s", path_b);
     std::vector<double> b(max_col);
     for (int i = 0; i < max_col; i++) {
-        if (fscanf(fb, "%lf\n", &b[i]) != 1) { fclose(fb); return fail(LPBOX_E_IO, "error when reading dense vector %s (entry %d)", path_b, i); }
+        if (fscanf(fb, "%lf\n", &b[i]) != 1) { fclose(fb); return lpbox_fail(LPBOX_E_IO, "error when reading dense vector %s (entry %d)", path_b, i); }
         b[i] = -1.0 * b[i];                                                // :2520
     }
     fclose(fb);
@@ -519,10 +468,10 @@ int lpbox_read_file(lpbox_t *h, int idx, const char *root, int i, int k, int j) 
 
 int lpbox_init(lpbox_t *h) {
     if (valid_handle(h) && h->seg) return segc_init(h->seg);
-    if (!valid_handle(h)) return fail(LPBOX_E_BADHANDLE, "bad handle");
+    if (!valid_handle(h)) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
     int rc = plan_and_upload(h);
     if (rc) return rc;
-    rc = use_device(h);
+    rc = use_device(h->device);
     if (rc) return rc;
     for (auto &I : h->inst) {
         I.left_idx.resize(I.n);
@@ -545,7 +494,7 @@ static int stage_xiters(lpbox_t *h, int ws, const std::vector<int> &h_ctl, const
                         const std::vector<uint8_t> *h_newfix, const std::vector<int> &h_left, const std::vector<int> &h_rows) {
     const size_t B = h->B, NS = h->geo.NS;
     if ((double)B * ws * NS * sizeof(double) > 64e9)
-        return fail(LPBOX_E_BADARG, "x history of %d iterations x %zu instances would need %.1f GB", ws, B, (double)B * ws * NS * 8 / 1e9);
+        return lpbox_fail(LPBOX_E_BADARG, "x history of %d iterations x %zu instances would need %.1f GB", ws, B, (double)B * ws * NS * 8 / 1e9);
     if (ws > 0 && (h->ws_cap < ws || !h->xhist.p)) {
         HIPCHK(hipStreamSynchronize(h->stream));
         HIPCHK(h->xhist.alloc(B * (size_t)ws * NS));
@@ -628,10 +577,10 @@ int pack_xiters(lpbox_t *h, int ws) {
 extern "C" {
 
 int lpbox_iterate(lpbox_t *h, int iter_start, int iter_end, int *rets) {
-    if (valid_handle(h) && h->seg) return fail(LPBOX_E_STATE, "this entry point belongs to the LP flavour");
-    if (!valid_handle(h)) return fail(LPBOX_E_BADHANDLE, "bad handle");
-    if (!h->inited) return fail(LPBOX_E_STATE, "solve_init has not been called");
-    int rc = use_device(h);
+    if (valid_handle(h) && h->seg) return lpbox_fail(LPBOX_E_STATE, "this entry point belongs to the LP flavour");
+    if (!valid_handle(h)) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
+    if (!h->inited) return lpbox_fail(LPBOX_E_STATE, "solve_init has not been called");
+    int rc = use_device(h->device);
     if (rc) return rc;
     const bool rec = h->record && iter_end > iter_start;
     h->rows_valid = false;
@@ -653,9 +602,9 @@ int lpbox_iterate(lpbox_t *h, int iter_start, int iter_end, int *rets) {
     }
     const bool log = h->log_on && iter_end > iter_start;
     if (log) {                         // does_log (LPcpp:1013-1067): the values of the reference's per-iteration text log, one record per iteration
-        if (h->direct || !lp_log_supported(h->geo.T, h->geo.EPT)) return fail(LPBOX_E_UNSUPPORTED, "the iteration log is built for the default PCG kernels (512 threads per instance)");
+        if (h->direct || !lp_log_supported(h->geo.T, h->geo.EPT)) return lpbox_fail(LPBOX_E_UNSUPPORTED, "the iteration log is built for the default PCG kernels (512 threads per instance)");
         const size_t need = (size_t)h->B * (size_t)(iter_end - iter_start) * LP_LOG_VALS;
-        if (need * sizeof(double) > (size_t)1 << 30) return fail(LPBOX_E_UNSUPPORTED, "the iteration log of this call would exceed 1 GiB");
+        if (need * sizeof(double) > (size_t)1 << 30) return lpbox_fail(LPBOX_E_UNSUPPORTED, "the iteration log of this call would exceed 1 GiB");
         if (h->logbuf.count < need) HIPCHK(h->logbuf.alloc(need));
         h->log_cap = iter_end - iter_start;
         HIPCHK(hipMemsetAsync(h->logbuf.p, 0xFF, need * sizeof(double), h->stream));      // NaN = iteration not logged (it broke off, or was never reached)
@@ -674,17 +623,17 @@ int lpbox_iterate_l2f(lpbox_t *h, int iter_start, int iter_end, const double *ve
     if (valid_handle(h) && h->seg) {
         int ret = 0;
         if (nums && nums[0] != 0 && vec_stride < segc_get_n(h->seg))
-            return fail(LPBOX_E_BADARG, "fix vector holds %ld entries, %d live variables", vec_stride, segc_get_n(h->seg));
+            return lpbox_fail(LPBOX_E_BADARG, "fix vector holds %ld entries, %d live variables", vec_stride, segc_get_n(h->seg));
         int rc = segc_l2f(h->seg, iter_start, iter_end, vec, nums ? nums[0] : 0, &ret);
         if (rc < 0) return rc;
         if (rets) rets[0] = ret;
         return ret;
     }
-    if (!valid_handle(h)) return fail(LPBOX_E_BADHANDLE, "bad handle");
-    if (!h->inited) return fail(LPBOX_E_STATE, "solve_init has not been called");
+    if (!valid_handle(h)) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
+    if (!h->inited) return lpbox_fail(LPBOX_E_STATE, "solve_init has not been called");
     const int ws = iter_end - iter_start;
-    if (ws > LP_XITERS_COLS) return fail(LPBOX_E_BADARG, "window of %d iterations exceeds the %d columns of x_iters (LPcpp:1113)", ws, LP_XITERS_COLS);
-    int rc = use_device(h);
+    if (ws > LP_XITERS_COLS) return lpbox_fail(LPBOX_E_BADARG, "window of %d iterations exceeds the %d columns of x_iters (LPcpp:1113)", ws, LP_XITERS_COLS);
+    int rc = use_device(h->device);
     if (rc) return rc;
     const size_t B = h->B;
     bool any_fix = false;
@@ -693,16 +642,16 @@ int lpbox_iterate_l2f(lpbox_t *h, int iter_start, int iter_end, const double *ve
         const LpInstance &I = h->inst[i];
         const int n_live = (int)I.left_idx.size();
         const int num = nums ? nums[i] : 0;
-        if (num != 0 && !h->h_isc[i * NI_COUNT + NI_ACTIVE]) return fail(LPBOX_E_BADARG, "instance %zu is parked (lpbox_set_active) but has a fix request", i);
-        if (num < 0 || num > n_live) return fail(LPBOX_E_BADARG, "instance %zu: fix count %d outside [0,%d]", i, num, n_live);
+        if (num != 0 && !h->h_isc[i * NI_COUNT + NI_ACTIVE]) return lpbox_fail(LPBOX_E_BADARG, "instance %zu is parked (lpbox_set_active) but has a fix request", i);
+        if (num < 0 || num > n_live) return lpbox_fail(LPBOX_E_BADARG, "instance %zu: fix count %d outside [0,%d]", i, num, n_live);
         if (num != 0) {
-            if (!vec) return fail(LPBOX_E_BADARG, "fix vector missing");
-            if (vec_stride < n_live) return fail(LPBOX_E_BADARG, "instance %zu: fix vector holds %ld entries, %d live variables", i, vec_stride, n_live);
+            if (!vec) return lpbox_fail(LPBOX_E_BADARG, "fix vector missing");
+            if (vec_stride < n_live) return lpbox_fail(LPBOX_E_BADARG, "instance %zu: fix vector holds %ld entries, %d live variables", i, vec_stride, n_live);
             const double *v = vec + (size_t)i * vec_stride;
             int cnt = 0;
             for (int q = 0; q < n_live; q++) if (v[q] == 1 || v[q] == 0) cnt++;
             if (cnt != num)                                                 // the reference would run out of bounds (LPcpp:1135-1149)
-                return fail(LPBOX_E_BADARG, "instance %zu: vec fixes %d variables but num = %d", i, cnt, num);
+                return lpbox_fail(LPBOX_E_BADARG, "instance %zu: vec fixes %d variables but num = %d", i, cnt, num);
             any_fix = true;
         }
     }
@@ -716,18 +665,18 @@ int lpbox_iterate_l2f(lpbox_t *h, int iter_start, int iter_end, const double *ve
 }
 
 int lpbox_set_x_update(lpbox_t *h, int mode) {
-    if (valid_handle(h) && h->seg) return fail(LPBOX_E_STATE, "this entry point belongs to the LP flavour");
-    if (!valid_handle(h)) return fail(LPBOX_E_BADHANDLE, "bad handle");
-    if (mode != LPBOX_XUPDATE_PCG && mode != LPBOX_XUPDATE_DIRECT) return fail(LPBOX_E_BADARG, "x-update mode %d", mode);
+    if (valid_handle(h) && h->seg) return lpbox_fail(LPBOX_E_STATE, "this entry point belongs to the LP flavour");
+    if (!valid_handle(h)) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
+    if (mode != LPBOX_XUPDATE_PCG && mode != LPBOX_XUPDATE_DIRECT) return lpbox_fail(LPBOX_E_BADARG, "x-update mode %d", mode);
     if (mode == LPBOX_XUPDATE_PCG) { h->direct = false; return LPBOX_OK; }
-    if (h->order == LPBOX_ORDER_REFERENCE) return fail(LPBOX_E_UNSUPPORTED, "the direct x-update has no reference-order variant (lpbox_set_order)");
+    if (h->order == LPBOX_ORDER_REFERENCE) return lpbox_fail(LPBOX_E_UNSUPPORTED, "the direct x-update has no reference-order variant (lpbox_set_order)");
     int rc = plan_and_upload(h);       // the geometry decides whether the dense inverse fits
     if (rc) return rc;
-    rc = use_device(h);
+    rc = use_device(h->device);
     if (rc) return rc;
     if (!lp_direct_supported(h->geo.T, h->geo.EPT))
-        return fail(LPBOX_E_UNSUPPORTED, "direct x-update needs n <= 512 (this batch: %d threads x %d slots)", h->geo.T, h->geo.EPT);
-    if (!h->identity_rows) return fail(LPBOX_E_UNSUPPORTED, "direct x-update needs the plain row placement (unset LPBOX_LP_BANKAWARE)");
+        return lpbox_fail(LPBOX_E_UNSUPPORTED, "direct x-update needs n <= 512 (this batch: %d threads x %d slots)", h->geo.T, h->geo.EPT);
+    if (!h->identity_rows) return lpbox_fail(LPBOX_E_UNSUPPORTED, "direct x-update needs the plain row placement (unset LPBOX_LP_BANKAWARE)");
     if (!h->Hinv.p) {
         // Rows with pairwise disjoint columns (D) are inverted in closed form, the rest (G) through a dense |G| x |G| inverse in LDS.
         const size_t B = h->B, NS = h->geo.NS;
@@ -736,12 +685,12 @@ int lpbox_set_x_update(lpbox_t *h, int mode) {
             I.nG = lp_plan_direct_rows(view_of(I), &I.dir_g);
             gmax = std::max(gmax, I.nG);
         }
-        if (gmax > 128) return fail(LPBOX_E_UNSUPPORTED, "direct x-update: %d rows of E share columns (at most 128 fit the on-chip inverse)", gmax);
+        if (gmax > 128) return lpbox_fail(LPBOX_E_UNSUPPORTED, "direct x-update: %d rows of E share columns (at most 128 fit the on-chip inverse)", gmax);
         // pitch = 4 (mod 32) doubles: the quads of a half-wave (8 rows x 4 consecutive columns) fall on 64 distinct LDS banks
         h->HL = std::max(gmax, 1); h->HLD = ((h->HL + 27) / 32) * 32 + 4;
         h->lds_direct = lp_window_lds_bytes(h->geo.T, h->geo.NS, h->geo.LS, h->geo.ZS, h->HL, h->HLD);
         if (h->lds_direct > 160 * 1024)
-            return fail(LPBOX_E_UNSUPPORTED, "direct x-update needs %zu B of LDS (> 160 KiB per CU)", h->lds_direct);
+            return lpbox_fail(LPBOX_E_UNSUPPORTED, "direct x-update needs %zu B of LDS (> 160 KiB per CU)", h->lds_direct);
         std::vector<int16_t> h_rdir(B * NS, -1);
         std::vector<int> h_ng(B, 0);
         for (size_t i = 0; i < B; i++) {
@@ -761,7 +710,7 @@ int lpbox_set_x_update(lpbox_t *h, int mode) {
 }
 
 int lpbox_set_record(lpbox_t *h, int on) {
-    if (!valid_handle(h)) return fail(LPBOX_E_BADHANDLE, "bad handle");
+    if (!valid_handle(h)) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
     if (h->seg) return segc_set_record(h->seg, on);
     h->record = on != 0;
     return LPBOX_OK;
@@ -770,9 +719,9 @@ int lpbox_set_record(lpbox_t *h, int on) {
 // The values of the reference's per-iteration text log (does_log, LPh:148, LPcpp:1013-1067), opt-in: while on, every lpbox_iterate call
 // leaves one record of LPBOX_LOG_VALS doubles per iteration it completed.
 int lpbox_set_log(lpbox_t *h, int on) {
-    if (!valid_handle(h)) return fail(LPBOX_E_BADHANDLE, "bad handle");
-    if (h->seg) return fail(LPBOX_E_UNSUPPORTED, "the segmentation solver of the reference writes no iteration log (SEGh:225)");
-    if (on && h->order == LPBOX_ORDER_REFERENCE) return fail(LPBOX_E_UNSUPPORTED, "the iteration log has no reference-order variant (lpbox_set_order)");
+    if (!valid_handle(h)) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
+    if (h->seg) return lpbox_fail(LPBOX_E_UNSUPPORTED, "the segmentation solver of the reference writes no iteration log (SEGh:225)");
+    if (on && h->order == LPBOX_ORDER_REFERENCE) return lpbox_fail(LPBOX_E_UNSUPPORTED, "the iteration log has no reference-order variant (lpbox_set_order)");
     h->log_on = on != 0;
     if (!h->log_on) h->log_rows = 0;
     return LPBOX_OK;
@@ -781,16 +730,16 @@ int lpbox_set_log(lpbox_t *h, int on) {
 // Summation order of the on-chip kernels.  The layout is built when the problem is uploaded, so the order is
 // chosen before that.
 int lpbox_set_order(lpbox_t *h, int mode) {
-    if (valid_handle(h) && h->seg) return fail(LPBOX_E_STATE, "this entry point belongs to the LP flavour");
-    if (!valid_handle(h)) return fail(LPBOX_E_BADHANDLE, "bad handle");
-    if (mode != LPBOX_ORDER_DEFAULT && mode != LPBOX_ORDER_REFERENCE) return fail(LPBOX_E_BADARG, "summation order %d", mode);
+    if (valid_handle(h) && h->seg) return lpbox_fail(LPBOX_E_STATE, "this entry point belongs to the LP flavour");
+    if (!valid_handle(h)) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
+    if (mode != LPBOX_ORDER_DEFAULT && mode != LPBOX_ORDER_REFERENCE) return lpbox_fail(LPBOX_E_BADARG, "summation order %d", mode);
     if (mode == LPBOX_ORDER_DEFAULT)
         for (size_t i = 0; i < h->inst.size(); i++)
             if (!h->inst[i].vals.empty())
-                return fail(LPBOX_E_UNSUPPORTED, "instance %zu stores values != 1; only the reference order carries them", i);
-    if (mode == LPBOX_ORDER_REFERENCE && h->direct) return fail(LPBOX_E_UNSUPPORTED, "the direct x-update has no reference-order variant");
-    if (mode == LPBOX_ORDER_REFERENCE && h->log_on) return fail(LPBOX_E_UNSUPPORTED, "the iteration log has no reference-order variant");
-    if (h->planned) return fail(LPBOX_E_STATE, "layout already planned; choose the summation order before lpbox_init and the layout getters");
+                return lpbox_fail(LPBOX_E_UNSUPPORTED, "instance %zu stores values != 1; only the reference order carries them", i);
+    if (mode == LPBOX_ORDER_REFERENCE && h->direct) return lpbox_fail(LPBOX_E_UNSUPPORTED, "the direct x-update has no reference-order variant");
+    if (mode == LPBOX_ORDER_REFERENCE && h->log_on) return lpbox_fail(LPBOX_E_UNSUPPORTED, "the iteration log has no reference-order variant");
+    if (h->planned) return lpbox_fail(LPBOX_E_STATE, "layout already planned; choose the summation order before lpbox_init and the layout getters");
     h->order = mode;
     return LPBOX_OK;
 }
@@ -800,10 +749,10 @@ int lpbox_set_order(lpbox_t *h, int mode) {
 int lpbox_get_log(lpbox_t *h, int idx, double *out, int cap_rows) {
     int rc = check_idx(h, idx);
     if (rc) return rc;
-    if (h->seg) return fail(LPBOX_E_STATE, "this entry point belongs to the LP flavour");
-    if (!out || cap_rows < 0) return fail(LPBOX_E_BADARG, "null output");
+    if (h->seg) return lpbox_fail(LPBOX_E_STATE, "this entry point belongs to the LP flavour");
+    if (!out || cap_rows < 0) return lpbox_fail(LPBOX_E_BADARG, "null output");
     if (h->log_rows <= 0) return 0;
-    rc = use_device(h);
+    rc = use_device(h->device);
     if (rc) return rc;
     std::vector<double> t((size_t)h->log_rows * LP_LOG_VALS);
     HIPCHK(hipMemcpy(t.data(), h->logbuf.p + (size_t)idx * h->log_cap * LP_LOG_VALS, t.size() * sizeof(double), hipMemcpyDeviceToHost));
@@ -822,12 +771,12 @@ int lpbox_get_log(lpbox_t *h, int idx, double *out, int cap_rows) {
 }
 
 int lpbox_seg_get_x_history(lpbox_t *h, int first, int count, double *out) {
-    if (!valid_handle(h) || !h->seg) return fail(LPBOX_E_BADHANDLE, "bad handle (segmentation flavour only)");
+    if (!valid_handle(h) || !h->seg) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle (segmentation flavour only)");
     return segc_get_x_history(h->seg, first, count, out);
 }
 
 int lpbox_policy_layout(int tokens, long *weight_halves, long *const_floats) {
-    if (tokens != 20 && tokens != 5) return fail(LPBOX_E_BADARG, "tokens must be 20 (LP) or 5 (segmentation)");
+    if (tokens != 20 && tokens != 5) return lpbox_fail(LPBOX_E_BADARG, "tokens must be 20 (LP) or 5 (segmentation)");
     if (weight_halves) *weight_halves = 2L * POLICY_FRAGS_PER_LAYER * 512;
     if (const_floats) *const_floats = POLICY_OFF_LAYER(tokens) + 2L * POLICY_LAYER_CONSTS;
     return LPBOX_OK;
@@ -835,10 +784,10 @@ int lpbox_policy_layout(int tokens, long *weight_halves, long *const_floats) {
 
 int lpbox_policy_encode_f16(const double *x_dev, const long long *row_off_dev, long rows, int tokens, int tok_stride,
                             const void *weights_dev, const float *consts_dev, void *out_dev, void *hip_stream) {
-    if (tokens != 20 && tokens != 5) return fail(LPBOX_E_BADARG, "tokens must be 20 (LP) or 5 (segmentation)");
-    if (rows < 0 || tok_stride < 1) return fail(LPBOX_E_BADARG, "bad rows / token stride");
+    if (tokens != 20 && tokens != 5) return lpbox_fail(LPBOX_E_BADARG, "tokens must be 20 (LP) or 5 (segmentation)");
+    if (rows < 0 || tok_stride < 1) return lpbox_fail(LPBOX_E_BADARG, "bad rows / token stride");
     if (rows == 0) return LPBOX_OK;
-    if (!x_dev || !row_off_dev || !weights_dev || !consts_dev || !out_dev) return fail(LPBOX_E_BADARG, "null device pointer");
+    if (!x_dev || !row_off_dev || !weights_dev || !consts_dev || !out_dev) return lpbox_fail(LPBOX_E_BADARG, "null device pointer");
     PolicyArgs pa;
     pa.x = x_dev; pa.row_off = row_off_dev; pa.rows = rows; pa.tok_stride = tok_stride;
     pa.weights = weights_dev; pa.consts = consts_dev; pa.out = out_dev;
@@ -847,7 +796,7 @@ int lpbox_policy_encode_f16(const double *x_dev, const long long *row_off_dev, l
 }
 
 int lpbox_policy_f32frag_layout(int tokens, long *weight_floats, long *const_floats) {
-    if (tokens != 20 && tokens != 5) return fail(LPBOX_E_BADARG, "tokens must be 20 (LP) or 5 (segmentation)");
+    if (tokens != 20 && tokens != 5) return lpbox_fail(LPBOX_E_BADARG, "tokens must be 20 (LP) or 5 (segmentation)");
     if (weight_floats) *weight_floats = policy_f32frag_floats();
     if (const_floats) *const_floats = POLICY_OFF_LAYER(tokens) + 2L * POLICY_LAYER_CONSTS;
     return LPBOX_OK;
@@ -855,10 +804,10 @@ int lpbox_policy_f32frag_layout(int tokens, long *weight_floats, long *const_flo
 
 int lpbox_policy_encode_f32(const double *x_dev, const long long *row_off_dev, long rows, int tokens, int tok_stride,
                             const float *weights_dev, const float *consts_dev, float *out_dev, void *hip_stream) {
-    if (tokens != 20 && tokens != 5) return fail(LPBOX_E_BADARG, "tokens must be 20 (LP) or 5 (segmentation)");
-    if (rows < 0 || tok_stride < 1) return fail(LPBOX_E_BADARG, "bad rows / token stride");
+    if (tokens != 20 && tokens != 5) return lpbox_fail(LPBOX_E_BADARG, "tokens must be 20 (LP) or 5 (segmentation)");
+    if (rows < 0 || tok_stride < 1) return lpbox_fail(LPBOX_E_BADARG, "bad rows / token stride");
     if (rows == 0) return LPBOX_OK;
-    if (!x_dev || !row_off_dev || !weights_dev || !consts_dev || !out_dev) return fail(LPBOX_E_BADARG, "null device pointer");
+    if (!x_dev || !row_off_dev || !weights_dev || !consts_dev || !out_dev) return lpbox_fail(LPBOX_E_BADARG, "null device pointer");
     PolicyArgs pa;
     pa.x = x_dev; pa.row_off = row_off_dev; pa.rows = rows; pa.tok_stride = tok_stride;
     pa.weights = weights_dev; pa.consts = consts_dev; pa.out = out_dev;
@@ -867,17 +816,17 @@ int lpbox_policy_encode_f32(const double *x_dev, const long long *row_off_dev, l
 }
 
 int lpbox_policy_f32_layout(int tokens, long *weight_floats) {
-    if (tokens != 20 && tokens != 5) return fail(LPBOX_E_BADARG, "tokens must be 20 (LP) or 5 (segmentation)");
+    if (tokens != 20 && tokens != 5) return lpbox_fail(LPBOX_E_BADARG, "tokens must be 20 (LP) or 5 (segmentation)");
     if (weight_floats) *weight_floats = policy_f32_weight_floats(tokens);
     return LPBOX_OK;
 }
 
 int lpbox_policy_score_f32(const double *x_dev, const long long *row_off_dev, long rows, int tokens, int tok_stride,
                            const float *weights_dev, float *sigmoid_dev, float *logit_dev, void *hip_stream) {
-    if (tokens != 20 && tokens != 5) return fail(LPBOX_E_BADARG, "tokens must be 20 (LP) or 5 (segmentation)");
-    if (rows < 0 || tok_stride < 1) return fail(LPBOX_E_BADARG, "bad rows / token stride");
+    if (tokens != 20 && tokens != 5) return lpbox_fail(LPBOX_E_BADARG, "tokens must be 20 (LP) or 5 (segmentation)");
+    if (rows < 0 || tok_stride < 1) return lpbox_fail(LPBOX_E_BADARG, "bad rows / token stride");
     if (rows == 0) return LPBOX_OK;
-    if (!x_dev || !row_off_dev || !weights_dev || !sigmoid_dev) return fail(LPBOX_E_BADARG, "null device pointer");
+    if (!x_dev || !row_off_dev || !weights_dev || !sigmoid_dev) return lpbox_fail(LPBOX_E_BADARG, "null device pointer");
     HIPCHK(policy_launch_f32(x_dev, row_off_dev, rows, tokens, tok_stride, weights_dev, sigmoid_dev, logit_dev, 0.f, 0.f, 0.f, nullptr, (hipStream_t)hip_stream));
     return LPBOX_OK;
 }
@@ -885,18 +834,18 @@ int lpbox_policy_score_f32(const double *x_dev, const long long *row_off_dev, lo
 int lpbox_policy_rescore_f32(const double *x_dev, const long long *row_off_dev, long rows, int tokens, int tok_stride,
                              const float *weights_dev, float *sigmoid_dev, float band, float thr_hi, float thr_lo,
                              unsigned long long *count_dev, void *hip_stream) {
-    if (tokens != 20 && tokens != 5) return fail(LPBOX_E_BADARG, "tokens must be 20 (LP) or 5 (segmentation)");
-    if (rows < 0 || tok_stride < 1 || !(band > 0.f)) return fail(LPBOX_E_BADARG, "bad rows / token stride / band");
+    if (tokens != 20 && tokens != 5) return lpbox_fail(LPBOX_E_BADARG, "tokens must be 20 (LP) or 5 (segmentation)");
+    if (rows < 0 || tok_stride < 1 || !(band > 0.f)) return lpbox_fail(LPBOX_E_BADARG, "bad rows / token stride / band");
     if (rows == 0) return LPBOX_OK;
-    if (!x_dev || !row_off_dev || !weights_dev || !sigmoid_dev) return fail(LPBOX_E_BADARG, "null device pointer");
+    if (!x_dev || !row_off_dev || !weights_dev || !sigmoid_dev) return lpbox_fail(LPBOX_E_BADARG, "null device pointer");
     HIPCHK(policy_launch_f32(x_dev, row_off_dev, rows, tokens, tok_stride, weights_dev, sigmoid_dev, nullptr, band, thr_hi, thr_lo, count_dev, (hipStream_t)hip_stream));
     return LPBOX_OK;
 }
 
 int lpbox_set_active(lpbox_t *h, const int *active) {
-    if (!valid_handle(h) || h->seg) return fail(LPBOX_E_BADHANDLE, "bad handle (LP flavour only)");
-    if (!h->inited) return fail(LPBOX_E_STATE, "solve_init has not been called");
-    int rc = use_device(h);
+    if (!valid_handle(h) || h->seg) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle (LP flavour only)");
+    if (!h->inited) return lpbox_fail(LPBOX_E_STATE, "solve_init has not been called");
+    int rc = use_device(h->device);
     if (rc) return rc;
     std::vector<int> a(h->B, 1);
     for (int i = 0; i < h->B && active; i++) a[i] = active[i] != 0;
@@ -941,12 +890,12 @@ int lpbox_get_x_iters(lpbox_t *h, int idx, int ws, double *out) {
     if (valid_handle(h) && h->seg) return segc_get_x_iters(h->seg, ws, out);
     int rc = check_idx(h, idx);
     if (rc) return rc;
-    if (!h->xi_valid) return fail(LPBOX_E_STATE, "solve_iter_l2f has not been called");
+    if (!h->xi_valid) return lpbox_fail(LPBOX_E_STATE, "solve_iter_l2f has not been called");
     const int ws_max = std::max(LP_XITERS_COLS, h->ws_cap);      // x_iters has 500 columns (LPcpp:1113); a recorded plain window may be longer
-    if (ws < 0 || ws > ws_max) return fail(LPBOX_E_BADARG, "ws = %d outside [0,%d]", ws, ws_max);
+    if (ws < 0 || ws > ws_max) return lpbox_fail(LPBOX_E_BADARG, "ws = %d outside [0,%d]", ws, ws_max);
     const int rows = h->inst[idx].xi_rows;
     if (!out || rows == 0 || ws == 0) return rows;
-    rc = use_device(h);
+    rc = use_device(h->device);
     if (rc) return rc;
     const int wsd = std::min(ws, h->ws_cap);          // columns beyond the staged window stay zero, like the reference's matrix
     rc = pack_xiters(h, wsd);                          // the whole batch, once per (call, ws)
@@ -964,10 +913,10 @@ int lpbox_get_x_iters(lpbox_t *h, int idx, int ws, double *out) {
 
 int lpbox_get_x_iters_device(lpbox_t *h, int ws, void **dev_ptr, long *stride_doubles) {
     if (valid_handle(h) && h->seg) return segc_get_x_iters_device(h->seg, ws, dev_ptr, stride_doubles);
-    if (!valid_handle(h)) return fail(LPBOX_E_BADHANDLE, "bad handle");
-    if (!h->xi_valid) return fail(LPBOX_E_STATE, "solve_iter_l2f has not been called");
-    if (ws <= 0 || ws > h->ws_cap) return fail(LPBOX_E_BADARG, "ws = %d outside (0,%d] (the last window)", ws, h->ws_cap);
-    int rc = use_device(h);
+    if (!valid_handle(h)) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
+    if (!h->xi_valid) return lpbox_fail(LPBOX_E_STATE, "solve_iter_l2f has not been called");
+    if (ws <= 0 || ws > h->ws_cap) return lpbox_fail(LPBOX_E_BADARG, "ws = %d outside (0,%d] (the last window)", ws, h->ws_cap);
+    int rc = use_device(h->device);
     if (rc) return rc;
     rc = pack_xiters(h, ws);
     if (rc) return rc;
@@ -977,11 +926,11 @@ int lpbox_get_x_iters_device(lpbox_t *h, int ws, void **dev_ptr, long *stride_do
 }
 
 long lpbox_get_x_iters_rows_device(lpbox_t *h, int ws, void **row_off_dev, int *first_row) {
-    if (valid_handle(h) && h->seg) return fail(LPBOX_E_STATE, "this entry point belongs to the LP flavour");
-    if (!valid_handle(h)) return fail(LPBOX_E_BADHANDLE, "bad handle");
-    if (!h->xi_valid) return fail(LPBOX_E_STATE, "solve_iter_l2f has not been called");
-    if (ws <= 0 || ws > h->ws_cap) return fail(LPBOX_E_BADARG, "ws = %d outside (0,%d] (the last window)", ws, h->ws_cap);
-    int rc = use_device(h);
+    if (valid_handle(h) && h->seg) return lpbox_fail(LPBOX_E_STATE, "this entry point belongs to the LP flavour");
+    if (!valid_handle(h)) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
+    if (!h->xi_valid) return lpbox_fail(LPBOX_E_STATE, "solve_iter_l2f has not been called");
+    if (ws <= 0 || ws > h->ws_cap) return lpbox_fail(LPBOX_E_BADARG, "ws = %d outside (0,%d] (the last window)", ws, h->ws_cap);
+    int rc = use_device(h->device);
     if (rc) return rc;
     rc = pack_xiters(h, ws);
     if (rc) return rc;
@@ -1006,18 +955,18 @@ long lpbox_get_x_iters_rows_device(lpbox_t *h, int ws, void **row_off_dev, int *
 
 int lpbox_iterate_l2f_scores(lpbox_t *h, int iter_start, int iter_end, const float *scores_dev, double hi, double lo, int min_fix,
                              int *rets, int *fixed) {
-    if (valid_handle(h) && h->seg) return fail(LPBOX_E_STATE, "this entry point belongs to the LP flavour (segmentation: lpbox_seg_batch_iterate_l2f_scores)");
-    if (!valid_handle(h)) return fail(LPBOX_E_BADHANDLE, "bad handle");
+    if (valid_handle(h) && h->seg) return lpbox_fail(LPBOX_E_STATE, "this entry point belongs to the LP flavour (segmentation: lpbox_seg_batch_iterate_l2f_scores)");
+    if (!valid_handle(h)) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
     const int ws = iter_end - iter_start;
-    if (ws > LP_XITERS_COLS) return fail(LPBOX_E_BADARG, "window of %d iterations exceeds the %d columns of x_iters (LPcpp:1113)", ws, LP_XITERS_COLS);
-    if (min_fix < 0) return fail(LPBOX_E_BADARG, "min_fix = %d is negative", min_fix);
-    if (!std::isfinite(hi) || !std::isfinite(lo) || hi < lo) return fail(LPBOX_E_BADARG, "thresholds hi = %g, lo = %g: both must be finite and hi >= lo", hi, lo);
+    if (ws > LP_XITERS_COLS) return lpbox_fail(LPBOX_E_BADARG, "window of %d iterations exceeds the %d columns of x_iters (LPcpp:1113)", ws, LP_XITERS_COLS);
+    if (min_fix < 0) return lpbox_fail(LPBOX_E_BADARG, "min_fix = %d is negative", min_fix);
+    if (!std::isfinite(hi) || !std::isfinite(lo) || hi < lo) return lpbox_fail(LPBOX_E_BADARG, "thresholds hi = %g, lo = %g: both must be finite and hi >= lo", hi, lo);
     if (scores_dev && !h->rows_valid)
-        return fail(LPBOX_E_STATE, "scores given but lpbox_get_x_iters_rows_device has not been called since the last window");
+        return lpbox_fail(LPBOX_E_STATE, "scores given but lpbox_get_x_iters_rows_device has not been called since the last window");
     if (scores_dev && h->rows_mask_changed)
-        return fail(LPBOX_E_STATE, "scores given but lpbox_set_active changed the active instances after the row table was built");
-    if (!h->inited) return fail(LPBOX_E_STATE, "solve_init has not been called");
-    int rc = use_device(h);
+        return lpbox_fail(LPBOX_E_STATE, "scores given but lpbox_set_active changed the active instances after the row table was built");
+    if (!h->inited) return lpbox_fail(LPBOX_E_STATE, "solve_init has not been called");
+    int rc = use_device(h->device);
     if (rc) return rc;
     const size_t B = h->B;
     std::vector<int> k(B, 0);
@@ -1047,8 +996,8 @@ int lpbox_get_x_sol(lpbox_t *h, int idx, double *out) {
     if (valid_handle(h) && h->seg) return segc_get_x_sol(h->seg, out);
     int rc = check_idx(h, idx);
     if (rc) return rc;
-    if (!h->inited || !out) return fail(LPBOX_E_STATE, "not initialised");
-    rc = use_device(h);
+    if (!h->inited || !out) return lpbox_fail(LPBOX_E_STATE, "not initialised");
+    rc = use_device(h->device);
     if (rc) return rc;
     std::vector<double> x; std::vector<uint8_t> live;
     if ((rc = fetch_vec(h, h->x.p, h->geo.NS, idx, h->inst[idx].n, x))) return rc;
@@ -1060,8 +1009,8 @@ int lpbox_get_x_sol(lpbox_t *h, int idx, double *out) {
 int lpbox_get_final_x_sol(lpbox_t *h, int idx, double *out) {
     int rc = check_idx(h, idx);
     if (rc) return rc;
-    if (!h->inited || !out) return fail(LPBOX_E_STATE, "not initialised");
-    rc = use_device(h);
+    if (!h->inited || !out) return lpbox_fail(LPBOX_E_STATE, "not initialised");
+    rc = use_device(h->device);
     if (rc) return rc;
     std::vector<double> x;
     if ((rc = fetch_vec(h, h->x.p, h->geo.NS, idx, h->inst[idx].n, x))) return rc;
@@ -1073,7 +1022,7 @@ int lpbox_get_final_x_sol(lpbox_t *h, int idx, double *out) {
 int lpbox_cal_obj(lpbox_t *h, int idx, double *out) {
     int rc = check_idx(h, idx);
     if (rc) return rc;
-    if (!h->inited || !out) return fail(LPBOX_E_STATE, "not initialised");
+    if (!h->inited || !out) return lpbox_fail(LPBOX_E_STATE, "not initialised");
     const double *d = &h->h_dsc[(size_t)idx * ND_COUNT];
     const int n_live = h->h_isc[(size_t)idx * NI_COUNT + NI_NLIVE];
     *out = n_live != 0 ? d[ND_SUM_FIX_OBJ] + d[ND_CUR_OBJ] : d[ND_SUM_FIX_OBJ];   // LPcpp:1630-1642
@@ -1083,7 +1032,7 @@ int lpbox_cal_obj(lpbox_t *h, int idx, double *out) {
 int lpbox_cur_bin_obj(lpbox_t *h, int idx, double *out) {
     int rc = check_idx(h, idx);
     if (rc) return rc;
-    if (!h->inited || !out) return fail(LPBOX_E_STATE, "not initialised");
+    if (!h->inited || !out) return lpbox_fail(LPBOX_E_STATE, "not initialised");
     *out = h->h_dsc[(size_t)idx * ND_COUNT + ND_CUR_OBJ];
     return LPBOX_OK;
 }
@@ -1092,7 +1041,7 @@ int lpbox_get_problem_lp(lpbox_t *h, int idx, int *n, int *l, int *nnz, int *col
     int rc = check_idx(h, idx);
     if (rc) return rc;
     const LpInstance &I = h->inst[idx];
-    if (!I.set) return fail(LPBOX_E_STATE, "instance %d has no problem (call read_File / set_problem first)", idx);
+    if (!I.set) return lpbox_fail(LPBOX_E_STATE, "instance %d has no problem (call read_File / set_problem first)", idx);
     if (n) *n = I.n;
     if (l) *l = I.l;
     if (nnz) *nnz = I.nnz;
@@ -1104,11 +1053,11 @@ int lpbox_get_problem_lp(lpbox_t *h, int idx, int *n, int *l, int *nnz, int *col
 }
 
 int lpbox_get_problem_lp_vals(lpbox_t *h, int idx, double *vals) {
-    if (valid_handle(h) && h->seg) return fail(LPBOX_E_STATE, "this entry point belongs to the LP flavour");
+    if (valid_handle(h) && h->seg) return lpbox_fail(LPBOX_E_STATE, "this entry point belongs to the LP flavour");
     int rc = check_idx(h, idx);
     if (rc) return rc;
     const LpInstance &I = h->inst[idx];
-    if (!I.set) return fail(LPBOX_E_STATE, "instance %d has no problem (call read_File / set_problem first)", idx);
+    if (!I.set) return lpbox_fail(LPBOX_E_STATE, "instance %d has no problem (call read_File / set_problem first)", idx);
     if (vals) {
         if (I.vals.empty()) std::fill(vals, vals + I.nnz, 1.0);
         else std::copy(I.vals.begin(), I.vals.end(), vals);
@@ -1119,8 +1068,8 @@ int lpbox_get_problem_lp_vals(lpbox_t *h, int idx, double *vals) {
 int lpbox_check_infeasible_lpbox(lpbox_t *h, int idx) {                     // LPcpp:1577-1591: rows of the CURRENT E with (E x)_i > 1
     int rc = check_idx(h, idx);
     if (rc) return rc;
-    if (!h->inited) return fail(LPBOX_E_STATE, "not initialised");
-    rc = use_device(h);
+    if (!h->inited) return lpbox_fail(LPBOX_E_STATE, "not initialised");
+    rc = use_device(h->device);
     if (rc) return rc;
     const LpInstance &I = h->inst[idx];
     if (I.left_idx.empty()) return 0;
@@ -1140,7 +1089,7 @@ int lpbox_check_infeasible_lpbox(lpbox_t *h, int idx) {                     // L
 int lpbox_check_infeasible_l2f(lpbox_t *h, int idx) {                       // LPcpp:1593-1612: ORIGINAL E times the rounded full-length x
     int rc = check_idx(h, idx);
     if (rc) return rc;
-    if (!h->inited) return fail(LPBOX_E_STATE, "not initialised");
+    if (!h->inited) return lpbox_fail(LPBOX_E_STATE, "not initialised");
     const LpInstance &I = h->inst[idx];
     std::vector<double> sol(I.n);
     rc = lpbox_get_x_sol(h, idx, sol.data());
@@ -1156,7 +1105,7 @@ int lpbox_check_infeasible_l2f(lpbox_t *h, int idx) {                       // L
 
 int lpbox_get_config(lpbox_t *h, int *threads, int *elems_per_thread, int *lds_bytes) {
     if (valid_handle(h) && h->seg) return segc_get_config(h->seg, threads, elems_per_thread, lds_bytes);
-    if (!valid_handle(h)) return fail(LPBOX_E_BADHANDLE, "bad handle");
+    if (!valid_handle(h)) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
     int rc = plan(h);
     if (rc) return rc;
     if (threads) *threads = h->geo.T;
@@ -1166,16 +1115,16 @@ int lpbox_get_config(lpbox_t *h, int *threads, int *elems_per_thread, int *lds_b
 }
 
 int lpbox_get_pcg_loop(lpbox_t *h, int *specialised) {
-    if (!valid_handle(h) || h->seg) return fail(LPBOX_E_BADHANDLE, "bad handle");
+    if (!valid_handle(h) || h->seg) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
     int rc = plan(h);
     if (rc) return rc;
-    if (!specialised) return fail(LPBOX_E_BADARG, "null output");
+    if (!specialised) return lpbox_fail(LPBOX_E_BADARG, "null output");
     *specialised = (h->order != LPBOX_ORDER_REFERENCE && !h->direct && !h->log_on && lp_pcg_specialised(h->geo.T, h->geo.EPT) && !h->opt.pcg_generic) ? 1 : 0;
     return LPBOX_OK;
 }
 
 int lpbox_wave_class_rule(int lanes, const int *row_len, const int *col_len, const int *help_len, int *class4) {
-    if (lanes < 0 || !class4 || (lanes > 0 && (!row_len || !col_len || !help_len))) return fail(LPBOX_E_BADARG, "null or negative argument");
+    if (lanes < 0 || !class4 || (lanes > 0 && (!row_len || !col_len || !help_len))) return lpbox_fail(LPBOX_E_BADARG, "null or negative argument");
     int caps[3];
     lp_pcg_list_caps(&caps[0], &caps[1], &caps[2]);
     lp_wave_class_rule(lanes, row_len, col_len, help_len, caps, class4);
@@ -1185,12 +1134,12 @@ int lpbox_wave_class_rule(int lanes, const int *row_len, const int *col_len, con
 int lpbox_get_wave_classes(lpbox_t *h, int idx, int *classes4) {
     int rc = check_idx(h, idx);
     if (rc) return rc;
-    if (h->seg) return fail(LPBOX_E_BADHANDLE, "bad handle");
+    if (h->seg) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
     rc = plan(h);
     if (rc) return rc;
-    if (!classes4) return fail(LPBOX_E_BADARG, "null output");
+    if (!classes4) return lpbox_fail(LPBOX_E_BADARG, "null output");
     const LpInstance &I = h->inst[idx];
-    if (I.lay.wave_class.empty()) return fail(LPBOX_E_UNSUPPORTED, "wave classes are defined for the 512 x 1 kernel of the default order");
+    if (I.lay.wave_class.empty()) return lpbox_fail(LPBOX_E_UNSUPPORTED, "wave classes are defined for the 512 x 1 kernel of the default order");
     for (size_t k = 0; k < I.lay.wave_class.size(); k++) classes4[k] = I.lay.wave_class[k];
     return (int)(I.lay.wave_class.size() / 4);
 }
@@ -1200,7 +1149,7 @@ int lpbox_get_layout(lpbox_t *h, int idx, int *pos_of_var) {
     if (rc) return rc;
     rc = plan(h);
     if (rc) return rc;
-    if (!pos_of_var) return fail(LPBOX_E_BADARG, "null output");
+    if (!pos_of_var) return lpbox_fail(LPBOX_E_BADARG, "null output");
     const LpInstance &I = h->inst[idx];
     for (int j = 0; j < I.n; j++) pos_of_var[j] = I.lay.cpos[j];
     return I.n;
@@ -1211,7 +1160,7 @@ int lpbox_get_row_split(lpbox_t *h, int idx, int *lanes_of_row) {
     if (rc) return rc;
     rc = plan(h);
     if (rc) return rc;
-    if (!lanes_of_row) return fail(LPBOX_E_BADARG, "null output");
+    if (!lanes_of_row) return lpbox_fail(LPBOX_E_BADARG, "null output");
     const LpInstance &I = h->inst[idx];
     for (int r = 0; r < I.l; r++) lanes_of_row[r] = I.lay.rowG[r];
     return I.l;
@@ -1222,7 +1171,7 @@ int lpbox_get_col_split(lpbox_t *h, int idx, int *own, int *help4) {
     if (rc) return rc;
     rc = plan(h);
     if (rc) return rc;
-    if (!own || !help4) return fail(LPBOX_E_BADARG, "null output");
+    if (!own || !help4) return lpbox_fail(LPBOX_E_BADARG, "null output");
     const LpInstance &I = h->inst[idx];
     for (int j = 0; j < I.n; j++) own[j] = I.lay.col_own[j];
     for (int k = 0; k < 4 * I.n; k++) help4[k] = I.lay.col_help[k];
@@ -1232,10 +1181,10 @@ int lpbox_get_col_split(lpbox_t *h, int idx, int *own, int *help4) {
 int lpbox_get_direct_rows(lpbox_t *h, int idx, int *gidx_of_row) {
     int rc = check_idx(h, idx);
     if (rc) return rc;
-    if (h->seg) return fail(LPBOX_E_STATE, "this entry point belongs to the LP flavour");
+    if (h->seg) return lpbox_fail(LPBOX_E_STATE, "this entry point belongs to the LP flavour");
     LpInstance &I = h->inst[idx];
-    if (!I.set) return fail(LPBOX_E_STATE, "instance %d has no problem (call read_File / set_problem first)", idx);
-    if (!gidx_of_row) return fail(LPBOX_E_BADARG, "null output");
+    if (!I.set) return lpbox_fail(LPBOX_E_STATE, "instance %d has no problem (call read_File / set_problem first)", idx);
+    if (!gidx_of_row) return lpbox_fail(LPBOX_E_BADARG, "null output");
     if ((int)I.dir_g.size() != I.l) I.nG = lp_plan_direct_rows(view_of(I), &I.dir_g);     // a function of the instance alone: no device, no mode
     for (int r = 0; r < I.l; r++) gidx_of_row[r] = I.dir_g[r];
     return I.nG;
@@ -1245,7 +1194,7 @@ int lpbox_get_counters(lpbox_t *h, int idx, long long *outer_iters, long long *p
     if (valid_handle(h) && h->seg) return segc_get_counters(h->seg, outer_iters, pcg_iters);
     int rc = check_idx(h, idx);
     if (rc) return rc;
-    if (!h->inited) return fail(LPBOX_E_STATE, "not initialised");
+    if (!h->inited) return lpbox_fail(LPBOX_E_STATE, "not initialised");
     if (outer_iters) *outer_iters = h->h_isc[(size_t)idx * NI_COUNT + NI_OUTER_TOTAL];
     if (pcg_iters) *pcg_iters = h->h_isc[(size_t)idx * NI_COUNT + NI_PCG_TOTAL];
     return LPBOX_OK;
@@ -1255,7 +1204,7 @@ int lpbox_get_stop(lpbox_t *h, int idx, int *reason, int *plain_iter_plus1) {
     if (valid_handle(h) && h->seg) return segc_get_stop(h->seg, reason, plain_iter_plus1);
     int rc = check_idx(h, idx);
     if (rc) return rc;
-    if (!h->inited) return fail(LPBOX_E_STATE, "not initialised");
+    if (!h->inited) return lpbox_fail(LPBOX_E_STATE, "not initialised");
     if (reason) *reason = h->h_isc[(size_t)idx * NI_COUNT + NI_STOP];
     if (plain_iter_plus1) *plain_iter_plus1 = h->h_isc[(size_t)idx * NI_COUNT + NI_PLAIN_ITER_P1];
     return LPBOX_OK;
@@ -1263,7 +1212,7 @@ int lpbox_get_stop(lpbox_t *h, int idx, int *reason, int *plain_iter_plus1) {
 
 int lpbox_kernel_time(lpbox_t *h, double *ms_total, long long *launches, int reset) {
     if (valid_handle(h) && h->seg) return segc_kernel_time(h->seg, ms_total, launches, reset);
-    if (!valid_handle(h)) return fail(LPBOX_E_BADHANDLE, "bad handle");
+    if (!valid_handle(h)) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
     if (ms_total) *ms_total = h->kernel_ms;
     if (launches) *launches = h->launches;
     if (reset) { h->kernel_ms = 0.0; h->launches = 0; }
@@ -1274,14 +1223,14 @@ int lpbox_kernel_time(lpbox_t *h, double *ms_total, long long *launches, int res
 int lpbox_debug_get_lp_table(lpbox_t *h, int idx, const char *name, int *out, int cap) {
     int rc = check_idx(h, idx);
     if (rc) return rc;
-    if (h->seg) return fail(LPBOX_E_STATE, "this entry point belongs to the LP flavour");
-    if (!name || !out) return fail(LPBOX_E_BADARG, "null argument");
+    if (h->seg) return lpbox_fail(LPBOX_E_STATE, "this entry point belongs to the LP flavour");
+    if (!name || !out) return lpbox_fail(LPBOX_E_BADARG, "null argument");
     rc = plan(h);
     if (rc) return rc;
     const LpInstanceLayout &L = h->inst[idx].lay;
     const size_t NS = h->geo.NS, ZS = h->geo.ZS;
     auto give = [&](const auto &table, size_t stride, int fill) {
-        if ((size_t)cap < stride) return fail(LPBOX_E_BADARG, "buffer too small");
+        if ((size_t)cap < stride) return lpbox_fail(LPBOX_E_BADARG, "buffer too small");
         for (size_t q = 0; q < stride; q++) out[q] = q < table.size() ? (int)table[q] : fill;
         return (int)stride;
     };
@@ -1294,15 +1243,15 @@ int lpbox_debug_get_lp_table(lpbox_t *h, int idx, const char *name, int *out, in
     if (!strcmp(name, "rgl")) return give(L.rgl, NS, 0);
     if (!strcmp(name, "rmeta")) return give(L.rmeta, NS, 0x10);
     if (!strcmp(name, "cmeta")) return give(L.cmeta, NS, 0);
-    return fail(LPBOX_E_BADARG, "unknown table '%s'", name);
+    return lpbox_fail(LPBOX_E_BADARG, "unknown table '%s'", name);
 }
 
 int lpbox_debug_get_vec(lpbox_t *h, int idx, const char *name, double *out, int cap) {
     if (valid_handle(h) && h->seg) return segc_debug_vec(h->seg, name, out, cap);
     int rc = check_idx(h, idx);
     if (rc) return rc;
-    if (!h->inited || !name || !out) return fail(LPBOX_E_STATE, "not initialised");
-    rc = use_device(h);
+    if (!h->inited || !name || !out) return lpbox_fail(LPBOX_E_STATE, "not initialised");
+    rc = use_device(h->device);
     if (rc) return rc;
     const LpInstance &I = h->inst[idx];
     const double *pool = nullptr; size_t stride = h->geo.NS; int len = I.n; bool by_var = true;
@@ -1314,19 +1263,19 @@ int lpbox_debug_get_vec(lpbox_t *h, int idx, const char *name, double *out, int 
     else if (!strcmp(name, "z4")) { pool = h->z4.p; stride = h->geo.LS; len = I.l; by_var = false; }
     else if (!strcmp(name, "f")) { pool = h->f.p; stride = h->geo.LS; len = I.l; by_var = false; }
     else if (!strcmp(name, "r4v")) {     // valued reference-order batches: the entries of rho4_E_transpose, CSC entry order
-        if (!h->valued) return fail(LPBOX_E_BADARG, "no stored values in this batch");
-        if (I.nnz > cap) return fail(LPBOX_E_BADARG, "buffer too small");
+        if (!h->valued) return lpbox_fail(LPBOX_E_BADARG, "no stored values in this batch");
+        if (I.nnz > cap) return lpbox_fail(LPBOX_E_BADARG, "buffer too small");
         HIPCHK(hipMemcpy(out, h->r4v.p + (size_t)idx * h->geo.ZS, sizeof(double) * (size_t)I.nnz, hipMemcpyDeviceToHost));
         return I.nnz;
     }
     else if (!strcmp(name, "live")) {
         std::vector<uint8_t> live;
         if ((rc = fetch_live(h, idx, live))) return rc;
-        if (I.n > cap) return fail(LPBOX_E_BADARG, "buffer too small");
+        if (I.n > cap) return lpbox_fail(LPBOX_E_BADARG, "buffer too small");
         for (int j = 0; j < I.n; j++) out[j] = live[j];
         return I.n;
-    } else return fail(LPBOX_E_BADARG, "unknown vector '%s'", name);
-    if (len > cap) return fail(LPBOX_E_BADARG, "buffer too small");
+    } else return lpbox_fail(LPBOX_E_BADARG, "unknown vector '%s'", name);
+    if (len > cap) return lpbox_fail(LPBOX_E_BADARG, "buffer too small");
     std::vector<double> v;
     if ((rc = fetch_vec(h, pool, stride, idx, len, v, by_var))) return rc;
     memcpy(out, v.data(), sizeof(double) * (size_t)len);
@@ -1337,7 +1286,7 @@ int lpbox_debug_get_vec(lpbox_t *h, int idx, const char *name, double *out, int 
 int lpbox_debug_get_stamps(lpbox_t *h, int idx, unsigned long long *out16) {
     int rc = check_idx(h, idx);
     if (rc) return rc;
-    if (!h->stamps.p) return fail(LPBOX_E_UNSUPPORTED, "library built without LPBOX_STAMPS");
+    if (!h->stamps.p) return lpbox_fail(LPBOX_E_UNSUPPORTED, "library built without LPBOX_STAMPS");
     HIPCHK(hipMemcpy(out16, h->stamps.p + (size_t)idx * 16, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return LPBOX_OK;
 }
@@ -1346,7 +1295,7 @@ int lpbox_debug_get_scalar(lpbox_t *h, int idx, const char *name, double *out) {
     if (valid_handle(h) && h->seg) return segc_debug_scalar(h->seg, name, out);
     int rc = check_idx(h, idx);
     if (rc) return rc;
-    if (!h->inited || !name || !out) return fail(LPBOX_E_STATE, "not initialised");
+    if (!h->inited || !name || !out) return lpbox_fail(LPBOX_E_STATE, "not initialised");
     const double *d = &h->h_dsc[(size_t)idx * ND_COUNT];
     const int *q = &h->h_isc[(size_t)idx * NI_COUNT];
     struct { const char *n; double v; } tab[] = {
@@ -1357,20 +1306,20 @@ int lpbox_debug_get_scalar(lpbox_t *h, int idx, const char *name, double *out) {
         {"rhoUpdated", (double)q[NI_RHO_UPDATED]}, {"last_pcg", (double)q[NI_LAST_PCG]},
     };
     for (auto &e : tab) if (!strcmp(e.n, name)) { *out = e.v; return LPBOX_OK; }
-    return fail(LPBOX_E_BADARG, "unknown scalar '%s'", name);
+    return lpbox_fail(LPBOX_E_BADARG, "unknown scalar '%s'", name);
 }
 
 int lpbox_debug_block_sum(int threads, int nv, int stage, int groups, int rounds, const double *in, double *out) {
-    if (!in || !out || groups <= 0 || groups > 1024 || rounds <= 0 || rounds > 1024) return fail(LPBOX_E_BADARG, "lpbox_debug_block_sum: bad argument");
-    if (lpbox_device_count() < 1) return fail(LPBOX_E_NODEVICE, "no HIP device");
+    if (!in || !out || groups <= 0 || groups > 1024 || rounds <= 0 || rounds > 1024) return lpbox_fail(LPBOX_E_BADARG, "lpbox_debug_block_sum: bad argument");
+    if (lpbox_device_count() < 1) return lpbox_fail(LPBOX_E_NODEVICE, "no HIP device");
     HIPCHK(hipSetDevice(g_device));
     const size_t per = (size_t)rounds * threads * nv;
-    struct Scratch : DevBuf<double> { ~Scratch() { release(); } } din, dout;     // freed on every return path
+    DevBuf<double> din, dout;                                                    // freed on every return path
     HIPCHK(din.alloc(per));
     HIPCHK(dout.alloc(per * groups));
     HIPCHK(hipMemcpy(din.p, in, per * sizeof(double), hipMemcpyHostToDevice));
     hipError_t e = lp_launch_debug_block_sum(threads, nv, stage, groups, rounds, din.p, dout.p, nullptr);
-    if (e == hipErrorInvalidConfiguration) return fail(LPBOX_E_BADARG, "lpbox_debug_block_sum: no kernel for %d threads, %d values, stage %d", threads, nv, stage);
+    if (e == hipErrorInvalidConfiguration) return lpbox_fail(LPBOX_E_BADARG, "lpbox_debug_block_sum: no kernel for %d threads, %d values, stage %d", threads, nv, stage);
     HIPCHK(e);
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(out, dout.p, per * groups * sizeof(double), hipMemcpyDeviceToHost));
@@ -1379,8 +1328,8 @@ int lpbox_debug_block_sum(int threads, int nv, int stage, int groups, int rounds
 
 // ---- segmentation flavour (SEG pxd = Segmentation/Segmentation/cython/src/LPboxADMMsolver.pxd) ----
 static int seg_handle(lpbox_t *h) {
-    if (!valid_handle(h)) return fail(LPBOX_E_BADHANDLE, "bad handle");
-    if (!h->seg) return fail(LPBOX_E_STATE, "this entry point belongs to the segmentation flavour");
+    if (!valid_handle(h)) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
+    if (!h->seg) return lpbox_fail(LPBOX_E_STATE, "this entry point belongs to the segmentation flavour");
     return LPBOX_OK;
 }
 
@@ -1404,7 +1353,7 @@ int lpbox_seg_legacy(lpbox_t *h, int *energy) {
 }
 
 int lpbox_seg_legacy_batch(lpbox_t **hs, int count, int *energies) {
-    if (!hs || count <= 0) return fail(LPBOX_E_BADARG, "empty batch");
+    if (!hs || count <= 0) return lpbox_fail(LPBOX_E_BADARG, "empty batch");
     std::vector<SegSolver *> ss(count);
     for (int i = 0; i < count; i++) {
         int rc = seg_handle(hs[i]);
@@ -1416,11 +1365,11 @@ int lpbox_seg_legacy_batch(lpbox_t **hs, int count, int *energies) {
 
 // ---- early-fixing windows for a batch of segmentation handles (lpbox_seg_capi.hip) ----
 lpbox_seg_batch_t *lpbox_seg_batch_create(lpbox_t **hs, int count) {
-    if (!hs || count <= 0) { fail(LPBOX_E_BADARG, "empty batch"); return nullptr; }
+    if (!hs || count <= 0) { lpbox_fail(LPBOX_E_BADARG, "empty batch"); return nullptr; }
     std::vector<SegSolver *> ss(count);
     for (int i = 0; i < count; i++) {
-        if (!valid_handle(hs[i])) { fail(LPBOX_E_BADHANDLE, "problem %d of the batch is not a handle", i); return nullptr; }
-        if (!hs[i]->seg) { fail(LPBOX_E_STATE, "problem %d of the batch is an LP-flavour handle", i); return nullptr; }
+        if (!valid_handle(hs[i])) { lpbox_fail(LPBOX_E_BADHANDLE, "problem %d of the batch is not a handle", i); return nullptr; }
+        if (!hs[i]->seg) { lpbox_fail(LPBOX_E_STATE, "problem %d of the batch is an LP-flavour handle", i); return nullptr; }
         ss[i] = hs[i]->seg;
     }
     return segbc_create(ss.data(), count);                         // NULL: refused, lpbox_last_status() / lpbox_last_error() say why
@@ -1428,7 +1377,7 @@ lpbox_seg_batch_t *lpbox_seg_batch_create(lpbox_t **hs, int count) {
 
 void lpbox_seg_batch_destroy(lpbox_seg_batch_t *b) { segbc_destroy(b); }
 
-#define SEG_BATCH_OR_FAIL(b) do { if (!(b)) return fail(LPBOX_E_BADHANDLE, "bad batch handle"); } while (0)
+#define SEG_BATCH_OR_FAIL(b) do { if (!(b)) return lpbox_fail(LPBOX_E_BADHANDLE, "bad batch handle"); } while (0)
 int lpbox_seg_batch_init(lpbox_seg_batch_t *b) { SEG_BATCH_OR_FAIL(b); return segbc_init(b); }
 int lpbox_seg_batch_set_active(lpbox_seg_batch_t *b, const unsigned char *active) { SEG_BATCH_OR_FAIL(b); return segbc_set_active(b, active); }
 int lpbox_seg_batch_iterate_l2f(lpbox_seg_batch_t *b, int iter_start, int iter_end, const double *vecs, long vec_stride, const int *nums,

@@ -1,22 +1,16 @@
 // lpbox_genb_capi.hip -- host side + C-ABI (lpbox_bqp_batch_* in include/lpbox_hip.h) of the BATCH of small generic constrained
 // binary QPs: the reference's ADMM_bqp (SEGcpp:1384-1832) for many independent problems with max(n, m, l) <= 2048 at once, one
 // persistent workgroup each (lpbox_genb_kernels.hip).  Validation, presets and messages are those of the one-problem handle
-// (lpbox_gen_host.h); a problem gives the same bits here and through lpbox_bqp_*.
+// (lpbox_gen_host.h); a problem gives the same bits here and through lpbox_bqp_*.  Device buffers, timer and error-check macros: lpbox_host.h.
 #include "lpbox_gen_host.h"
 #include "lpbox_genb.h"
+#include "lpbox_host.h"
 
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
-
-#define HIPCHK(expr)                                                                                         \
-    do {                                                                                                     \
-        hipError_t e_ = (expr);                                                                              \
-        if (e_ != hipSuccess) return lpbox_fail(LPBOX_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-#define CHK(expr) do { int rc_ = (expr); if (rc_ < 0) return rc_; } while (0)
 
 namespace {
 constexpr int GENB_DEFAULT_WINDOW = 64;      // outer iterations per launch
@@ -30,34 +24,20 @@ struct lpbox_bqp_batch {
     bool ref = false;                        // LPBOX_ORDER_REFERENCE: the REF kernels, c1 through libm's pow
     int nmax = 0, mmax = 0, lmax = 0, slots = 2, window = GENB_DEFAULT_WINDOW;
     hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    int *ipool = nullptr; double *dpool = nullptr; GenbProb *dprob = nullptr; GenState *dst = nullptr;
+    StreamTimer timer;
+    DevBuf<int> ipool; DevBuf<double> dpool; DevBuf<GenbProb> dprob; DevBuf<GenState> dst;
     std::vector<GenbProb> hprob;             // the descriptors as uploaded (device pointers): the getters read through them
     std::vector<GenState> hst;
     double kernel_ms = 0.0; long long launches = 0;
 };
 
 namespace {
-int batch_device(lpbox_bqp_batch *h) {
-    int cnt = 0;
-    if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) return lpbox_fail(LPBOX_E_NODEVICE, "no HIP device available");
-    HIPCHK(hipSetDevice(h->device));
-    return LPBOX_OK;
-}
 // c1 = pow(n, 1/p), p = 2 (SEGcpp:556) through libm's pow, as the reference and the oracle call it: with the literal exponent the compiler
 // may turn the call into sqrt, and glibc's pow is not correctly rounded.  Reference order only (as ref_c1 of lpbox_big_capi.hip); no
 // n <= GENB_MAXDIM tells the two apart, the default order keeps the expression it has always had.
 double ref_c1(int n) {
     volatile double e = 1.0 / 2;
     return std::pow((double)n, e);
-}
-void release(lpbox_bqp_batch *h) {
-    if (h->ipool) (void)hipFree(h->ipool);
-    if (h->dpool) (void)hipFree(h->dpool);
-    if (h->dprob) (void)hipFree(h->dprob);
-    if (h->dst) (void)hipFree(h->dst);
-    h->ipool = nullptr; h->dpool = nullptr; h->dprob = nullptr; h->dst = nullptr;
-    h->uploaded = false;
 }
 int check_index(lpbox_bqp_batch *h, int idx, bool all_ok) {
     if (!h) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
@@ -68,7 +48,7 @@ int check_index(lpbox_bqp_batch *h, int idx, bool all_ok) {
 // Placement: every matrix and every vector of ADMM state goes into two pooled device arrays (ints, doubles), a slice per problem;
 // the kernel keeps only the gathered vectors (n + m + l doubles of the largest problem) in LDS, so there is no nnz limit.
 int upload(lpbox_bqp_batch *h) {
-    release(h);
+    h->uploaded = false;
     std::vector<int> ip; std::vector<double> dp;
     struct Off { size_t aptr, aidx, adiag, crp, cri, ccp, cci, erp, eri, ecp, eci, aval, tmval, crv, ccv, ccsv, erv, ecv, ecsv, x0, b, d, f, nvec, z3, lvec; };
     std::vector<Off> off(h->count);
@@ -90,18 +70,14 @@ int upload(lpbox_bqp_batch *h) {
         o.nvec = room_d((size_t)10 * p.n); o.z3 = room_d(p.m); o.lvec = room_d((size_t)4 * p.l);
     }
     h->slots = h->nmax <= 512 ? 2 : h->nmax <= 1024 ? 4 : 8;
-    HIPCHK(hipMalloc((void **)&h->ipool, std::max<size_t>(ip.size(), 1) * sizeof(int)));
-    HIPCHK(hipMalloc((void **)&h->dpool, std::max<size_t>(dp.size(), 1) * sizeof(double)));
-    HIPCHK(hipMalloc((void **)&h->dprob, sizeof(GenbProb) * (size_t)h->count));
-    HIPCHK(hipMalloc((void **)&h->dst, sizeof(GenState) * (size_t)h->count));
-    if (!ip.empty()) HIPCHK(hipMemcpy(h->ipool, ip.data(), ip.size() * sizeof(int), hipMemcpyHostToDevice));
-    if (!dp.empty()) HIPCHK(hipMemcpy(h->dpool, dp.data(), dp.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(h->ipool.upload(ip, 1)); HIPCHK(h->dpool.upload(dp, 1));     // (at least one element, as lpbox_gen_capi.hip)
+    HIPCHK(h->dprob.alloc((size_t)h->count)); HIPCHK(h->dst.alloc((size_t)h->count));
     h->hprob.assign(h->count, GenbProb());
     for (int i = 0; i < h->count; i++) {
         const BatchProblem &p = h->prob[i];
         const Off &o = off[i];
         GenbProb &g = h->hprob[i];
-        const int *I = h->ipool; double *D = h->dpool;
+        const int *I = h->ipool.p; double *D = h->dpool.p;
         g.n = p.n; g.m = p.m; g.l = p.l; g.eq = p.m > 0; g.ineq = p.l > 0; g.prm = p.prm;
         g.c1 = h->ref ? ref_c1(p.n) : std::pow((double)p.n, 1.0 / 2);                 // std::pow(n, 1.0 / p), p = 2 (SEGcpp:556)
         g.aptr = I + o.aptr; g.aidx = I + o.aidx; g.adiag = I + o.adiag; g.aval = D + o.aval; g.tmval = D + o.tmval;
@@ -116,7 +92,7 @@ int upload(lpbox_bqp_batch *h) {
         double *lv = D + o.lvec; const size_t l = (size_t)p.l;
         g.z4 = lv; g.y3 = lv + l; g.fy = lv + 2 * l; g.Ex = lv + 3 * l;
     }
-    HIPCHK(hipMemcpy(h->dprob, h->hprob.data(), sizeof(GenbProb) * (size_t)h->count, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->dprob.p, h->hprob.data(), sizeof(GenbProb) * (size_t)h->count, hipMemcpyHostToDevice));
     h->uploaded = true;
     return LPBOX_OK;
 }
@@ -140,9 +116,7 @@ void lpbox_bqp_batch_destroy(lpbox_bqp_batch_t *h) {
     if (!h) return;
     if (h->uploaded || h->stream) (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    release(h);
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
+    h->timer.destroy();
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
@@ -193,10 +167,10 @@ int lpbox_bqp_batch_set_order(lpbox_bqp_batch_t *h, int mode) {
 int lpbox_bqp_batch_solve(lpbox_bqp_batch_t *h, int *iterations) {                 // ADMM_bqp SEGcpp:1384-1832, every problem of the batch
     if (!h) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
     for (int i = 0; i < h->count; i++) if (!h->prob[i].set) return lpbox_fail(LPBOX_E_STATE, "no problem set at index %d", i);
-    CHK(batch_device(h));
+    CHK(use_device(h->device));
     if (!h->stream) {
         HIPCHK(hipStreamCreate(&h->stream));
-        HIPCHK(hipEventCreate(&h->ev0)); HIPCHK(hipEventCreate(&h->ev1));
+        HIPCHK(h->timer.create());
     }
     if (!h->uploaded) CHK(upload(h));
     if (h->ref) {                                            // the staging rows of the reference order must fit beside the gathered vectors
@@ -207,21 +181,17 @@ int lpbox_bqp_batch_solve(lpbox_bqp_batch_t *h, int *iterations) {              
     }
     h->kernel_ms = 0; h->launches = 0; h->solved = false;
     h->hst.assign(h->count, GenState());
-    HIPCHK(hipEventRecord(h->ev0, h->stream));
-    HIPCHK(genb_launch_init(h->dprob, h->dst, h->count, h->slots, h->nmax, h->ref, h->stream)); h->launches++;
+    HIPCHK(h->timer.start(h->stream));
+    HIPCHK(genb_launch_init(h->dprob.p, h->dst.p, h->count, h->slots, h->nmax, h->ref, h->stream)); h->launches++;
     for (;;) {
-        HIPCHK(genb_launch_window(h->dprob, h->dst, h->count, h->slots, h->window, h->nmax, h->mmax, h->lmax, h->ref, h->stream)); h->launches++;
-        HIPCHK(hipMemcpyAsync(h->hst.data(), h->dst, sizeof(GenState) * (size_t)h->count, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(genb_launch_window(h->dprob.p, h->dst.p, h->count, h->slots, h->window, h->nmax, h->mmax, h->lmax, h->ref, h->stream)); h->launches++;
+        HIPCHK(hipMemcpyAsync(h->hst.data(), h->dst.p, sizeof(GenState) * (size_t)h->count, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
         bool all = true;
         for (const GenState &s : h->hst) if (s.halt == GEN_HALT_NONE) { all = false; break; }
         if (all) break;
     }
-    HIPCHK(hipEventRecord(h->ev1, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    h->kernel_ms = ms;
+    HIPCHK(h->timer.stop_sync(h->stream, &h->kernel_ms));
     h->solved = true;
     if (iterations) for (int i = 0; i < h->count; i++) iterations[i] = h->hst[i].iter;
     return LPBOX_OK;
@@ -230,7 +200,7 @@ int lpbox_bqp_batch_solve(lpbox_bqp_batch_t *h, int *iterations) {              
 int lpbox_bqp_batch_get_vec(lpbox_bqp_batch_t *h, int idx, const char *name, double *out, long cap) {
     if (!h || !h->solved || !h->uploaded || !out || !name) return lpbox_fail(LPBOX_E_STATE, "not solved");
     CHK(check_index(h, idx, false));
-    CHK(batch_device(h));
+    CHK(use_device(h->device));
     const GenbProb &g = h->hprob[idx];
     const double *src = nullptr; long len = g.n;
     if (!strcmp(name, "x")) src = g.x; else if (!strcmp(name, "y1")) src = g.y1; else if (!strcmp(name, "y2")) src = g.y2;

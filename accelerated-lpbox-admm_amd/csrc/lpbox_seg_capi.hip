@@ -1,8 +1,11 @@
 // lpbox_seg_capi.hip -- host side of the SEGMENTATION flavour behind the C-ABI: image -> (A, b, c) cost construction
 // (SEGcpp:46-248, :705-756), device buffers, the graph-replayed iteration driver, early-fix index bookkeeping and getters.
-// All solver arithmetic runs in lpbox_seg_kernels.hip; there is no CPU fallback.
+// All solver arithmetic runs in lpbox_seg_kernels.hip; there is no CPU fallback.  What the launch chains decide (kmax, batches, the resume
+// limit) is in lpbox_chain.h; the driver of the single-problem chain, the graph cache, the device buffer, the timer and the error-check
+// macros are in lpbox_host.h.  The lockstep chain of a batch (batch_run_chain) keeps its own loop and takes its rules from lpbox_chain.h.
 #include "../../include/lpbox_hip.h"
 #include "lpbox_capi_internal.h"
+#include "lpbox_host.h"
 #include "lpbox_seg.h"
 
 #include <algorithm>
@@ -12,25 +15,18 @@
 #include <utility>
 #include <vector>
 
-#define HIPCHK(expr)                                                                                         \
-    do {                                                                                                     \
-        hipError_t e_ = (expr);                                                                              \
-        if (e_ != hipSuccess) return lpbox_fail(LPBOX_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
 namespace {
-template <typename Tp>
-struct Buf {
-    Tp *p = nullptr; size_t count = 0;
-    hipError_t alloc(size_t c) { release(); count = c; return c ? hipMalloc((void **)&p, c * sizeof(Tp)) : hipSuccess; }
-    void release() { if (p) (void)hipFree(p); p = nullptr; count = 0; }
-};
-constexpr int ITERS_PER_GRAPH = 4;
-static_assert(ITERS_PER_GRAPH % 2 == 0, "an iteration is an odd number of launches: an even count keeps the ping-pong parity");
-constexpr int SEG_KMAX_LIMIT = 24;
-// A PCG of at most SEG_PCG_MAXITERS iterations is complete after this many resumes of 16 pairs whatever kmax was: a chain that asks for
-// more is broken, and the host loops return an error instead of resuming for ever.
-constexpr int SEG_RESUME_LIMIT = SEG_PCG_MAXITERS / 16 + 2;
+static_assert(SEG_HALT_NONE == CHAIN_HALT_NONE && SEG_HALT_PCG_MORE == CHAIN_HALT_PCG_MORE, "lpbox_chain.h reads SegState::halt");
+static_assert(CHAIN_RULES_SEG.pcg_cap == SEG_PCG_MAXITERS, "the resume limit follows the PCG cap of the kernels");
+static_assert(CHAIN_RULES_SEG.iters_per_graph % 2 == 0, "an iteration is an odd number of launches: an even count keeps the ping-pong parity");
+constexpr int SEG_KMAX_LIMIT = CHAIN_RULES_SEG.kmax_cap;
+
+// the rules of a chain created now: LPBOX_SEG_KMARGIN overrides the spare groups (also for the lockstep chain of a batch)
+ChainRules seg_rules() {
+    ChainRules r = CHAIN_RULES_SEG;
+    if (const char *e = getenv("LPBOX_SEG_KMARGIN")) r.margin = std::max(0, atoi(e));
+    return r;
+}
 }  // namespace
 
 struct SegSolver {
@@ -45,22 +41,21 @@ struct SegSolver {
     bool dleft_valid = false;    // d_left holds the live list (false between an init and the first early-fixing window)
     long win_serial = 0;         // inits and early-fixing windows run so far (a batch's packed rows belong to one of them)
     bool has_problem = false, uploaded = false, inited = false, xi_valid = false;
-    int G = 0, EPT = 2, kmax = 10, parity = 0;
+    int G = 0, EPT = 2, parity = 0;
     hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    // one instantiated graph (ITERS_PER_GRAPH iterations) per launch count kmax and start parity
-    hipGraph_t graph[SEG_KMAX_LIMIT + 1][2] = {}; hipGraphExec_t gexec[SEG_KMAX_LIMIT + 1][2] = {};
-    bool adaptive = true;
-    double kernel_ms = 0.0; long long launches = 0;
-    long long pcg_resumes = 0;   // SEG_HALT_PCG_MORE seen by the host loops on this handle's state since solve_init
-    Buf<int> d_ecol, d_left;
-    Buf<uint8_t> d_rowlen;
+    StreamTimer timer;
+    ChainController chain{seg_rules()};   // kmax; pcg_resumes: SEG_HALT_PCG_MORE seen by the host loops on this handle's state since solve_init
+    GraphCache graphs;
+    bool use_graph = getenv("LPBOX_SEG_NOGRAPH") == nullptr;     // eager launches (profilers that dislike graphs)
+    double kernel_ms = 0.0; long long launches = 0, collectives = 0;   // (no collectives on this path)
+    DevBuf<int> d_ecol, d_left;
+    DevBuf<uint8_t> d_rowlen;
     int ell_w = 0;
     bool dia = false; int doff[7] = {0, 0, 0, 0, 0, 0, 0};      // diagonal storage of the matrix (SegDev::dia), chosen by upload()
-    Buf<unsigned long long> d_dpack; Buf<double> d_adiag;
-    Buf<double> d_eval, x, y1, y2, z1, z2, b, rhs, r, z, tmp, dinv, td, p0, p1, part, xhist, xi_out;
-    Buf<uint8_t> live, fixval, newfix;
-    Buf<SegState> st;
+    DevBuf<unsigned long long> d_dpack; DevBuf<double> d_adiag;
+    DevBuf<double> d_eval, x, y1, y2, z1, z2, b, rhs, r, z, tmp, dinv, td, p0, p1, part, xhist, xi_out;
+    DevBuf<uint8_t> live, fixval, newfix;
+    DevBuf<SegState> st;
     int ws_cap = 0, last_ws = 0;
     int record = 0;        // legacy loop keeps x of up to `record` iterations (lpbox_set_record; print_info 1, SEGcpp:1209-1213,1270-1277)
     int rec_cols = 0;      // iterations the last legacy solve recorded
@@ -81,13 +76,6 @@ struct SegSolver {
 };
 
 namespace {
-
-int use_device(SegSolver *s) {
-    int cnt = 0;
-    if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) return lpbox_fail(LPBOX_E_NODEVICE, "no HIP device available");
-    HIPCHK(hipSetDevice(s->device));
-    return LPBOX_OK;
-}
 
 // cv::resize(src, dst, Size(), scale, scale) with INTER_LINEAR on 8-bit data (SEGcpp:705-714), following OpenCV 4.4's
 // fixed-point scheme: 11-bit coefficients, horizontal pass in int, vertical pass (((b0*(S0>>4))>>16) + ((b1*(S1>>4))>>16) + 2) >> 2
@@ -225,7 +213,7 @@ bool as_diagonals(const SegSolver *s, int (&doff)[7], std::vector<unsigned long 
 }
 
 int upload(SegSolver *s) {
-    int rc = use_device(s);
+    int rc = use_device(s->device);
     if (rc) return rc;
     const int n = s->n;
     s->EPT = 2;
@@ -234,7 +222,7 @@ int upload(SegSolver *s) {
     s->G = (n + SEG_T * s->EPT - 1) / (SEG_T * s->EPT);
     if (s->G > 2 * SEG_T) return lpbox_fail(LPBOX_E_UNSUPPORTED, "n = %d is beyond the two-level reduction of the segmentation kernels", n);
     if (!s->stream) HIPCHK(hipStreamCreate(&s->stream));
-    if (!s->ev0) { HIPCHK(hipEventCreate(&s->ev0)); HIPCHK(hipEventCreate(&s->ev1)); }
+    HIPCHK(s->timer.create());
     int w = 0;
     for (int i = 0; i < n; i++) w = std::max(w, s->rowptr[i + 1] - s->rowptr[i]);
     if (w > 255) return lpbox_fail(LPBOX_E_UNSUPPORTED, "a row of A stores %d entries; the ELL layout of the segmentation kernels holds at most 255", w);
@@ -251,7 +239,7 @@ int upload(SegSolver *s) {
         HIPCHK(s->d_ecol.alloc((size_t)w * n)); HIPCHK(s->d_eval.alloc((size_t)w * n));
     }
     HIPCHK(s->d_rowlen.alloc(n)); HIPCHK(s->d_left.alloc(n));
-    for (Buf<double> *bp : {&s->x, &s->y1, &s->y2, &s->z1, &s->z2, &s->b, &s->rhs, &s->r, &s->z, &s->tmp, &s->dinv, &s->td, &s->p0, &s->p1})
+    for (DevBuf<double> *bp : {&s->x, &s->y1, &s->y2, &s->z1, &s->z2, &s->b, &s->rhs, &s->r, &s->z, &s->tmp, &s->dinv, &s->td, &s->p0, &s->p1})
         HIPCHK(bp->alloc(n));
     HIPCHK(s->live.alloc(n)); HIPCHK(s->fixval.alloc(n)); HIPCHK(s->newfix.alloc(n));
     HIPCHK(s->part.alloc((size_t)5 * SEG_NPART * s->G)); HIPCHK(s->st.alloc(2));
@@ -281,77 +269,38 @@ int read_state(SegSolver *s) {
     return LPBOX_OK;
 }
 
-// one hipGraph = ITERS_PER_GRAPH (even) outer iterations of 3 + 2 kmax launches: an even number of launches, so the state ping-pong
-// parity is preserved across replays
-int ensure_graph(SegSolver *s) {
-    if (s->gexec[s->kmax][s->parity]) return LPBOX_OK;
-    int par = s->parity;
-    HIPCHK(hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
-    hipError_t e = seg_enqueue_iterations(s->dev(), ITERS_PER_GRAPH, s->kmax, &par, s->stream);
-    hipError_t e2 = hipStreamEndCapture(s->stream, &s->graph[s->kmax][s->parity]);
-    if (e != hipSuccess || e2 != hipSuccess) return lpbox_fail(LPBOX_E_HIP, "graph capture failed: %s", hipGetErrorString(e != hipSuccess ? e : e2));
-    HIPCHK(hipGraphInstantiate(&s->gexec[s->kmax][s->parity], s->graph[s->kmax][s->parity], nullptr, nullptr, 0));
-    return LPBOX_OK;
-}
-
-void drop_graphs(SegSolver *s) {
-    for (int k = 0; k <= SEG_KMAX_LIMIT; k++) for (int p = 0; p < 2; p++) {
-        if (s->gexec[k][p]) { (void)hipGraphExecDestroy(s->gexec[k][p]); s->gexec[k][p] = nullptr; }
-        if (s->graph[k][p]) { (void)hipGraphDestroy(s->graph[k][p]); s->graph[k][p] = nullptr; }
-    }
-}
-
 // run iterations up to iter_end (the window must already be set); returns when stopped / window done / all fixed.
 // Each batch enqueues kmax (matvec, update) pairs per outer iteration; kernels fall through once the PCG has converged, so
-// kmax only has to cover the iteration counts seen recently (pcg_max of the previous batch + 2); a batch that runs out of
-// pairs halts itself (SEG_HALT_PCG_MORE) and is resumed here.
-int run_window(SegSolver *s, int iter_end) {
-    static const bool nograph = getenv("LPBOX_SEG_NOGRAPH") != nullptr;   // eager launches (profilers that dislike graphs)
-    // spare (matvec, update) pairs per iteration beyond the largest PCG count of the previous batch of <= 32 iterations.  A spare pair
-    // is a launch that falls through (~3 us); a PCG that needs more than was enqueued halts the chain and is resumed (a host round
-    // trip).  Measured over 100 images at 10^4 nodes and the full-resolution one: 0 spare pairs 8 % / 7 % faster than 2, 1 in between
-    // -- the counts drift slowly, misses are rare.  LPBOX_SEG_KMARGIN overrides (also for the multi-problem chain, which defaults to 2:
-    // there one late problem stalls all).
-    static const int kmargin = getenv("LPBOX_SEG_KMARGIN") ? std::max(0, atoi(getenv("LPBOX_SEG_KMARGIN"))) : 0;
-    HIPCHK(hipEventRecord(s->ev0, s->stream));
-    int resumed = 0;                                                       // resumes since an outer iteration last completed
-    for (;;) {
-        int rc = read_state(s);
-        if (rc) return rc;
-        if (s->hst.halt == SEG_HALT_PCG_MORE) {
-            if (++resumed > SEG_RESUME_LIMIT)
-                return lpbox_fail(LPBOX_E_STATE, "iteration %d: the PCG is still halted at k = %d after %d resumes in a row", s->hst.iter, s->hst.pcg_k, resumed - 1);
-            s->pcg_resumes++;
-            HIPCHK(seg_enqueue_pcg_more(s->dev(), 16, &s->parity, s->stream));
-            s->launches += 34;
-            if (s->adaptive) s->kmax = std::min(SEG_KMAX_LIMIT, std::max(s->kmax, s->hst.pcg_k + 4));
-            continue;
-        }
-        if (s->hst.halt != SEG_HALT_NONE) break;
-        resumed = 0;
-        const int remaining = iter_end - s->hst.iter;
-        if (remaining <= 0 && !s->hst.have_prev) break;
-        // (pcg_max == 0: no PCG completed in the previous batch -- it only finalised an iteration that had been resumed -- so there is
-        //  nothing to track and kmax stays; it used to fall to 2 here, and the next window began with a halt)
-        if (s->adaptive && s->hst.outer_total > 0 && s->hst.pcg_max > 0) s->kmax = std::min(SEG_KMAX_LIMIT, std::max(2, s->hst.pcg_max + kmargin));
+// kmax only has to cover the iteration counts seen recently; a batch that runs out of pairs halts itself (SEG_HALT_PCG_MORE)
+// and is resumed (chain_run).  One hipGraph = 4 outer iterations of 3 + 2 kmax launches: an even number of launches, so the
+// state ping-pong parity is preserved across replays.  The enqueue helpers of the kernels file do not count: launches by formula.
+struct SegChainOps {
+    SegSolver *s;
+    int read_state(ChainView &v) { CHK(::read_state(s)); v = chain_view(s->hst); return LPBOX_OK; }
+    int resume_pcg() {
+        HIPCHK(seg_enqueue_pcg_more(s->dev(), CHAIN_PAIRS_PER_RESUME, &s->parity, s->stream));
+        s->launches += 2 + 2 * CHAIN_PAIRS_PER_RESUME;
+        return LPBOX_OK;
+    }
+    int batch_head() {
         HIPCHK(seg_launch_copy(s->dev(), 1, &s->parity, s->stream));       // pcg_max = 0 for the coming batch
         HIPCHK(seg_enqueue_prep(s->dev(), &s->parity, s->stream));         // head of the batch (inside it post + yrhs do prep's work)
         s->launches += 2;
-        const int per_launch = 3 + 2 * s->kmax;
-        int batch = std::min(std::max(remaining, 0), 32);
-        if (!nograph) { rc = ensure_graph(s); if (rc) return rc; }
-        while (!nograph && batch >= ITERS_PER_GRAPH) {
-            HIPCHK(hipGraphLaunch(s->gexec[s->kmax][s->parity], s->stream));
-            batch -= ITERS_PER_GRAPH; s->launches += (long long)ITERS_PER_GRAPH * per_launch;
-        }
-        if (batch > 0) { HIPCHK(seg_enqueue_iterations(s->dev(), batch, s->kmax, &s->parity, s->stream)); s->launches += (long long)batch * per_launch; }
-        HIPCHK(seg_enqueue_finalize(s->dev(), &s->parity, s->stream));
-        s->launches += 1;
+        return LPBOX_OK;
     }
-    HIPCHK(hipEventRecord(s->ev1, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, s->ev0, s->ev1));
+    int enqueue(int n) {
+        HIPCHK(seg_enqueue_iterations(s->dev(), n, s->chain.kmax, &s->parity, s->stream));
+        s->launches += (long long)n * (3 + 2 * s->chain.kmax);
+        return LPBOX_OK;
+    }
+    int finalize() { HIPCHK(seg_enqueue_finalize(s->dev(), &s->parity, s->stream)); s->launches += 1; return LPBOX_OK; }
+};
+
+int run_window(SegSolver *s, int iter_end) {
+    HIPCHK(s->timer.start(s->stream));
+    CHK(chain_run(s->chain, s->graphs, ChainIo{s->stream, s->parity, s->launches, s->collectives, s->use_graph, true}, iter_end, SegChainOps{s}));
+    double ms = 0.0;
+    HIPCHK(s->timer.stop_sync(s->stream, &ms));
     s->kernel_ms += ms;
     return LPBOX_OK;
 }
@@ -368,13 +317,13 @@ int refresh_left(SegSolver *s) {
 
 // the host side of segc_init for a member of a batch: upload, b, identity live list (the init KERNEL runs batched)
 int batch_reset_handle(SegSolver *s) {
-    int rc = s->uploaded ? use_device(s) : upload(s);
+    int rc = s->uploaded ? use_device(s->device) : upload(s);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(s->b.p, s->orgb.data(), sizeof(double) * (size_t)s->n, hipMemcpyHostToDevice, s->stream));
     s->left_idx.resize(s->n);
     for (int k = 0; k < s->n; k++) s->left_idx[k] = k;
     s->left_stale = false; s->dleft_valid = false; s->win_serial++;
-    s->pcg_resumes = 0;
+    s->chain.pcg_resumes = 0;
     return LPBOX_OK;
 }
 
@@ -382,23 +331,19 @@ int batch_reset_handle(SegSolver *s) {
 // problem, each on its own control state -- one that has stopped, is all fixed or whose PCG has converged falls through, a
 // SEG_HALT_PCG_MORE on any problem resumes the chain.  hs[B] receives the final states; *kmax carries the adaptive launch count;
 // resumes[B] is raised for every problem whose own state showed the halt at a resume.
-int batch_run_chain(const SegDev *devs, SegState *dstates, int B, int Gmax, int iter_end, int *parity, int *kmax, bool adaptive,
-                    SegState *hs, long long *launches, long long *resumes, hipStream_t st) {
-    // spare (matvec, update) pairs per iteration beyond the largest PCG count any problem showed in the previous batch of iterations: 0, as
-    // in the single-problem chain (a miss halts that problem's PCG and the chain resumes it).  Measured, 100 problems at 10^4 nodes, fastest
-    // / median of five runs: margin 2 119 / 120 ms, margin 1 111 / 112 ms, margin 0 108 / 108 ms; 16 problems 46 -> 41 ms.
-    static const int bmargin = getenv("LPBOX_SEG_KMARGIN") ? std::max(0, atoi(getenv("LPBOX_SEG_KMARGIN"))) : 0;
+int batch_run_chain(const ChainRules &rules, const SegDev *devs, SegState *dstates, int B, int Gmax, int iter_end, int *parity, int *kmax,
+                    bool adaptive, SegState *hs, long long *launches, long long *resumes, hipStream_t st) {
     std::vector<int> resumed(B, 0);                                 // per problem: resumes since one of its outer iterations last completed
     for (;;) {
         HIPCHK(segb_collect_states(devs, B, *parity, dstates, st));
         HIPCHK(hipMemcpyAsync(hs, dstates, sizeof(SegState) * (size_t)B, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         bool more = false, any_run = false;
-        int remaining = 0, pcg_max = 0, pcg_k = 0;
+        int remaining = 0, vote = 0, pcg_k = 0;
         for (int i = 0; i < B; i++) {
             const SegState &h = hs[i];
             if (h.halt == SEG_HALT_PCG_MORE) {
-                if (++resumed[i] > SEG_RESUME_LIMIT)
+                if (++resumed[i] > rules.resume_limit())
                     return lpbox_fail(LPBOX_E_STATE, "problem %d of the batch, iteration %d: the PCG is still halted at k = %d after %d resumes in a row", i, h.iter, h.pcg_k, resumed[i] - 1);
                 resumes[i]++; more = true; pcg_k = std::max(pcg_k, h.pcg_k);
                 continue;
@@ -407,22 +352,21 @@ int batch_run_chain(const SegDev *devs, SegState *dstates, int B, int Gmax, int 
             if (h.halt != SEG_HALT_NONE) continue;
             const int rem = iter_end - h.iter;
             if (rem <= 0 && !h.have_prev) continue;
-            // (pcg_max == 0: this problem completed no PCG in the previous batch, which only finalised a resumed iteration or was not
-            //  its own: nothing to track, it votes for the kmax in use -- it used to vote 0, and a window after one whose last iteration
-            //  had been resumed began at kmax = 2, with a halt of every problem)
+            // (a problem that completed no PCG in the previous batch -- which only finalised a resumed iteration or was not its own --
+            //  votes for the kmax in use: chain_pcg_vote)
             any_run = true; remaining = std::max(remaining, rem);
-            pcg_max = std::max(pcg_max, h.outer_total > 0 && h.pcg_max > 0 ? h.pcg_max : *kmax - bmargin);
+            vote = std::max(vote, chain_pcg_vote(rules, *kmax, chain_view(h)));
         }
         if (more) {                                                 // some PCG ran out of launches: resume it (the others fall through)
-            HIPCHK(segb_enqueue_pcg_more(devs, B, Gmax, 16, parity, st));
-            *launches += 34;
-            if (adaptive) *kmax = std::min(SEG_KMAX_LIMIT, std::max(*kmax, pcg_k + 4));
+            HIPCHK(segb_enqueue_pcg_more(devs, B, Gmax, CHAIN_PAIRS_PER_RESUME, parity, st));
+            *launches += 2 + 2 * CHAIN_PAIRS_PER_RESUME;
+            if (adaptive) *kmax = chain_kmax_after_halt(rules, *kmax, pcg_k);
             continue;
         }
         if (!any_run) break;
-        if (adaptive) *kmax = std::min(SEG_KMAX_LIMIT, std::max(2, pcg_max + bmargin));
+        if (adaptive) *kmax = chain_kmax_for_vote(rules, vote);
         HIPCHK(segb_launch_copy(devs, B, 1, parity, st));
-        const int batch = std::min(std::max(remaining, 0), 32);
+        const int batch = chain_batch_iters(rules, remaining);
         if (batch > 0) HIPCHK(segb_enqueue_iterations(devs, B, Gmax, batch, *kmax, parity, st));
         HIPCHK(segb_enqueue_finalize(devs, B, Gmax, parity, st));
         *launches += 2 + (long long)batch * (4 + 2 * *kmax);
@@ -436,7 +380,7 @@ SegSolver *segc_create(int print_info, int device) {
     SegSolver *s = new SegSolver();
     s->print_info = print_info; s->device = device;
     memset(&s->hst, 0, sizeof(s->hst));
-    if (const char *e = getenv("LPBOX_SEG_KMAX")) { int v = atoi(e); if (v >= 1 && v <= SEG_KMAX_LIMIT) { s->kmax = v; s->adaptive = false; } }
+    if (const char *e = getenv("LPBOX_SEG_KMAX")) { int v = atoi(e); if (v >= 1 && v <= SEG_KMAX_LIMIT) s->chain.force_kmax(v); }
     return s;
 }
 
@@ -444,14 +388,8 @@ void segc_destroy(SegSolver *s) {
     if (!s) return;
     if (s->uploaded) (void)hipSetDevice(s->device);
     if (s->stream) (void)hipStreamSynchronize(s->stream);
-    drop_graphs(s);
-    s->d_ecol.release(); s->d_rowlen.release(); s->d_left.release(); s->d_eval.release(); s->d_dpack.release(); s->d_adiag.release();
-    for (Buf<double> *bp : {&s->x, &s->y1, &s->y2, &s->z1, &s->z2, &s->b, &s->rhs, &s->r, &s->z, &s->tmp, &s->dinv, &s->td, &s->p0, &s->p1,
-                            &s->part, &s->xhist, &s->xi_out})
-        bp->release();
-    s->live.release(); s->fixval.release(); s->newfix.release(); s->st.release();
-    if (s->ev0) (void)hipEventDestroy(s->ev0);
-    if (s->ev1) (void)hipEventDestroy(s->ev1);
+    s->graphs.clear();
+    s->timer.destroy();
     if (s->stream) (void)hipStreamDestroy(s->stream);
     delete s;
 }
@@ -493,13 +431,13 @@ int segc_set_image(SegSolver *s, const unsigned char *gray, int rows, int cols, 
 
 int segc_init(SegSolver *s) {
     if (!s->has_problem) return lpbox_fail(LPBOX_E_STATE, "no problem set");
-    int rc = s->uploaded ? use_device(s) : upload(s);
+    int rc = s->uploaded ? use_device(s->device) : upload(s);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(s->b.p, s->orgb.data(), sizeof(double) * (size_t)s->n, hipMemcpyHostToDevice, s->stream));
     s->left_idx.resize(s->n);
     for (int i = 0; i < s->n; i++) s->left_idx[i] = i;
     s->left_stale = false; s->dleft_valid = false; s->win_serial++;
-    s->xi_valid = false; s->parity = 0; s->pcg_resumes = 0;
+    s->xi_valid = false; s->parity = 0; s->chain.pcg_resumes = 0;
     HIPCHK(seg_launch_init(s->dev(), std::pow((double)s->n, 1.0 / 2), s->stream));    // pow(n, 1/p), p = 2 (SEGcpp:557,670)
     rc = read_state(s);
     if (rc) return rc;
@@ -509,11 +447,11 @@ int segc_init(SegSolver *s) {
 
 int segc_legacy(SegSolver *s, int *energy) {                                  // ADMM_bqp_unconstrained_legacy SEGcpp:1200-1380
     if (!s->inited) return lpbox_fail(LPBOX_E_STATE, "solve_init has not been called");
-    int rc = use_device(s);
+    int rc = use_device(s->device);
     if (rc) return rc;
     if (s->record > 0 && (!s->xhist.p || s->ws_cap < s->record)) {
         HIPCHK(hipStreamSynchronize(s->stream));
-        HIPCHK(s->xhist.alloc((size_t)s->record * s->n)); s->ws_cap = s->record; drop_graphs(s);
+        HIPCHK(s->xhist.alloc((size_t)s->record * s->n)); s->ws_cap = s->record; s->graphs.clear();
         HIPCHK(hipMemsetAsync(s->xhist.p, 0, sizeof(double) * (size_t)s->ws_cap * s->n, s->stream));
     }
     HIPCHK(seg_launch_set_window(s->dev(), 0, SEG_MAX_ITERS, s->record > 0 ? 2 : 0, &s->parity, s->stream));
@@ -551,27 +489,24 @@ int segc_legacy_batch(SegSolver **ss, int B, int *energies) {
     hipStream_t st = s0->stream;
     std::vector<SegDev> hd(B);
     for (int i = 0; i < B; i++) hd[i] = ss[i]->dev();
-    Buf<SegDev> devs; Buf<SegState> dstates;
-    struct Release { Buf<SegDev> &a; Buf<SegState> &b; ~Release() { a.release(); b.release(); } } release_on_exit{devs, dstates};
+    DevBuf<SegDev> devs; DevBuf<SegState> dstates;
     HIPCHK(devs.alloc(B)); HIPCHK(dstates.alloc(B));
     HIPCHK(hipMemcpyAsync(devs.p, hd.data(), sizeof(SegDev) * (size_t)B, hipMemcpyHostToDevice, st));
     std::vector<SegState> hs(B);
-    int parity = 0, kmax = s0->kmax;
+    int parity = 0, kmax = s0->chain.kmax;
     long long launches = 0;
     std::vector<long long> resumes(B, 0);
-    HIPCHK(hipEventRecord(s0->ev0, st));
+    HIPCHK(s0->timer.start(st));
     HIPCHK(segb_launch_init(devs.p, B, Gmax, st));
     HIPCHK(segb_launch_set_window(devs.p, B, 0, SEG_MAX_ITERS, 0, &parity, st));
     launches += 2;
-    if ((rc = batch_run_chain(devs.p, dstates.p, B, Gmax, SEG_MAX_ITERS, &parity, &kmax, s0->adaptive, hs.data(), &launches, resumes.data(), st))) return rc;
-    HIPCHK(hipEventRecord(s0->ev1, st));
-    HIPCHK(hipStreamSynchronize(st));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, s0->ev0, s0->ev1));
+    if ((rc = batch_run_chain(s0->chain.rules, devs.p, dstates.p, B, Gmax, SEG_MAX_ITERS, &parity, &kmax, s0->chain.adaptive, hs.data(), &launches, resumes.data(), st))) return rc;
+    double ms = 0.0;
+    HIPCHK(s0->timer.stop_sync(st, &ms));
     for (int i = 0; i < B; i++) {
         SegSolver *s = ss[i];
         s->hst = hs[i]; s->parity = parity; s->rec_cols = 0; s->xi_valid = false; s->inited = true;
-        s->pcg_resumes += resumes[i];
+        s->chain.pcg_resumes += resumes[i];
         if (energies) energies[i] = (int)(s->hst.cur_obj + s->c);     // :1379
     }
     s0->kernel_ms += ms; s0->launches += launches;
@@ -582,7 +517,7 @@ int segc_l2f(SegSolver *s, int iter_start, int iter_end, const double *vec, int 
     if (!s->inited) return lpbox_fail(LPBOX_E_STATE, "solve_init has not been called");
     const int ws = iter_end - iter_start;
     if (ws > SEG_XITERS_COLS) return lpbox_fail(LPBOX_E_BADARG, "window of %d iterations exceeds the %d columns of x_iters (SEGcpp:924)", ws, SEG_XITERS_COLS);
-    int rc = use_device(s);
+    int rc = use_device(s->device);
     if (rc) return rc;
     if ((rc = refresh_left(s))) return rc;
     const int n_live = (int)s->left_idx.size();
@@ -609,7 +544,7 @@ int segc_l2f(SegSolver *s, int iter_start, int iter_end, const double *vec, int 
     s->xi_rows = n_live - num; s->xi_left_idx = s->left_idx;
     if (ws > 0 && (!s->xhist.p || s->ws_cap < ws)) {
         HIPCHK(hipStreamSynchronize(s->stream));
-        HIPCHK(s->xhist.alloc((size_t)SEG_XITERS_COLS * s->n)); s->ws_cap = SEG_XITERS_COLS; drop_graphs(s);
+        HIPCHK(s->xhist.alloc((size_t)SEG_XITERS_COLS * s->n)); s->ws_cap = SEG_XITERS_COLS; s->graphs.clear();
     }
     if (s->ws_cap > 0 && s->xhist.p) HIPCHK(hipMemsetAsync(s->xhist.p, 0, sizeof(double) * (size_t)s->ws_cap * s->n, s->stream));   // x_iters = Zero (SEGcpp:924): ALL staged columns, also those of an earlier, longer window
     s->rec_cols = 0;
@@ -636,7 +571,7 @@ int segc_get_x_history(SegSolver *s, int first, int count, double *out) {     //
     if (!out) return s->rec_cols;
     if (first < 0 || count < 0 || first + count > s->rec_cols)
         return lpbox_fail(LPBOX_E_BADARG, "iterations [%d,%d) outside the %d recorded", first, first + count, s->rec_cols);
-    int rc = use_device(s);
+    int rc = use_device(s->device);
     if (rc) return rc;
     if (count) HIPCHK(hipMemcpy(out, s->xhist.p + (size_t)first * s->n, sizeof(double) * (size_t)count * s->n, hipMemcpyDeviceToHost));
     return count;
@@ -647,7 +582,7 @@ int segc_get_x_iters(SegSolver *s, int ws, double *out) {                     //
     if (ws < 0 || ws > SEG_XITERS_COLS) return lpbox_fail(LPBOX_E_BADARG, "ws = %d outside [0,%d]", ws, SEG_XITERS_COLS);
     const int rows = s->xi_rows;
     if (!out || rows == 0 || ws == 0) return rows;
-    int rc = use_device(s);
+    int rc = use_device(s->device);
     if (rc) return rc;
     if (s->xi_out.count < (size_t)rows * ws) HIPCHK(s->xi_out.alloc((size_t)s->n * SEG_XITERS_COLS));
     HIPCHK(seg_launch_pack_xiters(s->dev(), s->d_left.p, rows, ws, s->xi_out.p, s->stream));
@@ -660,7 +595,7 @@ int segc_get_x_iters(SegSolver *s, int ws, double *out) {                     //
 int segc_get_x_iters_device(SegSolver *s, int ws, void **dev_ptr, long *stride) {
     if (!s->xi_valid) return lpbox_fail(LPBOX_E_STATE, "solve_iter_l2f has not been called");
     if (ws <= 0 || ws > SEG_XITERS_COLS) return lpbox_fail(LPBOX_E_BADARG, "ws = %d outside (0,%d]", ws, SEG_XITERS_COLS);
-    int rc = use_device(s);
+    int rc = use_device(s->device);
     if (rc) return rc;
     const int rows = s->xi_rows;
     if (s->xi_out.count < (size_t)std::max(rows, 1) * ws) HIPCHK(s->xi_out.alloc((size_t)s->n * SEG_XITERS_COLS));
@@ -683,7 +618,7 @@ static int fetch_solution(SegSolver *s, std::vector<double> &sol) {            /
 
 int segc_get_x_sol(SegSolver *s, double *out) {
     if (!s->inited || !out) return lpbox_fail(LPBOX_E_STATE, "not initialised");
-    int rc = use_device(s);
+    int rc = use_device(s->device);
     if (rc) return rc;
     std::vector<double> sol;
     if ((rc = fetch_solution(s, sol))) return rc;
@@ -693,7 +628,7 @@ int segc_get_x_sol(SegSolver *s, double *out) {
 
 int segc_get_obj(SegSolver *s, double *out) {                                 // get_final_obj SEGcpp:868-893
     if (!s->inited || !out) return lpbox_fail(LPBOX_E_STATE, "not initialised");
-    int rc = use_device(s);
+    int rc = use_device(s->device);
     if (rc) return rc;
     std::vector<double> xx;
     if ((rc = fetch_solution(s, xx))) return rc;
@@ -738,7 +673,7 @@ int segc_kernel_time(SegSolver *s, double *ms, long long *launches, int reset) {
 
 int segc_debug_vec(SegSolver *s, const char *name, double *out, int cap) {
     if (!s->inited) return lpbox_fail(LPBOX_E_STATE, "not initialised");
-    int rc = use_device(s);
+    int rc = use_device(s->device);
     if (rc) return rc;
     const double *src = nullptr;
     if (!strcmp(name, "x")) src = s->x.p; else if (!strcmp(name, "z1")) src = s->z1.p; else if (!strcmp(name, "z2")) src = s->z2.p;
@@ -756,7 +691,7 @@ int segc_debug_scalar(SegSolver *s, const char *name, double *out) {
         {"rho1", h.rho1}, {"gamma", h.gamma_val}, {"cur_obj", h.cur_obj}, {"std_obj", h.std_obj}, {"cvg1", h.cvg1}, {"cvg2", h.cvg2},
         {"obj_val", h.obj_val}, {"best_bin_obj", h.best_bin_obj}, {"c", s->c}, {"last_pcg", (double)h.last_pcg}, {"iter", (double)h.iter},
         {"matrix_as_diagonals", s->dia ? 1.0 : 0.0}, {"ell_width", (double)s->ell_w},
-        {"pcg_resumes", (double)s->pcg_resumes}, {"kmax", (double)s->kmax},
+        {"pcg_resumes", (double)s->chain.pcg_resumes}, {"kmax", (double)s->chain.kmax},
     };
     for (auto &e : tab) if (!strcmp(e.n, name)) { *out = e.v; return LPBOX_OK; }
     return lpbox_fail(LPBOX_E_BADARG, "unknown scalar '%s'", name);
@@ -783,9 +718,10 @@ struct lpbox_seg_batch {
     std::vector<SegSolver *> ss;
     std::vector<uint8_t> active;
     int B = 0, kmax = 10;
+    ChainRules rules = seg_rules();
     hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    Buf<SegDev> devs; Buf<SegBatchAux> aux; Buf<SegFixPar> par; Buf<SegState> dstates; Buf<int> counts; Buf<double> pack;
+    StreamTimer timer;
+    DevBuf<SegDev> devs; DevBuf<SegBatchAux> aux; DevBuf<SegFixPar> par; DevBuf<SegState> dstates; DevBuf<int> counts; DevBuf<double> pack;
     uint8_t *h_newfix = nullptr;                 // pinned staging of the host-vector form, problem i at nf_off[i]
     std::vector<size_t> nf_off;
     std::vector<SegDev> h_devs; std::vector<SegBatchAux> h_aux;   // host side of devs / aux (alive until the stream has taken them)
@@ -800,7 +736,7 @@ int segb_ensure(lpbox_seg_batch *b) {
     if (b->stream) return LPBOX_OK;
     const int B = b->B;
     HIPCHK(hipStreamCreate(&b->stream));
-    HIPCHK(hipEventCreate(&b->ev0)); HIPCHK(hipEventCreate(&b->ev1));
+    HIPCHK(b->timer.create());
     HIPCHK(b->devs.alloc(B)); HIPCHK(b->aux.alloc(B)); HIPCHK(b->par.alloc(B)); HIPCHK(b->dstates.alloc(B)); HIPCHK(b->counts.alloc(2 * (size_t)B));
     size_t tot = 0;
     b->nf_off.assign(B, 0);
@@ -861,7 +797,7 @@ int segb_window(lpbox_seg_batch *b, int iter_start, int iter_end, bool score_for
     }
     for (int k = 0; k < A; k++)
         if (!b->ss[act[k]]->inited) return lpbox_fail(LPBOX_E_STATE, "problem %d of the batch: solve_init has not been called", act[k]);
-    int rc = use_device(b->ss[0]);
+    int rc = use_device(b->ss[0]->device);
     if (rc) return rc;
     if (A == 0) return LPBOX_OK;
     if ((rc = segb_ensure(b))) return rc;
@@ -872,7 +808,7 @@ int segb_window(lpbox_seg_batch *b, int iter_start, int iter_end, bool score_for
         Gmax = std::max(Gmax, s->G);
         if (ws > 0 && (!s->xhist.p || s->ws_cap < ws)) {
             HIPCHK(hipStreamSynchronize(s->stream));
-            HIPCHK(s->xhist.alloc((size_t)SEG_XITERS_COLS * s->n)); s->ws_cap = SEG_XITERS_COLS; drop_graphs(s);
+            HIPCHK(s->xhist.alloc((size_t)SEG_XITERS_COLS * s->n)); s->ws_cap = SEG_XITERS_COLS; s->graphs.clear();
         }
         if (!s->dleft_valid) {                       // first early-fixing window after an init: the identity list
             if (!s->left_idx.empty()) HIPCHK(hipMemcpyAsync(s->d_left.p, s->left_idx.data(), sizeof(int) * s->left_idx.size(), hipMemcpyHostToDevice, st));
@@ -889,7 +825,7 @@ int segb_window(lpbox_seg_batch *b, int iter_start, int iter_end, bool score_for
     std::vector<int> row0(A, 0);
     if (score_form && scores) for (int k = 0; k < A; k++) row0[k] = b->row_off[act[k]];
     if ((rc = segb_describe(b, act, live, row0))) return rc;
-    HIPCHK(hipEventRecord(b->ev0, st));
+    HIPCHK(b->timer.start(st));
 
     std::vector<SegFixPar> hp(A);
     std::vector<int> applied(A, 0);
@@ -935,17 +871,15 @@ int segb_window(lpbox_seg_batch *b, int iter_start, int iter_end, bool score_for
     std::vector<SegState> hs(A);
     std::vector<long long> resumes(A, 0);
     int kmax = b->kmax;
-    if ((rc = batch_run_chain(b->devs.p, b->dstates.p, A, Gmax, iter_end, &parity, &kmax, b->ss[0]->adaptive, hs.data(), &launches, resumes.data(), st))) return rc;
+    if ((rc = batch_run_chain(b->rules, b->devs.p, b->dstates.p, A, Gmax, iter_end, &parity, &kmax, b->ss[0]->chain.adaptive, hs.data(), &launches, resumes.data(), st))) return rc;
     b->kmax = kmax;
-    HIPCHK(hipEventRecord(b->ev1, st));
-    HIPCHK(hipStreamSynchronize(st));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, b->ev0, b->ev1));
+    double ms = 0.0;
+    HIPCHK(b->timer.stop_sync(st, &ms));
     for (int k = 0; k < A; k++) {
         SegSolver *s = b->ss[act[k]];
         s->hst = hs[k]; s->parity = parity; s->rec_cols = 0;
         s->xi_rows = live[k] - applied[k]; s->last_ws = ws; s->xi_valid = true; s->win_serial++;
-        s->pcg_resumes += resumes[k];
+        s->chain.pcg_resumes += resumes[k];
         if (score_form && applied[k]) s->left_stale = true;          // fixed on the device: the host list follows on demand
         else if (applied[k]) s->left_idx.swap(kept[k]);
         s->xi_left_idx.clear();
@@ -970,7 +904,7 @@ lpbox_seg_batch *segbc_create(SegSolver **ss, int B) {
             if (ss[k] == ss[i]) return refuse(lpbox_fail(LPBOX_E_BADARG, "problem %d and problem %d of the batch are the same handle", k, i));
     }
     lpbox_seg_batch *b = new lpbox_seg_batch();
-    b->ss.assign(ss, ss + B); b->B = B; b->active.assign(B, 1); b->kmax = ss[0]->kmax;
+    b->ss.assign(ss, ss + B); b->B = B; b->active.assign(B, 1); b->kmax = ss[0]->chain.kmax;
     b->row_off.assign((size_t)B + 1, 0); b->pack_serial.assign(B, -1);
     return b;
 }
@@ -980,9 +914,8 @@ void segbc_destroy(lpbox_seg_batch *b) {
     if (b->stream) {
         (void)hipSetDevice(b->ss[0]->device);
         (void)hipStreamSynchronize(b->stream);
-        b->devs.release(); b->aux.release(); b->par.release(); b->dstates.release(); b->counts.release(); b->pack.release();
         if (b->h_newfix) (void)hipHostFree(b->h_newfix);
-        (void)hipEventDestroy(b->ev0); (void)hipEventDestroy(b->ev1);
+        b->timer.destroy();
         (void)hipStreamDestroy(b->stream);
     }
     delete b;
@@ -1034,7 +967,7 @@ int segbc_get_x_iters_device(lpbox_seg_batch *b, int ws, void **dev_ptr, long *r
     const int A = (int)act.size();
     for (int k = 0; k < A; k++)
         if (!b->ss[act[k]]->xi_valid) return lpbox_fail(LPBOX_E_STATE, "problem %d of the batch: solve_iter_l2f has not been called", act[k]);
-    int rc = use_device(b->ss[0]);
+    int rc = use_device(b->ss[0]->device);
     if (rc) return rc;
     if ((rc = segb_ensure(b))) return rc;
     std::vector<int> rows(A), row0(A);

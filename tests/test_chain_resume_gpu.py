@@ -1,6 +1,6 @@
-"""GPU tests of the PCG halt-and-resume path of the segmentation and generic-BQP launch chains (run_window / batch_run_chain in
-csrc/lpbox_seg_capi.hip, the loop of lpbox_bqp_solve in csrc/lpbox_gen_capi.hip): an outer iteration enqueues kmax (matvec, update)
-pairs; a PCG that needs more halts the chain from `post`, every launch behind the halt falls through, and the host enqueues
+"""GPU tests of the PCG halt-and-resume path of the segmentation and generic-BQP launch chains (chain_run in csrc/lpbox_host.h with the
+operations of csrc/lpbox_seg_capi.hip and csrc/lpbox_gen_capi.hip, batch_run_chain in csrc/lpbox_seg_capi.hip): an outer iteration
+enqueues kmax (matvec, update) pairs; a PCG that needs more halts the chain from `post`, every launch behind the halt falls through, and the host enqueues
 resume + 16 pairs + post.  The problems (tests/chain_cases.py, pinned on the CPU by tests/test_chain_resume_cases.py) need up to 44 and
 1000 PCG iterations, and LPBOX_SEG_KMAX / LPBOX_BQP_KMAX force the launch count down to 1.
 
@@ -9,8 +9,8 @@ energies); where the PCG counts of the restatement agree, also the numpy restate
 kmax = k the number of resumes is exact: sum of ceil((K_i - k) / 16) over the oracle's PCG counts K_i > k.
 
 Run as a script (`python test_chain_resume_gpu.py OUT.npy`) the file runs S1 at kmax = 2 and the batched legacy solve and writes
-every result to OUT: the statics test starts it in fresh child processes, because LPBOX_SEG_NOGRAPH and LPBOX_SEG_KMARGIN are read
-once per process."""
+every result to OUT: the statics test starts it in fresh child processes with LPBOX_SEG_NOGRAPH and LPBOX_SEG_KMARGIN set (they
+used to be read once per process; now every handle and every batch reads them when it is created)."""
 import ctypes
 import functools
 import os
@@ -452,7 +452,7 @@ def test_bqp_adaptive_chain_on_g4(monkeypatch):
     P, _ = bqp_case("G4")
     for v in bqp_names(P):
         assert bits_equal(h.vec(v), g.vec(v)), v
-    for s in BQP_SCALARS + ("iters", "stop", "total_pcg", "last_pcg", "outer_total", "pcg_resumes", "kmax"):
+    for s in BQP_SCALARS + ("iters", "stop", "total_pcg", "last_pcg", "outer_total", "pcg_resumes", "kmax", "launches"):
         assert h.scalar(s) == g.scalar(s), s
 
 

@@ -65,3 +65,18 @@ hipError_t gen_launch_pcg_upd(const GenDev &d, int *parity, hipStream_t s);
 hipError_t gen_launch_post(const GenDev &d, int *parity, hipStream_t s);
 hipError_t gen_launch_dual(const GenDev &d, int init_only, int *parity, hipStream_t s);
 hipError_t gen_launch_resume(const GenDev &d, int reset_pcg_max, int *parity, hipStream_t s);
+
+// ---- the reference's summation order (lpbox_bqp_set_order(LPBOX_ORDER_REFERENCE), lpbox_gen_ref_kernels.hip) ----
+#define GEN_REF_NSTAGE 7   // staging rows of n doubles, numbered as the slots of GenDev::part (post fills all seven)
+struct GenRef {
+    double *stage;         // row `slot`, column j: the term of element j of the sum that ends in GenDev::red[slot]
+};
+// nv sums from the rows slot0 .. slot0 + nv - 1 into red[].  sidx: the GenState index the producer wrote (-1: walk unconditionally);
+// the walk is skipped when that state is halted, or (pcg != 0) when its PCG is done -- the producer fell through and staged nothing.
+hipError_t genref_launch_walk(const GenDev &d, const GenRef &rf, int nv, int slot0, int sidx, int pcg, hipStream_t s);
+hipError_t genref_launch_init(const GenDev &d, const GenRef &rf, double c1, const double *x0, hipStream_t s);   // with its walk, as gen_launch_init with its fin
+hipError_t genref_launch_prep(const GenDev &d, const GenRef &rf, int do_prep, int *parity, hipStream_t s);
+hipError_t genref_launch_resid(const GenDev &d, const GenRef &rf, int *parity, hipStream_t s);
+hipError_t genref_launch_pcg_cols(const GenDev &d, const GenRef &rf, int *parity, hipStream_t s);
+hipError_t genref_launch_pcg_upd(const GenDev &d, const GenRef &rf, int *parity, hipStream_t s);
+hipError_t genref_launch_post(const GenDev &d, const GenRef &rf, int *parity, hipStream_t s);

@@ -1,6 +1,7 @@
 // lpbox_gen_capi.hip -- host side + C-ABI (lpbox_bqp_* in include/lpbox_hip.h) of the GENERIC constrained binary-QP path:
 // the reference's ADMM_bqp (SEGcpp:1384-1832) behind its four wrappers ADMM_bqp_unconstrained / _linear_eq / _linear_ineq /
-// _linear_eq_and_uneq (SEGcpp:1834-2109).  The kernels are in lpbox_gen_kernels.hip; the host loop of the launch chain is chain_run of
+// _linear_eq_and_uneq (SEGcpp:1834-2109).  The kernels are in lpbox_gen_kernels.hip (and, for the opt-in reference summation order of
+// lpbox_bqp_set_order, lpbox_gen_ref_kernels.hip); the host loop of the launch chain is chain_run of
 // lpbox_host.h with the rules of lpbox_chain.h (CHAIN_RULES_GEN), which also holds the graph cache, the device buffer and the macros.
 #include "lpbox_gen_host.h"
 #include "lpbox_host.h"
@@ -31,8 +32,11 @@ struct lpbox_bqp : GenHostProblem {
     int G = 0, Gm = 0, Gl = 0, EPT = 2, EPTm = 2, EPTl = 2, parity = 0;
     ChainController chain{CHAIN_RULES_GEN};      // kmax, and pcg_resumes of the last lpbox_bqp_solve
     double kernel_ms = 0.0; long long launches = 0, collectives = 0;   // (no collectives on this path)
-    GraphCache graphs;
+    GraphCache graphs;                           // of the order in use: lpbox_bqp_set_order clears it
     bool use_graph = true;
+    bool ref = false;                            // LPBOX_ORDER_REFERENCE: the staging producers and the walker, c1 through libm's pow
+    DevBuf<double> stage;                        // GEN_REF_NSTAGE rows of n, allocated by the first solve in that order
+    GenRef rf() const { return GenRef{stage.p}; }
     DevCsr dA, dCr, dCc, dEr, dEc;
     DevBuf<int> d_adiag;
     DevBuf<double> tmval, Cc_sv, Ec_sv, x, xt, y1, y2, z1, z2, db, rhs, r, z, tmp, p0, p1, gsrc, pdiag, dinv, Csq, Esq, best, dx0,
@@ -57,34 +61,39 @@ struct lpbox_bqp : GenHostProblem {
 };
 
 namespace {
-#define FIN(nv) do { HIPCHK(gen_launch_fin(d, nv, h->stream)); h->launches++; } while (0)
+// the six kernels that feed a reduction have reference-order counterparts (KL); the launch behind each of them is the reduction over
+// the workgroup partials or, in reference order, the walk over the staged terms of the state the producer has just written
+// (h->parity after its flip).  One launch either way: the `launches` of a solve do not depend on the order.
+#define KL(name, ...) (h->ref ? genref_launch_##name(d, h->rf(), ##__VA_ARGS__) : gen_launch_##name(d, ##__VA_ARGS__))
+#define FIN(nv, pcg) do { HIPCHK(h->ref ? genref_launch_walk(d, h->rf(), nv, 0, h->parity, pcg, h->stream) : gen_launch_fin(d, nv, h->stream)); \
+                          h->launches++; } while (0)
 #define ROWS(mode) do { HIPCHK(gen_launch_rows(d, mode, &h->parity, h->stream)); h->launches++; } while (0)
 
 int enqueue_pcg(lpbox_bqp *h, const GenDev &d, int pairs) {
     for (int k = 0; k < pairs; k++) {
         ROWS(1);
-        HIPCHK(gen_launch_pcg_cols(d, &h->parity, h->stream)); h->launches++;
-        FIN(1);
-        HIPCHK(gen_launch_pcg_upd(d, &h->parity, h->stream)); h->launches++;
-        FIN(2);
+        HIPCHK(KL(pcg_cols, &h->parity, h->stream)); h->launches++;
+        FIN(1, 1);
+        HIPCHK(KL(pcg_upd, &h->parity, h->stream)); h->launches++;
+        FIN(2, 1);
     }
     return LPBOX_OK;
 }
 int enqueue_tail(lpbox_bqp *h, const GenDev &d) {
-    HIPCHK(gen_launch_post(d, &h->parity, h->stream)); h->launches++;
-    FIN(7);
+    HIPCHK(KL(post, &h->parity, h->stream)); h->launches++;
+    FIN(7, 0);
     ROWS(0);
     HIPCHK(gen_launch_dual(d, 0, &h->parity, h->stream)); h->launches++;
     return LPBOX_OK;
 }
 int enqueue_iteration(lpbox_bqp *h, const GenDev &d) {
-    HIPCHK(gen_launch_prep(d, 1, &h->parity, h->stream)); h->launches++;
-    FIN(1);
+    HIPCHK(KL(prep, 1, &h->parity, h->stream)); h->launches++;
+    FIN(1, 0);
     HIPCHK(gen_launch_y(d, &h->parity, h->stream)); h->launches++;
     HIPCHK(gen_launch_rhs_cols(d, &h->parity, h->stream)); h->launches++;
     ROWS(0);
-    HIPCHK(gen_launch_resid(d, &h->parity, h->stream)); h->launches++;
-    FIN(3);
+    HIPCHK(KL(resid, &h->parity, h->stream)); h->launches++;
+    FIN(3, 0);
     CHK(enqueue_pcg(h, d, h->chain.kmax));
     return enqueue_tail(h, d);
 }
@@ -106,7 +115,7 @@ struct GenChainOps {
     }
     int batch_head() { HIPCHK(gen_launch_resume(d, 1, &h->parity, h->stream)); return LPBOX_OK; }
     int enqueue(int n) { for (int it = 0; it < n; it++) CHK(enqueue_iteration(h, d)); return LPBOX_OK; }
-    int finalize() { HIPCHK(gen_launch_prep(d, 0, &h->parity, h->stream)); h->launches++; return LPBOX_OK; }
+    int finalize() { HIPCHK(KL(prep, 0, &h->parity, h->stream)); h->launches++; return LPBOX_OK; }
 };
 }  // namespace
 
@@ -140,6 +149,22 @@ int lpbox_bqp_preset(lpbox_bqp_t *h, int type) {
 int lpbox_bqp_set_params(lpbox_bqp_t *h, const double *p11) {
     if (!h || !p11) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
     return gen_set_params(h->prm, p11);
+}
+
+int lpbox_bqp_set_order(lpbox_bqp_t *h, int mode) {
+    if (!h) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
+    if (mode != LPBOX_ORDER_DEFAULT && mode != LPBOX_ORDER_REFERENCE)
+        return lpbox_fail(LPBOX_E_BADARG, "summation order %d: LPBOX_ORDER_DEFAULT or LPBOX_ORDER_REFERENCE", mode);
+    const bool ref = mode == LPBOX_ORDER_REFERENCE;
+    if (ref == h->ref) return LPBOX_OK;
+    if (h->uploaded) {                           // the captured graphs hold the launches of the other order
+        CHK(use_device(h->device));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        h->graphs.clear();
+    }
+    h->ref = ref;
+    h->solved = false;                           // what the getters hold was computed in the other order
+    return LPBOX_OK;
 }
 
 int lpbox_bqp_set_problem(lpbox_bqp_t *h, int n, const int *Ap, const int *Ai, const double *Av, const double *b, const double *x0,
@@ -177,11 +202,13 @@ int lpbox_bqp_solve(lpbox_bqp_t *h, int *iterations) {                          
         HIPCHK(hipMemset(h->red.p, 0, sizeof(double) * GEN_NPART));
         h->uploaded = true;
     }
+    if (h->ref && !h->stage.p) HIPCHK(h->stage.alloc((size_t)GEN_REF_NSTAGE * n));
     const GenDev d = h->dev();
     h->parity = 0; h->kernel_ms = 0; h->launches = 0; h->chain.pcg_resumes = 0;
     h->chain.rules.pcg_cap = h->prm.pcg_maxiters;
     HIPCHK(h->timer.start(h->stream));
-    HIPCHK(gen_launch_init(d, std::pow((double)n, 1.0 / 2), h->dx0.p, h->stream));    // std::pow(n, 1.0 / p), p = 2 (SEGcpp:556)
+    // c1 = std::pow(n, 1.0 / p), p = 2 (SEGcpp:556); in the reference's order through libm's pow with an exponent no compiler folds
+    HIPCHK(KL(init, h->ref ? gen_ref_c1(n) : std::pow((double)n, 1.0 / 2), h->dx0.p, h->stream));
     HIPCHK(gen_launch_init2(d, h->stream));
     ROWS(0);                                                                        // E x0 for the first y3
     HIPCHK(gen_launch_dual(d, 1, &h->parity, h->stream));
@@ -211,6 +238,8 @@ int lpbox_bqp_get_vec(lpbox_bqp_t *h, const char *name, double *out, long cap) {
 }
 
 int lpbox_bqp_get_scalar(lpbox_bqp_t *h, const char *name, double *out) {
+    // the order is a setting, not a result: readable at any time, before the first solve and straight after lpbox_bqp_set_order too
+    if (h && out && name && !strcmp(name, "order")) { *out = h->ref ? (double)LPBOX_ORDER_REFERENCE : (double)LPBOX_ORDER_DEFAULT; return LPBOX_OK; }
     if (!h || !h->solved || !out || !name) return lpbox_fail(LPBOX_E_STATE, "not solved");
     const GenState &s = h->hst;
     struct { const char *n; double v; } tab[] = {
@@ -219,7 +248,7 @@ int lpbox_bqp_get_scalar(lpbox_bqp_t *h, const char *name, double *out) {
         {"total_pcg", (double)s.pcg_total}, {"outer_total", (double)s.outer_total}, {"last_pcg", (double)s.last_pcg},
         {"kernel_ms", h->kernel_ms}, {"launches", (double)h->launches}, {"threads", (double)GEN_T}, {"chunk", (double)(GEN_T * h->EPT)},
         {"pcg_resumes", (double)h->chain.pcg_resumes}, {"kmax", (double)h->chain.kmax}, {"kmax_kept", (double)h->chain.kept},
-        {"graph_revisits", (double)h->graphs.revisits},
+        {"graph_revisits", (double)h->graphs.revisits}, {"order", h->ref ? (double)LPBOX_ORDER_REFERENCE : (double)LPBOX_ORDER_DEFAULT},
     };
     for (auto &e : tab) if (!strcmp(e.n, name)) { *out = e.v; return LPBOX_OK; }
     return lpbox_fail(LPBOX_E_BADARG, "unknown scalar '%s'", name);

@@ -6,7 +6,16 @@
 #include "lpbox_gen.h"
 #include "lpbox_capi_internal.h"
 
+#include <cmath>
 #include <vector>
+
+// c1 = pow(n, 1/p), p = 2 (SEGcpp:556) through libm's pow, as the reference and the oracle call it: with the literal exponent the compiler
+// may turn the call into sqrt, and glibc's pow is not correctly rounded (n = 2921, 3541: one ulp apart; as ref_c1 of lpbox_big_capi.hip).
+// Reference order only, for both front ends; the default order keeps the expression it has always had.
+inline double gen_ref_c1(int n) {
+    volatile double e = 1.0 / 2;
+    return std::pow((double)n, e);
+}
 
 struct GenHostCsr { int rows = 0, cols = 0; std::vector<int> ptr, idx; std::vector<double> val; };
 

@@ -32,13 +32,6 @@ struct lpbox_bqp_batch {
 };
 
 namespace {
-// c1 = pow(n, 1/p), p = 2 (SEGcpp:556) through libm's pow, as the reference and the oracle call it: with the literal exponent the compiler
-// may turn the call into sqrt, and glibc's pow is not correctly rounded.  Reference order only (as ref_c1 of lpbox_big_capi.hip); no
-// n <= GENB_MAXDIM tells the two apart, the default order keeps the expression it has always had.
-double ref_c1(int n) {
-    volatile double e = 1.0 / 2;
-    return std::pow((double)n, e);
-}
 int check_index(lpbox_bqp_batch *h, int idx, bool all_ok) {
     if (!h) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
     if ((idx == -1 && all_ok) || (idx >= 0 && idx < h->count)) return LPBOX_OK;
@@ -79,7 +72,7 @@ int upload(lpbox_bqp_batch *h) {
         GenbProb &g = h->hprob[i];
         const int *I = h->ipool.p; double *D = h->dpool.p;
         g.n = p.n; g.m = p.m; g.l = p.l; g.eq = p.m > 0; g.ineq = p.l > 0; g.prm = p.prm;
-        g.c1 = h->ref ? ref_c1(p.n) : std::pow((double)p.n, 1.0 / 2);                 // std::pow(n, 1.0 / p), p = 2 (SEGcpp:556)
+        g.c1 = h->ref ? gen_ref_c1(p.n) : std::pow((double)p.n, 1.0 / 2);                 // std::pow(n, 1.0 / p), p = 2 (SEGcpp:556)
         g.aptr = I + o.aptr; g.aidx = I + o.aidx; g.adiag = I + o.adiag; g.aval = D + o.aval; g.tmval = D + o.tmval;
         g.Cr = GenCsr{I + o.crp, I + o.cri, D + o.crv}; g.Cc = GenCsr{I + o.ccp, I + o.cci, D + o.ccv}; g.Cc_sv = D + o.ccsv;
         g.Er = GenCsr{I + o.erp, I + o.eri, D + o.erv}; g.Ec = GenCsr{I + o.ecp, I + o.eci, D + o.ecv}; g.Ec_sv = D + o.ecsv;

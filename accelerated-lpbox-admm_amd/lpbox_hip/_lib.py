@@ -128,6 +128,7 @@ SYMBOLS = {
     "lpbox_bqp_solve": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "lpbox_bqp_get_vec": (C.c_int, [C.c_void_p, C.c_char_p, _dp, C.c_long]),
     "lpbox_bqp_get_scalar": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_double)]),
+    "lpbox_bqp_set_order": (C.c_int, [C.c_void_p, C.c_int]),
     "lpbox_bqp_batch_create": (C.c_void_p, [C.c_int, C.c_int]),
     "lpbox_bqp_batch_destroy": (None, [C.c_void_p]),
     "lpbox_bqp_batch_preset": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),

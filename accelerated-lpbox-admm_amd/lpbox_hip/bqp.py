@@ -44,7 +44,10 @@ def with_diagonal(rowptr, colidx, vals, n):
 
 
 class BqpSolver:
-    def __init__(self, n, A, b, x0, C_=None, d=None, E=None, f=None, preset=None, params=None, device=0):
+    """One problem per handle, any size.  order: "default", or "reference" (see `set_order`)."""
+
+    def __init__(self, n, A, b, x0, C_=None, d=None, E=None, f=None, preset=None, params=None, device=0, order="default"):
+        mode = _order_mode(order)
         self._L = _lib.load()
         self.n = int(n)
         self.m = 0 if C_ is None else len(d)
@@ -79,6 +82,19 @@ class BqpSolver:
             if isinstance(params, dict):
                 raise TypeError("params: the 11 values in the order of bqp.PARAM_NAMES")
             check(self._L.lpbox_bqp_set_params(self._h, np.ascontiguousarray(params, np.float64)), "lpbox_bqp_set_params")
+        self.order = "default"
+        if mode:
+            self.set_order(order)
+
+    def set_order(self, name="default"):
+        """Summation order of the kernel chain, chosen at any time, also between two solves.  "default": the kernels' own reduction
+        tree.  "reference": an opt-in that associates every sum over the n elements as the reference's Eigen path does (DESIGN.md
+        section 14.3) -- the reference's iterates, iteration counts and binary answers, except that the std stop test takes sqrt where
+        the reference calls pow(v, 1/2); each reduction becomes a sequential walk by one workgroup, so an iteration costs more.  A
+        call that changes the order discards the results of the previous solve."""
+        mode = _order_mode(name)
+        check(self._L.lpbox_bqp_set_order(self._h, mode), "lpbox_bqp_set_order")
+        self.order = name
 
     def close(self):
         if getattr(self, "_h", None):
@@ -112,8 +128,8 @@ class BqpSolver:
 
 
 # ---- the reference's four entry points by name (SEGcpp:1834-2109); each returns the Solution dict -------------------------------
-def _run(n, A, b, x0, C_=None, d=None, E=None, f=None, preset=0, params=None, device=0):
-    s = BqpSolver(n, A, b, x0, C_, d, E, f, preset=preset, params=params, device=device)
+def _run(n, A, b, x0, C_=None, d=None, E=None, f=None, preset=0, params=None, device=0, order="default"):
+    s = BqpSolver(n, A, b, x0, C_, d, E, f, preset=preset, params=params, device=device, order=order)
     it = s.solve()
     sol = s.solution()
     sol.update(iterations=it, stop=int(s.scalar("stop")), best_bin_obj=s.scalar("best_bin_obj"), time_elapsed_ms=s.scalar("kernel_ms"))

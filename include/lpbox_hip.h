@@ -396,7 +396,19 @@ int lpbox_bqp_set_problem(lpbox_bqp_t *h, int n, const int *Ap, const int *Ai, c
                           int l, const int *Ep, const int *Ei, const double *Ev, const double *f);
 int lpbox_bqp_solve(lpbox_bqp_t *h, int *iterations);          /* the whole ADMM_bqp loop; *iterations = the `iter` it ended on */
 int lpbox_bqp_get_vec(lpbox_bqp_t *h, const char *name, double *out, long cap);   /* Solution (LPh): "x" (x_sol), "y1", "y2", "best_sol"; also "z1","z2","z3","z4","y3" */
-int lpbox_bqp_get_scalar(lpbox_bqp_t *h, const char *name, double *out);          /* "iters","stop" (1 xyy, 2 obj_std, 0 max_iters),"cur_obj","best_bin_obj","total_pcg",... */
+int lpbox_bqp_get_scalar(lpbox_bqp_t *h, const char *name, double *out);          /* "iters","stop" (1 xyy, 2 obj_std, 0 max_iters),"cur_obj","best_bin_obj","total_pcg",...,"order" */
+/* OPT-IN: the summation order of the one-problem chain, LPBOX_ORDER_DEFAULT / LPBOX_ORDER_REFERENCE as for lpbox_bqp_batch_set_order
+ * below -- the only route to the reference's order for a problem with a dimension above 2048.  REFERENCE = every sum over the n
+ * elements (the dot products and squared norms of the PCG, of the y2 projection, of the stop tests and of compute_cost) associated as
+ * the reference's Eigen 3.3.8 SSE2 redux associates it, and c1 through libm's pow: bit for bit oracle/bqp_oracle.c in its Eigen order on
+ * every vector and scalar, except that the std stop test takes sqrt where the reference calls pow(v, 1/2) ("std_obj" within 2 ulps).
+ * What it costs: the kernels that fed a reduction write one term per element to seven staging rows of n doubles (allocated by the
+ * first solve in this order) and one workgroup walks them, n / 4 dependent additions per reduction; DESIGN.md section 14.3 holds the
+ * measurements.  Allowed at any time, also between two lpbox_bqp_solve calls on one handle (a solve re-initialises); a call that
+ * changes the order marks the handle as not solved: the results of the other order are refused until the next solve, while
+ * lpbox_bqp_get_scalar(h, "order") answers at any time, before the first solve too.  "threads", "chunk" and "launches" keep their values.  Bad handle ->
+ * LPBOX_E_BADHANDLE; unknown mode -> LPBOX_E_BADARG, and the handle stays as it was. */
+int lpbox_bqp_set_order(lpbox_bqp_t *h, int mode);
 
 /* ---- a batch of SMALL generic constrained binary QPs (max(n, m, l) <= 2048 each), one persistent workgroup per problem -------------
  * The same ADMM_bqp loop (SEGcpp:1384-1832: the y updates :1598-1613, the rho refresh :1619-1650, the PCG on the matrix expression
@@ -426,7 +438,7 @@ int lpbox_bqp_batch_get_scalar(lpbox_bqp_batch_t *h, int idx, const char *name, 
  * by four lanes (two walks per PCG step) instead of a tree, and four staging rows of LDS per workgroup (about 32 n bytes for the batch's
  * largest n; DESIGN.md section 14.2 holds the plan and the measurements: 1.4 to 1.5 times the default order's kernel time); a batch whose LDS need exceeds one workgroup's 160 KB -> LPBOX_E_UNSUPPORTED
  * from lpbox_bqp_batch_solve.  Allowed at any time before a solve; marks the batch as not solved.  "threads" and "chunk" keep their values
- * (they describe the default order).  Unknown mode -> LPBOX_E_BADARG.  lpbox_bqp_* (one problem per handle) has no such mode. */
+ * (they describe the default order).  Unknown mode -> LPBOX_E_BADARG.  lpbox_bqp_* (one problem per handle): lpbox_bqp_set_order above. */
 int lpbox_bqp_batch_set_order(lpbox_bqp_batch_t *h, int mode);
 
 #ifdef __cplusplus

@@ -62,6 +62,14 @@ namespace {
 #else
 #define LPBOX_PCG_SPEC 0
 #endif
+// The fused outer iteration of the 512 x 1 kernel (see lp_outer_fused) goes with the specialised loops: the diagnostic builds keep the
+// text their stamps and knock-outs were placed in, and -DLPBOX_LP_OUTER_LEGACY restores it for an A/B of the shipped kernel
+// (make variant NAME=legacy EXTRA=-DLPBOX_LP_OUTER_LEGACY).
+#if LPBOX_PCG_SPEC && !defined(LPBOX_LP_OUTER_LEGACY)
+#define LPBOX_OUTER_FUSED 1
+#else
+#define LPBOX_OUTER_FUSED 0
+#endif
 
 // ------------------------------------------------------------------------------------------------
 // LDS carve-up shared by the launcher (size) and the kernel (pointers)
@@ -114,6 +122,10 @@ __host__ __device__ constexpr bool lp_pcg_spec_geometry(int T, int EPT, bool dir
 __host__ __device__ constexpr bool lp_pcg_spec_built(int rn, int cn, int hn) {
     return rn >= 0 && rn <= LP_PCG_RCAP / 2 && cn >= 0 && cn <= LP_PCG_CCAP / 2 && hn >= 0 && hn <= LP_PCG_HCAP / 2;
 }
+// Outer iteration of lp_window_kernel per geometry.  512 x 1 (not DIRECT, not LOG): E x and E y1 of the next iteration come out of ONE
+// row pass, the three column products in front of the PCG out of ONE column pass (two gather passes and one barrier fewer per
+// iteration; same expressions on the same operands).  Every other kernel keeps the passes where they were.
+__host__ __device__ constexpr bool lp_outer_fused(int T, int EPT, bool direct, bool log) { return LPBOX_OUTER_FUSED != 0 && T == 512 && EPT == 1 && !direct && !log; }
 
 typedef __attribute__((address_space(3))) double lds_double;
 
@@ -342,6 +354,56 @@ __device__ __forceinline__ void gather_all2(const Lists<C> &g, const uint16_t *i
     });
 }
 
+// One-slot lists, one sum per component COMP... of the gathered elements through its own OP, each component added in ascending list
+// order from +0.0 like a gather_all of its own.  DISPATCH: gather_all's straight-line path per wave-uniform list length (every read is
+// issued before the first addition: one LDS latency for all components; the row pass).  Otherwise gather_all2's rounds of GCH entries
+// (the column pass of three components: with up to 36 reads in flight the dispatched form measured slower).
+template <bool DISPATCH, typename C, int STRIDE, int... COMP, typename... OP>
+__device__ __forceinline__ void gather_comps(const Lists<C> &g, const uint16_t *idx, double (&out)[sizeof...(COMP)], OP... op) {
+    static_assert(C::N == 1 && Lists<C>::TAILREG && sizeof...(COMP) == sizeof...(OP), "one slot, one operation per component");
+    constexpr int NC = sizeof...(COMP), G1 = LPBOX_LP_G1, MAXCAP = caps_max<C>();
+    double acc[NC];
+#pragma unroll
+    for (int c = 0; c < NC; c++) acc[c] = 0.0;
+    if constexpr (DISPATCH) {
+    dispatch_chunks<MAXCAP / G1>((g.wlen[0] + G1 - 1) / G1, [&](auto K) {
+        constexpr int n = decltype(K)::value * G1;
+        double v[n > 0 ? n : 1][NC];
+#pragma unroll
+        for (int q = 0; q < n; q++) { int c = 0; ((v[q][c++] = lds_ld<COMP>(g.addr[q])), ...); }
+#pragma unroll
+        for (int q = 0; q < n; q++) { int c = 0; ((acc[c] = op(acc[c], v[q][c]), c++), ...); }
+    });
+    } else {
+    static_for<MAXCAP / GCH>([&](auto CI) {
+        constexpr int c0 = decltype(CI)::value * GCH;
+        if (c0 < g.wlen[0]) {                                           // wave-uniform
+            double v[GCH][NC];
+#pragma unroll
+            for (int q = 0; q < GCH; q++) { int c = 0; ((v[q][c++] = lds_ld<COMP>(g.addr[c0 + q])), ...); }
+#pragma unroll
+            for (int q = 0; q < GCH; q++) { int c = 0; ((acc[c] = op(acc[c], v[q][c]), c++), ...); }
+        }
+    });
+    }
+    for (int k = g.tail_begin[0]; k < g.tail_end[0]; k += GCH) {           // long lists: indices from LDS
+        unsigned o[GCH];
+#pragma unroll
+        for (int q = 0; q < GCH; q++) o[q] = (k + q < g.tail_end[0]) ? g.base + STRIDE * (unsigned)idx[k + q] : g.zero;
+        double v[GCH][NC];
+#pragma unroll
+        for (int q = 0; q < GCH; q++) { int c = 0; ((v[q][c++] = lds_ld<COMP>(o[q])), ...); }
+#pragma unroll
+        for (int q = 0; q < GCH; q++) { int c = 0; ((acc[c] = op(acc[c], v[q][c]), c++), ...); }
+    }
+#pragma unroll
+    for (int c = 0; c < NC; c++) out[c] = acc[c];
+}
+template <typename C, typename OPA, typename OPB, typename OPC>
+__device__ __forceinline__ void gather_all3(const Lists<C> &g, const uint16_t *idx, OPA opa, OPB opb, OPC opc, double (&out)[3]) {
+    gather_comps<false, C, 24, 0, 1, 2>(g, idx, out, opa, opb, opc);           // components 0, 1, 2 of the interleaved l-vectors
+}
+
 // ------------------------------------------------------------------------------------------------
 // ADMM_lp_iters_init (LPcpp:489-763) for every instance: x=1, z=0, rho=25, ...
 // ------------------------------------------------------------------------------------------------
@@ -483,6 +545,7 @@ __global__ void __launch_bounds__(T) lp_window_kernel(LpBatchDev bd, int iter_st
     const int l2f = mode & 1, rec = mode & 2;     // rec: keep x after every iteration in xhist (x_iters of the l2f loop; print_fix_info 2/3 of the plain loop)
     constexpr int RS = (DIRECT || LOG) ? RED_STAGE_BCAST : lp_red_stage(T, EPT);    // second stage of every block_sum of this kernel
     constexpr bool SCALAR_LOOP = lp_pcg_scalar_loop(T, EPT, DIRECT, LOG), SPEC = lp_pcg_spec_geometry(T, EPT, DIRECT, LOG);
+    constexpr bool FUSED = lp_outer_fused(T, EPT, DIRECT, LOG);
     // A test on a value that came out of block_sum is the same in every lane, which the compiler cannot see: it builds the PCG loop as a
     // divergent one (iteration counter in a vector register, exec-mask save / restore behind both reductions).  Going through the lane
     // mask (v_cmp into a scalar pair, s_cmp_lg_u64) states the uniformity.  All lanes of a wave are active wherever this is used.
@@ -705,6 +768,30 @@ __global__ void __launch_bounds__(T) lp_window_kernel(LpBatchDev bd, int iter_st
             for (int s = 0; s < EPT; s++) { outA[s] = ownA[s]; outB[s] = ownB[s]; }
         }
     };
+    // fused outer iteration (one slot): E x and E y1 -- both n-vectors of gx through the same list addresses -- in one row pass,
+    // and components 0, 1, 2 of the l-vectors in one column pass; splits and combines per component as in rows_gather / cols_gather
+    auto rows_gather_x_y1 = [&](double (&ex)[EPT], double (&q)[EPT]) {
+        if constexpr (FUSED) {
+            double part[2];
+            gather_comps<true, RCAPS, 8, 0, GX2>(rl, s_rs_col, part, op_add, op_add);
+            const double pa[EPT] = {part[0]}, pb[EPT] = {part[1]};
+            rows_combine(pa, ex);
+            rows_combine(pb, q);
+        }
+    };
+    auto cols_gather3 = [&](auto opa, double (&outA)[EPT], double (&outB)[EPT], double (&outC)[EPT]) {
+        if constexpr (FUSED) {
+            double own[3], hp[3];
+            gather_all3(cl, s_cs_row, opa, op_add, op_add, own);
+            gather_all3(hl, s_cs_row, opa, op_add, op_add, hp);
+            if (anyhelp[0]) {
+                const double ta = quad_sum(hp[0]), tb = quad_sum(hp[1]), tc = quad_sum(hp[2]);
+                outA[0] = clong[0] ? own[0] + ta : own[0];
+                outB[0] = clong[0] ? own[1] + tb : own[1];
+                outC[0] = clong[0] ? own[2] + tc : own[2];
+            } else { outA[0] = own[0]; outB[0] = own[1]; outC[0] = own[2]; }
+        }
+    };
 
     // ---- early fixing: apply this call's fix vector (LPcpp:1124-1335) as a mask ----
     bool finished = false;
@@ -758,26 +845,46 @@ __global__ void __launch_bounds__(T) lp_window_kernel(LpBatchDev bd, int iter_st
         // applied while no rho update is pending (stale preconditioner = UB in the reference) is well defined.
 #pragma unroll
         for (int s = 0; s < EPT; s++) { const double v = pd.get(s); dinv[s] = (v != 0.0) ? 1.0 / v : 1.0; }
+        // (one-/two-slot variants carry y1 and the unscaled y2 into the next iteration in registers; the register-lean ones recompute them)
+        double y1c[LEAN ? 1 : EPT], uc[LEAN ? 1 : EPT];
+        // Fused outer iteration: the PCG start vector y1 = clamp(x + z1 / rho1) of the NEXT iteration needs only x, the updated z1 and the
+        // rho1 that iteration will see, so it is published next to x, E y1 comes out of the row pass that gathers E x, and prepare()
+        // publishes r4 * (E y1) with the other l-vectors -- r4 being the rho4_E_transpose the next refresh will produce (r4n).
+        double qn[FUSED ? EPT : 1], r4n = 0.0;
+        auto start_vec = [&](double r1) {
+            if constexpr (FUSED) {
+                const double t = x[0] + z1.get(0) / r1;
+                const double y1n = t > 1 ? 1 : (t < 0 ? 0 : t);       // project_box :409-421
+                gx[GX2 + tid] = live[0] ? y1n : 0.0;                  // PCG start x0 = y1 (:892)
+                y1c[0] = y1n;
+            }
+        };
         // E*x for the first iteration's y3
         __syncthreads();
 #pragma unroll
         for (int s = 0; s < EPT; s++) gx[s * T + tid] = live[s] ? x[s] : 0.0;
+        if constexpr (FUSED) {
+            start_vec(rho1);
+            // what the first refresh of this launch makes of rho4_E_transpose: update_expression(0), a pending rho update (after a fix
+            // in this launch that is the double count of SURVEY Q1: the fix has just reset r4Et to rho4), or nothing
+            r4n = it == 0 ? rho4 : (rhoUpdated ? learning_fact * r4Et : r4Et);
+        }
         __syncthreads();
-        rows_gather(Ex);
+        if constexpr (FUSED) rows_gather_x_y1(Ex, qn);
+        else rows_gather(Ex);
 
         // The first half of an iteration (LPcpp:806-828) needs only what the END of the previous one holds -- x, z1, z2, z4, E x and the
         // rho of the next iteration: y3 with the published l-vectors, the PCG start vector y1 and this thread's share of the sphere
         // norm are prepared there, so that the norm rides in the residual reduction and the l-vectors are published by its barrier
         // (two barriers fewer per iteration than computing them where the reference does; same expressions, same bits).
-        // (one-/two-slot variants carry y1 and the unscaled y2 into the next iteration in registers; the register-lean ones recompute them)
-        double y1c[LEAN ? 1 : EPT], uc[LEAN ? 1 : EPT];
         auto prepare = [&](double r1, double r2, double r4) {
             double part = 0.0;
 #pragma unroll
             for (int s = 0; s < EPT; s++) {
                 const double u = (x[s] + z2.get(s) / r2) - 0.5;       // project_shifted_Lp_ball :423-428
                 part = part + (live[s] ? u * u : 0.0);
-                if constexpr (!DIRECT || !LEAN) {
+                if constexpr (FUSED) uc[s] = u;                       // (y1 went out with x, see start_vec)
+                else if constexpr (!DIRECT || !LEAN) {
                     const double t = x[s] + z1.get(s) / r1;
                     const double y1n = t > 1 ? 1 : (t < 0 ? 0 : t);   // project_box :409-421
                     if constexpr (!DIRECT) gx[GX2 + s * T + tid] = live[s] ? y1n : 0.0;      // PCG start x0 = y1 (:892)
@@ -800,7 +907,10 @@ __global__ void __launch_bounds__(T) lp_window_kernel(LpBatchDev bd, int iter_st
                 const double v = fs - Ex[s] - z4s / r4;
                 const double y3s = v < 0 ? 0 : v;
                 y3.set(s, rgl(s), rvalid(s), y3s);
-                if (rvalid(s)) { gl[3 * rgl(s)] = fs - y3s; gl[3 * rgl(s) + 1] = z4s; }
+                if (rvalid(s)) {
+                    gl[3 * rgl(s)] = fs - y3s; gl[3 * rgl(s) + 1] = z4s;
+                    if constexpr (FUSED) gl[3 * rgl(s) + 2] = r4n * qn[s];      // the factor of the column product, once per row (see the PCG loop)
+                }
                 }
             }
             return part;
@@ -870,6 +980,9 @@ __global__ void __launch_bounds__(T) lp_window_kernel(LpBatchDev bd, int iter_st
 #endif
             // ---------------- rhs (:872-878) and q = E*y1 ----------------
             double rhs[EPT], tAs[EPT], tBs[EPT];
+            double tcf[FUSED ? EPT : 1];
+            if constexpr (FUSED) cols_gather3(op_scaled, tAs, tBs, tcf);                // ... and E^T (r4 E y1), published by prepare(), with them
+            else
             cols_gather2(op_scaled, op_add, tAs, tBs);                                  // (rho4 E^T)(f - y3) and E^T z4 in one pass
 #pragma unroll
             for (int s = 0; s < EPT; s++) {
@@ -879,7 +992,7 @@ __global__ void __launch_bounds__(T) lp_window_kernel(LpBatchDev bd, int iter_st
                 r_ -= tB;
                 rhs[s] = r_;
             }
-            if constexpr (!DIRECT) {
+            if constexpr (!DIRECT && !FUSED) {
                 double q[EPT];
                 rows_gather_at(std::integral_constant<int, GX2>{}, q);    // q = E y1 (the start vector sits in the second n-vector)
 #pragma unroll
@@ -993,6 +1106,8 @@ __global__ void __launch_bounds__(T) lp_window_kernel(LpBatchDev bd, int iter_st
             double r[EPT], p[EPT];
             double p3[3] = {0.0, 0.0, 0.0};
             double tcol[EPT];
+            if constexpr (FUSED) tcol[0] = tcf[0];
+            else
             cols_gather(std::integral_constant<int, 2>{}, op_add, tcol);
 #pragma unroll
             for (int s = 0; s < EPT; s++) {
@@ -1238,7 +1353,14 @@ __global__ void __launch_bounds__(T) lp_window_kernel(LpBatchDev bd, int iter_st
                 z2.set(s, z2.get(s) + g2 * (x[s] - y2[s]));
                 gx[s * T + tid] = live[s] ? x[s] : 0.0;
             }
+            if constexpr (FUSED) {
+                const bool step = (it + 1) % LP_RHO_STEP == 0;        // (rho_step below)
+                start_vec(step ? learning_fact * rho1 : rho1);
+                r4n = step ? learning_fact * r4Et : r4Et;             // the next refresh: rho4_E_transpose *= learning_fact (:864) at a rho step
+            }
             __syncthreads();
+            if constexpr (FUSED) rows_gather_x_y1(Ex, qn);            // ... and E*y1 of the next iteration's PCG start
+            else
             rows_gather(Ex);                                          // E*x: feeds z4 now and y3 of the next iteration
 #pragma unroll
             for (int s = 0; s < EPT; s++) {

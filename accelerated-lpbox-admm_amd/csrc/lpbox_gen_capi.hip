@@ -148,7 +148,10 @@ int lpbox_bqp_preset(lpbox_bqp_t *h, int type) {
 
 int lpbox_bqp_set_params(lpbox_bqp_t *h, const double *p11) {
     if (!h || !p11) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
-    return gen_set_params(h->prm, p11);
+    GenParams tmp;                            // a rejected call leaves the parameters as they were
+    CHK(gen_set_params(tmp, p11));
+    h->prm = tmp;
+    return LPBOX_OK;
 }
 
 int lpbox_bqp_set_order(lpbox_bqp_t *h, int mode) {
@@ -172,7 +175,9 @@ int lpbox_bqp_set_problem(lpbox_bqp_t *h, int n, const int *Ap, const int *Ai, c
                           int l, const int *Ep, const int *Ei, const double *Ev, const double *f) {
     if (!h) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
     if (h->uploaded) return lpbox_fail(LPBOX_E_STATE, "problem already uploaded; create a new handle");
-    CHK(gen_load_problem(*h, n, Ap, Ai, Av, b, x0, m, Cp, Ci, Cv, d, l, Ep, Ei, Ev, f));
+    GenHostProblem tmp;                       // a rejected call leaves the problem that was set before untouched
+    CHK(gen_load_problem(tmp, n, Ap, Ai, Av, b, x0, m, Cp, Ci, Cv, d, l, Ep, Ei, Ev, f));
+    static_cast<GenHostProblem &>(*h) = std::move(tmp);
     h->has_problem = true;
     return LPBOX_OK;
 }

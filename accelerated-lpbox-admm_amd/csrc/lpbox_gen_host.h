@@ -30,9 +30,11 @@ inline int gen_load_csr(GenHostCsr &M, int rows, int cols, const int *ptr, const
     if (!ptr || ptr[0] != 0) return lpbox_fail(LPBOX_E_BADARG, "%s: bad row pointer", what);
     for (int i = 0; i < rows; i++) {
         if (ptr[i + 1] < ptr[i]) return lpbox_fail(LPBOX_E_BADARG, "%s: row pointer not monotone", what);
+        if (ptr[i + 1] > ptr[i] && (!idx || !val)) return lpbox_fail(LPBOX_E_BADARG, "%s: index or value array missing", what);
         for (int k = ptr[i]; k < ptr[i + 1]; k++) {
             if (idx[k] < 0 || idx[k] >= cols) return lpbox_fail(LPBOX_E_BADARG, "%s: column index out of range", what);
             if (k > ptr[i] && idx[k] <= idx[k - 1]) return lpbox_fail(LPBOX_E_BADARG, "%s: columns must ascend inside a row", what);
+            if (!std::isfinite(val[k])) return lpbox_fail(LPBOX_E_BADARG, "%s has a non-finite stored value (row %d, column %d)", what, i, idx[k]);
         }
     }
     M.rows = rows; M.cols = cols;
@@ -67,7 +69,19 @@ inline int gen_preset(GenParams &p, int type) {
     return lpbox_fail(LPBOX_E_BADARG, "preset %d: 0 unconstrained, 1 equality, 2 inequality, 3 both", type);
 }
 
+// A NaN in any vector makes every PCG exit test false: max_iters x pcg_maxiters PCG iterations of halt-and-resume chains before the call
+// returns (the reference accepts it and computes garbage; the same deliberate deviation as the LP path's, DESIGN.md sections 24 and 26).
+inline int gen_check_finite(const double *v, int len, const char *what) {
+    for (int i = 0; i < len; i++)
+        if (!std::isfinite(v[i])) return lpbox_fail(LPBOX_E_BADARG, "%s has a non-finite entry (index %d)", what, i);
+    return LPBOX_OK;
+}
+
 inline int gen_set_params(GenParams &p, const double *p11) {
+    static const char *const names[11] = {"stop_threshold", "std_threshold", "gamma_val", "gamma_factor", "rho_change_step", "max_iters",
+                                          "initial_rho", "history_size", "learning_fact", "pcg_tol", "pcg_maxiters"};
+    for (int i = 0; i < 11; i++)      // before anything is written (and before a NaN reaches an int cast): a rejected call changes nothing
+        if (!std::isfinite(p11[i])) return lpbox_fail(LPBOX_E_BADARG, "params has a non-finite entry (index %d, %s)", i, names[i]);
     p.stop_threshold = p11[0]; p.std_threshold = p11[1]; p.gamma_val = p11[2]; p.gamma_factor = p11[3]; p.rho_change_step = (int)p11[4];
     p.max_iters = (int)p11[5]; p.initial_rho = p11[6]; p.history_size = (int)p11[7]; p.learning_fact = p11[8]; p.pcg_tol = p11[9];
     p.pcg_maxiters = (int)p11[10];
@@ -83,6 +97,7 @@ inline int gen_load_problem(GenHostProblem &h, int n, const int *Ap, const int *
     if (n <= 0 || !b || !x0 || m < 0 || l < 0) return lpbox_fail(LPBOX_E_BADARG, "bad problem arguments");
     int rc = gen_load_csr(h.A, n, n, Ap, Ai, Av, "A");
     if (rc < 0) return rc;
+    if ((rc = gen_check_finite(b, n, "b")) < 0 || (rc = gen_check_finite(x0, n, "x0")) < 0) return rc;
     h.adiag.assign(n, -1);
     for (int i = 0; i < n; i++) {
         for (int k = Ap[i]; k < Ap[i + 1]; k++) if (Ai[k] == i) h.adiag[i] = k;
@@ -91,12 +106,12 @@ inline int gen_load_problem(GenHostProblem &h, int n, const int *Ap, const int *
     }
     if (m > 0) {
         if (!d) return lpbox_fail(LPBOX_E_BADARG, "d missing");
-        if ((rc = gen_load_csr(h.C, m, n, Cp, Ci, Cv, "C")) < 0) return rc;
+        if ((rc = gen_load_csr(h.C, m, n, Cp, Ci, Cv, "C")) < 0 || (rc = gen_check_finite(d, m, "d")) < 0) return rc;
         gen_transpose(h.C, h.Ct); h.d.assign(d, d + m);
     }
     if (l > 0) {
         if (!f) return lpbox_fail(LPBOX_E_BADARG, "f missing");
-        if ((rc = gen_load_csr(h.E, l, n, Ep, Ei, Ev, "E")) < 0) return rc;
+        if ((rc = gen_load_csr(h.E, l, n, Ep, Ei, Ev, "E")) < 0 || (rc = gen_check_finite(f, l, "f")) < 0) return rc;
         gen_transpose(h.E, h.Et); h.f.assign(f, f + l);
     }
     h.n = n; h.m = m; h.l = l;

@@ -9,6 +9,7 @@
 #include "lpbox_seg.h"
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -374,6 +375,13 @@ int batch_run_chain(const ChainRules &rules, const SegDev *devs, SegState *dstat
     return LPBOX_OK;
 }
 
+// `(int)energy` of SEGcpp:1379 as a defined conversion: truncation toward zero while the result fits an int, INT_MIN otherwise (NaN
+// included) -- the value the reference's cast yields on x86-64 (cvttsd2si), where the C++ cast itself is undefined.  oracle/seg_oracle.c
+// and oracle/bqp_numpy.py convert the same way.
+int energy_int(double e) {
+    return e > -2147483649.0 && e < 2147483648.0 ? (int)e : INT_MIN;
+}
+
 }  // namespace
 
 SegSolver *segc_create(int print_info, int device) {
@@ -395,7 +403,7 @@ void segc_destroy(SegSolver *s) {
 }
 
 int segc_set_problem(SegSolver *s, int n, int nnz, const int *rowptr, const int *colidx, const double *vals, const double *b,
-                     double c, int rows, int cols) {
+                     double c, int rows, int cols, bool from_image) {
     if (s->uploaded) return lpbox_fail(LPBOX_E_STATE, "problem already uploaded; create a new handle to change it");
     if (n <= 0 || nnz <= 0 || !rowptr || !colidx || !vals || !b) return lpbox_fail(LPBOX_E_BADARG, "bad problem arguments");
     if (rowptr[0] != 0 || rowptr[n] != nnz) return lpbox_fail(LPBOX_E_BADARG, "rowptr does not span nnz");
@@ -405,10 +413,18 @@ int segc_set_problem(SegSolver *s, int n, int nnz, const int *rowptr, const int 
         for (int k = rowptr[i]; k < rowptr[i + 1]; k++) {
             if (colidx[k] < 0 || colidx[k] >= n) return lpbox_fail(LPBOX_E_BADARG, "column index out of range");
             if (k > rowptr[i] && colidx[k] <= colidx[k - 1]) return lpbox_fail(LPBOX_E_BADARG, "column indices must ascend inside a row");
+            if (!from_image && !std::isfinite(vals[k])) return lpbox_fail(LPBOX_E_BADARG, "vals has a non-finite stored value (row %d, column %d)", i, colidx[k]);
             diag |= colidx[k] == i;
         }
         if (!diag) return lpbox_fail(LPBOX_E_BADARG, "row %d stores no diagonal entry (the reference always stores one, SEGcpp:213-219)", i);
     }
+    // a NaN in b makes every PCG exit test false: up to 1e4 x 1e3 PCG iterations of halt-and-resume chains before the call returns (the
+    // reference accepts it and computes garbage; the same deliberate deviation as the LP path's, DESIGN.md sections 24 and 26).  What
+    // the library's own cost builder made of an image is taken as it is: a constant image divides by a zero variance, every weight is
+    // NaN, and the reference's result there -- NaN iterates -- is reproduced bit for bit (tests/test_seg_fuzz_gpu.py).
+    for (int i = 0; i < n && !from_image; i++)
+        if (!std::isfinite(b[i])) return lpbox_fail(LPBOX_E_BADARG, "b has a non-finite entry (index %d)", i);
+    if (!from_image && !std::isfinite(c)) return lpbox_fail(LPBOX_E_BADARG, "c is not finite");
     s->n = n; s->nnz = nnz; s->rows = rows; s->cols = cols; s->c = c;
     s->rowptr.assign(rowptr, rowptr + n + 1); s->colidx.assign(colidx, colidx + nnz); s->vals.assign(vals, vals + nnz);
     s->orgb.assign(b, b + n);
@@ -426,7 +442,7 @@ int segc_set_image(SegSolver *s, const unsigned char *gray, int rows, int cols, 
     if (sr < 2 || sc < 2) return lpbox_fail(LPBOX_E_BADARG, "scaled image %dx%d too small", sr, sc);
     std::vector<int> rowptr, colidx; std::vector<double> vals, b; double c = 0;
     build_costs(src, sr, sc, rowptr, colidx, vals, b, c);
-    return segc_set_problem(s, sr * sc, (int)colidx.size(), rowptr.data(), colidx.data(), vals.data(), b.data(), c, sr, sc);
+    return segc_set_problem(s, sr * sc, (int)colidx.size(), rowptr.data(), colidx.data(), vals.data(), b.data(), c, sr, sc, true);
 }
 
 int segc_init(SegSolver *s) {
@@ -459,7 +475,7 @@ int segc_legacy(SegSolver *s, int *energy) {                                  //
     if (rc) return rc;
     s->rec_cols = s->record > 0 ? std::min(s->hst.cc, s->ws_cap) : 0;
     s->xi_valid = false; s->win_serial++;
-    if (energy) *energy = (int)(s->hst.cur_obj + s->c);                        // :1379
+    if (energy) *energy = energy_int(s->hst.cur_obj + s->c);                   // :1379
     return LPBOX_OK;
 }
 
@@ -507,7 +523,7 @@ int segc_legacy_batch(SegSolver **ss, int B, int *energies) {
         SegSolver *s = ss[i];
         s->hst = hs[i]; s->parity = parity; s->rec_cols = 0; s->xi_valid = false; s->inited = true;
         s->chain.pcg_resumes += resumes[i];
-        if (energies) energies[i] = (int)(s->hst.cur_obj + s->c);     // :1379
+        if (energies) energies[i] = energy_int(s->hst.cur_obj + s->c); // :1379
     }
     s0->kernel_ms += ms; s0->launches += launches;
     return LPBOX_OK;

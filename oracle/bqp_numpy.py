@@ -431,7 +431,8 @@ class NumpySeg:
             it += 1
         self.legacy_iter_plus1 = it + 1
         self.cur_obj = cost((self.x >= 0.5).astype(float), self.A, self.b)
-        return int(self.cur_obj + self.c)
+        e = self.cur_obj + self.c           # (int)energy (:1379): truncated while it fits an int, INT_MIN otherwise (x86-64's cast)
+        return int(e) if -2147483649.0 < e < 2147483648.0 else -2147483648
 
     def get_x_sol(self):
         out = np.zeros(self.org_n)

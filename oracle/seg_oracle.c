@@ -468,6 +468,12 @@ static int iteration(sego_t *o, int iter, int l2f, int *ret, int *cc) {
     return 0;
 }
 
+/* (int)energy of :1379 as a defined conversion: truncation toward zero while the result fits an int, INT_MIN otherwise (NaN included) --
+   what the reference's cast yields on x86-64 (cvttsd2si); the C cast itself is undefined there. */
+static int energy_int(double e) {
+    return e > -2147483649.0 && e < 2147483648.0 ? (int)e : (-2147483647 - 1);
+}
+
 int sego_legacy(sego_t *o) {                                                /* SEGcpp:1200-1380 */
     if (!o->inited) return -1;
     int ret = 0, cc = 0, iter;
@@ -476,7 +482,7 @@ int sego_legacy(sego_t *o) {                                                /* S
     o->iter_legacy_p1 = iter + 1;
     for (int i = 0; i < o->n; i++) o->tv[i] = o->x[i] >= 0.5 ? 1.0 : 0.0;   /* :1371-1372 */
     o->cur_obj = compute_cost(o, o->tv);
-    return (int)(o->cur_obj + o->c);                                        /* :1379 */
+    return energy_int(o->cur_obj + o->c);                                   /* :1379 */
 }
 
 int sego_l2f(sego_t *o, int iter_start, int iter_end, const double *vec, int fix_num) {   /* SEGcpp:917-1195 */

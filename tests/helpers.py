@@ -37,6 +37,21 @@ def bits_equal(a, b):
     return a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
 
 
+def bits_equal_nan(a, b):
+    """bits_equal for data that may hold NaN: a NaN must meet a NaN in the same place, whatever the two NaNs' sign and payload bits (IEEE
+    754 leaves both to the implementation, and a compiler may turn a - b into -(b - a), which flips a NaN's sign); every other value is compared by bit pattern, so -0.0 still differs from +0.0."""
+    a = np.array(a, np.float64, ndmin=1)
+    b = np.array(b, np.float64, ndmin=1)
+    a[np.isnan(a)] = np.nan
+    b[np.isnan(b)] = np.nan
+    return bits_equal(a, b)
+
+
+def scalar_bits_equal(a, b):
+    """Two float64 scalars by the rule of bits_equal_nan: NaN equals NaN, -0.0 differs from +0.0."""
+    return bits_equal_nan(np.array([a], np.float64), np.array([b], np.float64))
+
+
 def oracle_like(g, I):
     """CPU oracle configured with the reduction tree of the HIP solver `g` (threads + storage positions)."""
     return oracle_for(g.batch if hasattr(g, "batch") else g, 0, I)
@@ -258,6 +273,17 @@ def assert_within_bound(got, ref, e, g, tag):
     d = np.abs(got - ref).max(initial=0.0)
     B = spread_bound(e, g)
     assert d <= B, f"{tag}: |got - restatement| = {d:.3e} > B = {B:.3e}"
+
+
+def assert_within_bound_nan(got, ref, e, g, tag):
+    """assert_within_bound where the data may hold NaN: an entry that is NaN in `got`, in the restatement AND in both oracle orders counts
+    as agreement, a NaN on one side alone is a failure (the rule of tests/lp_steplock.py); the other entries are held to B of their own."""
+    got, ref, e, g = (np.atleast_1d(np.asarray(v, float)) for v in (got, ref, e, g))
+    assert got.shape == ref.shape == e.shape == g.shape, f"{tag}: shapes {got.shape}, {ref.shape}, {e.shape}, {g.shape}"
+    nan = np.isnan(ref)
+    for name, v in (("subject", got), ("eigen-order oracle", e), ("kernel-order oracle", g)):
+        assert np.array_equal(np.isnan(v), nan), f"{tag}: NaN in other places in the {name} than in the restatement"
+    assert_within_bound(got[~nan], ref[~nan], e[~nan], g[~nan], tag)
 
 
 def common_prefix(*traces):

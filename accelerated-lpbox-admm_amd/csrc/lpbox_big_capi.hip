@@ -507,7 +507,8 @@ int lpbox_big_init(lpbox_big_t *h) {
         auto groups = [](long nn, int ept) { return (int)((nn + (long)BIG_T * ept - 1) / ((long)BIG_T * ept)); };
         h->EPT = 2; while (groups(nmax, h->EPT) > fold_cap && h->EPT < 8) h->EPT *= 2;
         if (groups(nmax, h->EPT) > fold_cap) { h->EPT = 2; while (groups(nmax, h->EPT) > 2 * BIG_T * 8 && h->EPT < 64) h->EPT *= 2; }
-        if (const char *e = getenv("LPBOX_BIG_EPT")) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4 || v == 8 || v == 16) h->EPT = std::max(v, h->EPT); }   // tuning
+        // tuning: MORE slots per thread than the rule above picks, never fewer (the rule's EPT is at least 2, so 1 and 2 would change nothing)
+        if (const char *e = getenv("LPBOX_BIG_EPT")) { const int v = atoi(e); if (v == 4 || v == 8 || v == 16) h->EPT = std::max(v, h->EPT); }
         h->G = groups(n, h->EPT);
         h->Gs = std::max(groups(nmax, h->EPT), 1);
         h->fold = !h->ref && h->Gs <= fold_cap && h->world <= BIG_MAXW && getenv("LPBOX_BIG_NOFOLD") == nullptr;   // LPBOX_BIG_NOFOLD: keep the reduction launches (A/B)

@@ -167,6 +167,26 @@ def test_plain_windows_of_length_one_and_two(cfg, case):
     assert c.done or (c.checked == len(steps) and o.total_outer_iters == 80)
 
 
+@pytest.mark.parametrize("n,ranks", [(9000, 1), (17000, 2)])
+def test_second_level_with_more_partials_than_threads(n, ranks):
+    """The oracle's two-level order with MORE workgroup partials than threads (redux_sum_gpu_full(part, Gn, T) with Gn > T): T = 64 and
+    chunks of 64 positions give a rank more than 128 partials, so every thread of the second level adds up to three of them (t, t + 64,
+    t + 128) before the tree -- the multi-slot loop that the large route's kernels run above 256 workgroups.  Iterations 0..29 (the rho
+    update at 25), the bound of the unit cases."""
+    from lpbox_hip.synth import make_auction_like
+    I = make_auction_like(n, 1)
+    per_rank = -(-n // ranks)
+    assert 128 < -(-per_rank // 64) <= 192                      # three slots per thread, the third partly filled
+    o = O.LpOracle(0, order=O.ORDER_GPU, T=64, chunk=64, ranks=ranks)
+    o.set_problem(I["n"], I["l"], I["colptr"], I["rowidx"], I["b"])
+    o.solve_init()
+    c = S.Case(I, S.OracleSubject(o), f"gpu64c64 ranks{ranks} auction{n}")
+    assert c.c == STEPLOCK_C
+    S.run_cases(S.OracleGroup([o]), [c], S.l2f_steps(0, 30))
+    check([c])
+    assert c.checked == 30 and not c.done and o.total_outer_iters == 30
+
+
 def test_calibration_of_c():
     """c is calibrated on the restatement alone: the distance of every float64 permuted member from the natural member, over the spread of
     the other eleven; the worst over all named cases must stay below c / 2 (helpers.STEPLOCK_C)."""

@@ -96,6 +96,25 @@ hipError_t big_launch_z4(const BigDev &d, int init_only, int *parity, hipStream_
 hipError_t big_launch_resume(const BigDev &d, int reset_pcg_max, int *parity, hipStream_t s);
 hipError_t big_launch_rank_sum(const double *g, int W, long count, long stride, double *out, hipStream_t s);   // rank-ordered sum of W gathered contributions
 
+// ---- a BATCH of problems through one launch chain in lockstep (lpbox_big_batch_*; one rank each, folded reductions, plain windows) ----
+// devs: device array of B descriptors; every launch has the grid (X, B), X the largest extent of that kernel over the batch -- the
+// kernels differ in what they are launched over, so there is one maximum per kind.  Row blockIdx.y of a grid works on problem
+// blockIdx.y alone: its own state, partials and vectors, the reduction tree and the row / column order of its own handle.
+struct BigBatchGrid {
+    int B;
+    int cols;      // max G: prep, rhs_cols, resid, pcg_cols, pcg_upd, post
+    int y;         // max of max(G, Gl)
+    int rows;      // max of (P > 1 ? Glr : Gl)
+    int z4;        // max Gl
+};
+hipError_t bigb_launch_set_window(const BigDev *devs, const BigBatchGrid &g, int iter_start, int iter_end, int *parity, hipStream_t s);
+hipError_t bigb_launch_resume(const BigDev *devs, const BigBatchGrid &g, int reset_pcg_max, int *parity, hipStream_t s);
+hipError_t bigb_launch_prep(const BigDev *devs, const BigBatchGrid &g, int do_prep, int *parity, hipStream_t s);
+hipError_t bigb_enqueue_pcg(const BigDev *devs, const BigBatchGrid &g, int pairs, int *parity, hipStream_t s);      // pairs x (rows(1), pcg_cols, pcg_upd)
+hipError_t bigb_enqueue_tail(const BigDev *devs, const BigBatchGrid &g, int *parity, hipStream_t s);                // post, rows(0), z4
+hipError_t bigb_enqueue_iterations(const BigDev *devs, const BigBatchGrid &g, int iters, int kmax, int *parity, hipStream_t s);   // 8 + 3 kmax launches each
+hipError_t bigb_collect_states(const BigDev *devs, const BigBatchGrid &g, int parity, BigState *out, hipStream_t s);   // out[i] = st[parity] of problem i
+
 // ---- reference-order mode of this path (lpbox_big_set_order(LPBOX_ORDER_REFERENCE), one rank; lpbox_big_ref_kernels.hip) ----
 // Every reduction over the live variables follows Eigen's redux (oracle/lpbox_oracle.c redux_sum_eigen): the producers write their
 // per-variable terms into `stage` at the variable's LIVE RANK instead of summing them per workgroup, a walker kernel adds them up in

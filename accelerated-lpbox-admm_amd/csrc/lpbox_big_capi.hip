@@ -826,4 +826,237 @@ int lpbox_big_get_scalar(lpbox_big_t *h, const char *name, double *out) {
     return lpbox_fail(LPBOX_E_BADARG, "unknown scalar '%s'", name);
 }
 
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------
+// A BATCH of large-route handles through ONE launch chain in lockstep: plain windows (ADMM_lp_iters) of every
+// member at once, grid (X, B) per launch, each member on its own control state -- one that has stopped, reached the end of the
+// window or whose PCG has converged falls through; a BIG_HALT_PCG_MORE on any member resumes the chain for all.  The handles are
+// borrowed and stay ordinary handles: per member the arithmetic is that of lpbox_big_iterate on its own, bit for bit.
+struct lpbox_big_batch {
+    std::vector<lpbox_big *> hs;
+    int B = 0, device = 0;
+    bool inited = false;
+    ChainRules rules = CHAIN_RULES_BIG;
+    int kmax = CHAIN_RULES_BIG.kmax_start;
+    bool adaptive = true, use_graph = false;
+    hipStream_t stream = nullptr;
+    StreamTimer timer;
+    GraphCache graphs;                              // two iterations per (kmax, start parity); the grid extents never change
+    BigBatchGrid grid{0, 0, 0, 0, 0};
+    DevBuf<BigDev> devs; DevBuf<BigState> dstates;
+    std::vector<BigDev> h_devs;                     // host side of devs (alive until the stream has taken it)
+    std::vector<BigState> h_states;
+    double kernel_ms = 0.0; long long launches = 0, collectives = 0, parity_copies = 0;
+};
+
+namespace {
+
+// what a member must be for the lockstep chain; `i` names it in the message.  Checked at create, init and iterate: a handle can be
+// changed between the calls (recording switched on, an early-fixing window of its own).
+int bigb_member_ok(const lpbox_big *h, int i) {
+    if (!h || !h->has_problem) return lpbox_fail(LPBOX_E_STATE, "problem %d of the batch has no problem", i);
+    if (h->ref) return lpbox_fail(LPBOX_E_UNSUPPORTED, "problem %d of the batch runs in the reference summation order; the batch runs the default order", i);
+    if (h->world != 1) return lpbox_fail(LPBOX_E_UNSUPPORTED, "problem %d of the batch is sharded over %d ranks; the batch runs one rank per problem", i, h->world);
+    if (h->comm || h->ag) return lpbox_fail(LPBOX_E_UNSUPPORTED, "problem %d of the batch has a transport; the batch issues no collectives", i);
+    if (h->lean) return lpbox_fail(LPBOX_E_UNSUPPORTED, "problem %d of the batch uses the comm-lean PCG", i);
+    if (h->record) return lpbox_fail(LPBOX_E_UNSUPPORTED, "problem %d of the batch is recording; recording is per handle (lpbox_big_iterate)", i);
+    if (h->uploaded && !h->fold)
+        return lpbox_fail(LPBOX_E_UNSUPPORTED, "problem %d of the batch runs without folded reductions (LPBOX_BIG_NOFOLD, or more than %d workgroups)", i, BIG_FOLD_U * BIG_T);
+    if (h->inited && h->n_live_glob != h->n_glob)
+        return lpbox_fail(LPBOX_E_UNSUPPORTED, "problem %d of the batch has fixed variables; early-fixing windows are per handle (lpbox_big_iterate_l2f)", i);
+    return LPBOX_OK;
+}
+
+int bigb_collect(lpbox_big_batch *b, int parity) {
+    HIPCHK(bigb_collect_states(b->devs.p, b->grid, parity, b->dstates.p, b->stream));
+    HIPCHK(hipMemcpyAsync(b->h_states.data(), b->dstates.p, sizeof(BigState) * (size_t)b->B, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    return LPBOX_OK;
+}
+
+// The lockstep chain up to iter_end (the window already set); the loop of batch_run_chain in lpbox_seg_capi.hip with this route's
+// launches.  b->h_states receives the final states; resumes[i] is raised for every member whose own state showed the halt at a resume.
+int bigb_run_chain(lpbox_big_batch *b, int iter_end, int *parity, long long *resumes) {
+    const ChainRules &rules = b->rules;
+    const BigDev *devs = b->devs.p;
+    const BigBatchGrid &g = b->grid;
+    hipStream_t st = b->stream;
+    std::vector<int> resumed(b->B, 0);                              // per member: resumes since one of its outer iterations last completed
+    for (;;) {
+        CHK(bigb_collect(b, *parity));
+        bool more = false, any_run = false;
+        int remaining = 0, vote = 0, pcg_k = 0;
+        for (int i = 0; i < b->B; i++) {
+            const BigState &h = b->h_states[i];
+            if (h.halt == BIG_HALT_PCG_MORE) {
+                if (++resumed[i] > rules.resume_limit())
+                    return lpbox_fail(LPBOX_E_STATE, "problem %d of the batch, iteration %d: the PCG is still halted at k = %d after %d resumes in a row", i, h.iter, h.pcg_k, resumed[i] - 1);
+                resumes[i]++; more = true; pcg_k = std::max(pcg_k, h.pcg_k);
+                continue;
+            }
+            resumed[i] = 0;
+            if (h.halt != BIG_HALT_NONE) continue;
+            const int rem = iter_end - h.iter;
+            if (rem <= 0 && !h.have_prev) continue;
+            any_run = true; remaining = std::max(remaining, rem);
+            vote = std::max(vote, chain_pcg_vote(rules, b->kmax, chain_view(h)));
+        }
+        if (more) {                                                 // some PCG ran out of launch groups: resume it (the others fall through)
+            HIPCHK(bigb_launch_resume(devs, g, 0, parity, st));
+            HIPCHK(bigb_enqueue_pcg(devs, g, CHAIN_PAIRS_PER_RESUME, parity, st));
+            HIPCHK(bigb_enqueue_tail(devs, g, parity, st));
+            b->launches += 4 + 3 * CHAIN_PAIRS_PER_RESUME;
+            if (b->adaptive) b->kmax = chain_kmax_after_halt(rules, b->kmax, pcg_k);
+            continue;
+        }
+        if (!any_run) break;
+        if (b->adaptive) b->kmax = chain_kmax_for_vote(rules, vote);
+        const int kmax = b->kmax;
+        HIPCHK(bigb_launch_resume(devs, g, 1, parity, st));
+        int batch = chain_batch_iters(rules, remaining);
+        const int per_graph = rules.iters_per_graph;
+        auto enqueue = [&](int n) {
+            HIPCHK(bigb_enqueue_iterations(devs, g, n, kmax, parity, st));
+            b->launches += (long long)n * (8 + 3 * kmax);
+            return (int)LPBOX_OK;
+        };
+        if (b->use_graph && batch >= per_graph) {
+            ChainIo io{st, *parity, b->launches, b->collectives, b->use_graph, true};
+            const GraphCache::Entry *ge = nullptr;
+            if (b->graphs.get(kmax, io, [&] { return enqueue(per_graph); }, &ge) < 0) {     // go on with eager launches for good
+                b->use_graph = false;
+                (void)hipGetLastError();
+            } else {
+                for (; batch >= per_graph; batch -= per_graph) { HIPCHK(hipGraphLaunch(ge->exec, st)); b->launches += ge->launches; }
+            }
+        }
+        if (batch > 0) CHK(enqueue(batch));
+        HIPCHK(bigb_launch_prep(devs, g, 0, parity, st));
+        b->launches += 2;
+    }
+    return LPBOX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+lpbox_big_batch_t *lpbox_big_batch_create(lpbox_big_t **handles, int count) {
+    auto refuse = [](int) -> lpbox_big_batch * { return nullptr; };        // lpbox_fail has recorded status and text
+    if (!handles || count <= 0) return refuse(lpbox_fail(LPBOX_E_BADARG, "empty batch"));
+    for (int i = 0; i < count; i++) {                               // no device call
+        if (bigb_member_ok(handles[i], i) < 0) return nullptr;
+        if (handles[i]->device != handles[0]->device) return refuse(lpbox_fail(LPBOX_E_BADARG, "problem %d of the batch lives on another device than problem 0", i));
+        for (int k = 0; k < i; k++)
+            if (handles[k] == handles[i]) return refuse(lpbox_fail(LPBOX_E_BADARG, "problem %d and problem %d of the batch are the same handle", k, i));
+    }
+    lpbox_big_batch *b = new lpbox_big_batch();
+    b->hs.assign(handles, handles + count); b->B = count; b->device = handles[0]->device;
+    if (const char *e = getenv("LPBOX_BIG_KMAX")) { int v = atoi(e); if (v >= 1 && v <= 1000) { b->kmax = v; b->adaptive = false; } }
+    if (const char *e = getenv("LPBOX_BIG_KMARGIN")) b->rules.margin = std::max(0, atoi(e));
+    if (const char *e = getenv("LPBOX_BIG_BATCH_GRAPH")) b->use_graph = atoi(e) != 0;     // replay captured iterations instead of eager launches
+    return b;
+}
+
+void lpbox_big_batch_destroy(lpbox_big_batch_t *b) {
+    if (!b) return;
+    if (b->stream) {
+        (void)hipSetDevice(b->device);
+        (void)hipStreamSynchronize(b->stream);
+        b->graphs.clear();
+        b->timer.destroy();
+        (void)hipStreamDestroy(b->stream);
+    }
+    delete b;
+}
+
+// lpbox_big_init on every member (a handful of launches once per solve), then the descriptors of all members in one device array
+int lpbox_big_batch_init(lpbox_big_batch_t *b) {
+    if (!b) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
+    for (int i = 0; i < b->B; i++) CHK(bigb_member_ok(b->hs[i], i));
+    CHK(use_device(b->device));
+    b->inited = false;
+    for (int i = 0; i < b->B; i++) CHK(lpbox_big_init(b->hs[i]));
+    for (int i = 0; i < b->B; i++) CHK(bigb_member_ok(b->hs[i], i));           // folded reductions are decided by the upload
+    for (int i = 0; i < b->B; i++) HIPCHK(hipStreamSynchronize(b->hs[i]->stream));
+    if (!b->stream) {
+        HIPCHK(hipStreamCreate(&b->stream));
+        HIPCHK(b->timer.create());
+        HIPCHK(b->devs.alloc(b->B)); HIPCHK(b->dstates.alloc(b->B));
+        b->h_devs.resize(b->B); b->h_states.resize(b->B);
+    }
+    BigBatchGrid g{b->B, 0, 0, 0, 0};
+    for (int i = 0; i < b->B; i++) {
+        const lpbox_big *h = b->hs[i];
+        g.cols = std::max(g.cols, h->G); g.y = std::max(g.y, std::max(h->G, h->Gl));
+        g.rows = std::max(g.rows, h->P > 1 ? h->Glr : h->Gl); g.z4 = std::max(g.z4, h->Gl);
+    }
+    if (g.cols != b->grid.cols || g.y != b->grid.y || g.rows != b->grid.rows || g.z4 != b->grid.z4) b->graphs.clear();
+    b->grid = g;
+    b->inited = true;
+    return 1;
+}
+
+// ADMM_lp_iters (LPcpp:766-1095) of every member over [iter_start, iter_end); rets[i] = member i's return value
+int lpbox_big_batch_iterate(lpbox_big_batch_t *b, int iter_start, int iter_end, int *rets) {
+    if (!b) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
+    if (!b->inited) return lpbox_fail(LPBOX_E_STATE, "lpbox_big_batch_init has not been called");
+    for (int i = 0; i < b->B; i++) {
+        CHK(bigb_member_ok(b->hs[i], i));
+        if (!b->hs[i]->inited) return lpbox_fail(LPBOX_E_STATE, "problem %d of the batch: solve_init has not been called", i);
+    }
+    CHK(use_device(b->device));
+    hipStream_t st = b->stream;
+    for (int i = 0; i < b->B; i++) HIPCHK(hipStreamSynchronize(b->hs[i]->stream));     // windows of its own in between have completed
+    // one ping-pong parity for the chain: a member that ran windows of its own in between may sit on the other one
+    int parity = b->hs[0]->parity;
+    long long copies = 0;
+    for (int i = 1; i < b->B; i++) {
+        lpbox_big *h = b->hs[i];
+        if (h->parity != parity) { HIPCHK(big_launch_resume(h->dev(), 0, &h->parity, st)); copies++; }   // st[in] -> st[out]; no halt is pending between windows
+    }
+    for (int i = 0; i < b->B; i++) b->h_devs[i] = b->hs[i]->dev();
+    HIPCHK(hipMemcpyAsync(b->devs.p, b->h_devs.data(), sizeof(BigDev) * (size_t)b->B, hipMemcpyHostToDevice, st));
+    HIPCHK(b->timer.start(st));
+    const long long l0 = b->launches;
+    b->launches += copies; b->parity_copies += copies;
+    HIPCHK(bigb_launch_set_window(b->devs.p, b->grid, iter_start, iter_end, &parity, st));
+    b->launches++;
+    std::vector<long long> resumes(b->B, 0);
+    const int rc = bigb_run_chain(b, iter_end, &parity, resumes.data());
+    double ms = 0.0;
+    const hipError_t e = b->timer.stop_sync(st, &ms);
+    if (rc < 0) return rc;
+    HIPCHK(e);
+    b->kernel_ms += ms;
+    for (int i = 0; i < b->B; i++) {
+        lpbox_big *h = b->hs[i];
+        h->hst = b->h_states[i]; h->parity = parity;
+        h->chain.pcg_resumes += resumes[i];
+        if (rets) rets[i] = h->hst.ret;
+    }
+    b->hs[0]->kernel_ms += ms; b->hs[0]->launches += b->launches - l0;      // the chain's launches are nobody's in particular: booked on member 0
+    return LPBOX_OK;
+}
+
+int lpbox_big_batch_get_scalar(lpbox_big_batch_t *b, const char *name, double *out) {
+    if (!b || !name || !out) return lpbox_fail(LPBOX_E_BADARG, "bad handle / name / output");
+    if (!strncmp(name, "pcg_resumes_", 12)) {
+        char *end = nullptr;
+        const long i = strtol(name + 12, &end, 10);
+        if (end == name + 12 || *end || i < 0 || i >= b->B) return lpbox_fail(LPBOX_E_BADARG, "'%s': no such member", name);
+        *out = (double)b->hs[i]->chain.pcg_resumes;
+        return LPBOX_OK;
+    }
+    struct { const char *n; double v; } tab[] = {
+        {"count", (double)b->B}, {"launches", (double)b->launches}, {"kernel_ms", b->kernel_ms}, {"kmax", (double)b->kmax},
+        {"graph", b->use_graph ? 1.0 : 0.0}, {"parity_copies", (double)b->parity_copies},
+        {"grid_cols", (double)b->grid.cols}, {"grid_y", (double)b->grid.y}, {"grid_rows", (double)b->grid.rows}, {"grid_z4", (double)b->grid.z4},
+    };
+    for (auto &e : tab) if (!strcmp(e.n, name)) { *out = e.v; return LPBOX_OK; }
+    return lpbox_fail(LPBOX_E_BADARG, "unknown scalar '%s'", name);
+}
+
 }  // extern "C"

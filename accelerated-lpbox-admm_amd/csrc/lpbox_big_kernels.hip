@@ -126,21 +126,21 @@ __global__ void big_k_init2(BigDev d) {       // after the partial of b.x0 has b
     d.st[1].best_bin_obj = d.red[BIG_PH_X * BIG_NPART];
 }
 
-__global__ void big_k_set_window(BigDev d, int in, int out, int iter_start, int iter_end, int l2f) {
+__device__ __forceinline__ void big_b_set_window(const BigDev &d, int in, int out, int iter_start, int iter_end, int l2f) {
     d.st[out] = d.st[in];
     BigState *s = d.st + out;
     s->iter = iter_start; s->iter_start = iter_start; s->iter_end = iter_end; s->ret = 0; s->stop = LP_STOP_NONE; s->halt = BIG_HALT_NONE;
     s->l2f = l2f & 1; s->rec = (l2f >> 1) & 1; s->cc = 0;
 }
 
-__global__ void big_k_resume(BigDev d, int in, int out, int reset_pcg_max) {
+__device__ __forceinline__ void big_b_resume(const BigDev &d, int in, int out, int reset_pcg_max) {
     d.st[out] = d.st[in];
     if (d.st[out].halt == BIG_HALT_PCG_MORE) d.st[out].halt = BIG_HALT_NONE;
     if (reset_pcg_max) d.st[out].pcg_max = 0;
 }
 
 // finalise the previous iteration from red[0..5) (x.x, |x-y1|^2, |x-y2|^2, b.x, b.round(x)), then partial ||x+z2/rho2-1/2||^2
-__global__ void __launch_bounds__(T) big_k_prep(BigDev d, int in, int out, int do_prep) {
+__device__ __forceinline__ void big_b_prep(const BigDev &d, int in, int out, int do_prep) {
     __shared__ double red[2 * RED_MAXV * RED_MAXW];
     int parity = 0;
     const BigState *si = d.st + in;
@@ -212,7 +212,7 @@ __global__ void __launch_bounds__(T) big_k_prep(BigDev d, int in, int out, int d
 }
 
 // y1, y2, expression refresh (:831-866), rhs base, PCG start x0 = y1; for the rows: y3 = max(0, f - Ex - z4/rho4), fz = (f - y3, z4)
-__global__ void __launch_bounds__(T) big_k_y(BigDev d, int in, int out) {
+__device__ __forceinline__ void big_b_y(const BigDev &d, int in, int out) {
     __shared__ double red[2 * RED_MAXV * RED_MAXW];
     int parity = 0;
     const BigState *si = d.st + in;
@@ -263,7 +263,7 @@ __global__ void __launch_bounds__(T) big_k_y(BigDev d, int in, int out) {
     }
 }
 
-__global__ void __launch_bounds__(T) big_k_rhs_cols(BigDev d, int in, int out) {   // :874-877
+__device__ __forceinline__ void big_b_rhs_cols(const BigDev &d, int in, int out) {   // :874-877
     const BigState *si = d.st + in;
     if (si->halt || si->phase != 1) { forward_state(d, in, out); return; }
     const double r4Et = si->r4Et;
@@ -343,7 +343,7 @@ __device__ __forceinline__ double row_sum_sliced(const BigDev &d, int i, const d
     return acc;
 }
 
-__global__ void __launch_bounds__(T) big_k_rows(BigDev d, int in, int out, int mode) {
+__device__ __forceinline__ void big_b_rows(const BigDev &d, int in, int out, int mode) {
     __shared__ double red[2 * RED_MAXV * RED_MAXW];
     int parity = 0;
     const BigState *si = d.st + in;
@@ -461,7 +461,7 @@ __global__ void __launch_bounds__(T) big_k_rows(BigDev d, int in, int out, int m
     if (lean_qq) { block_sum<T, 1>(qq, red, parity); if (threadIdx.x == 0) d.lsmall[d.Gs + blockIdx.x] = qq[0]; }
 }
 
-__global__ void __launch_bounds__(T) big_k_resid(BigDev d, int in, int out) {       // :267-294
+__device__ __forceinline__ void big_b_resid(const BigDev &d, int in, int out) {       // :267-294
     __shared__ double red[2 * RED_MAXV * RED_MAXW];
     int parity = 0;
     const BigState *si = d.st + in;
@@ -497,7 +497,7 @@ __global__ void __launch_bounds__(T) big_k_resid(BigDev d, int in, int out) {   
     if (LEADER) { d.st[out] = *si; d.st[out].pcg_k = 0; d.st[out].pcg_done = 0; d.st[out].pcg_first = 0; d.st[out].phase = 2; }
 }
 
-__global__ void __launch_bounds__(T) big_k_pcg_cols(BigDev d, int in, int out) {    // tmp = M p, partial p.tmp (:298-300)
+__device__ __forceinline__ void big_b_pcg_cols(const BigDev &d, int in, int out) {    // tmp = M p, partial p.tmp (:298-300)
     __shared__ double red[2 * RED_MAXV * RED_MAXW];
     int parity = 0;
     const BigState *si = d.st + in;
@@ -542,7 +542,7 @@ __global__ void __launch_bounds__(T) big_k_pcg_cols(BigDev d, int in, int out) {
     forward_state(d, in, out);
 }
 
-__global__ void __launch_bounds__(T) big_k_pcg_upd(BigDev d, int in, int out) {     // :300-317
+__device__ __forceinline__ void big_b_pcg_upd(const BigDev &d, int in, int out) {     // :300-317
     __shared__ double red[2 * RED_MAXV * RED_MAXW];
     int parity = 0;
     const BigState *si = d.st + in;
@@ -676,7 +676,7 @@ __global__ void __launch_bounds__(T) big_k_rank_sum_qq(const double *g, int W, l
 }
 
 // after the PCG: duals z1, z2 (:917-918), the five partials (:931-1003), gsrc = x for the E*x that feeds z4 and the next y3
-__global__ void __launch_bounds__(T) big_k_post(BigDev d, int in, int out) {
+__device__ __forceinline__ void big_b_post(const BigDev &d, int in, int out) {
     __shared__ double red[2 * RED_MAXV * RED_MAXW];
     int parity = 0;
     const BigState *si = d.st + in;
@@ -725,7 +725,7 @@ __global__ void __launch_bounds__(T) big_k_post(BigDev d, int in, int out) {
 }
 
 // Ex = q (= E*x, already all-reduced), z4 dual update (:919-924; the plain loop OVERWRITES z4 on the first iteration of a call)
-__global__ void __launch_bounds__(T) big_k_z4(BigDev d, int in, int out, int init_only) {
+__device__ __forceinline__ void big_b_z4(const BigDev &d, int in, int out, int init_only) {
     const BigState *si = d.st + in;
     if (init_only) {
         for (int s = 0; s < d.EPTl; s++) { const int i = blockIdx.x * (T * d.EPTl) + s * T + threadIdx.x; if (i < d.l) d.Ex[i] = d.q[i]; }
@@ -838,6 +838,42 @@ __global__ void big_k_pack_xiters(BigDev d, const int *live_idx, int rows, int w
     }
 }
 
+// ---- entries.  big_k_*: one problem, the descriptor in the kernel arguments.  big_kb_*: a BATCH of problems in lockstep (one rank each,
+// folded reductions, plain windows), grid (X, B): row blockIdx.y of the grid runs problem blockIdx.y through the same body on its own
+// descriptor, control state, partials and vectors.  X is the largest extent of that kernel over the batch; a workgroup at or beyond its
+// problem's own extent leaves before the first barrier and before any store (the whole workgroup: uniform), so LEADER and every
+// reduction see exactly the workgroups the problem's own launch would have had.
+__global__ void big_k_set_window(BigDev d, int in, int out, int iter_start, int iter_end, int l2f) { big_b_set_window(d, in, out, iter_start, iter_end, l2f); }
+__global__ void big_k_resume(BigDev d, int in, int out, int reset_pcg_max) { big_b_resume(d, in, out, reset_pcg_max); }
+__global__ void __launch_bounds__(T) big_k_prep(BigDev d, int in, int out, int do_prep) { big_b_prep(d, in, out, do_prep); }
+__global__ void __launch_bounds__(T) big_k_y(BigDev d, int in, int out) { big_b_y(d, in, out); }
+__global__ void __launch_bounds__(T) big_k_rhs_cols(BigDev d, int in, int out) { big_b_rhs_cols(d, in, out); }
+__global__ void __launch_bounds__(T) big_k_rows(BigDev d, int in, int out, int mode) { big_b_rows(d, in, out, mode); }
+__global__ void __launch_bounds__(T) big_k_resid(BigDev d, int in, int out) { big_b_resid(d, in, out); }
+__global__ void __launch_bounds__(T) big_k_pcg_cols(BigDev d, int in, int out) { big_b_pcg_cols(d, in, out); }
+__global__ void __launch_bounds__(T) big_k_pcg_upd(BigDev d, int in, int out) { big_b_pcg_upd(d, in, out); }
+__global__ void __launch_bounds__(T) big_k_post(BigDev d, int in, int out) { big_b_post(d, in, out); }
+__global__ void __launch_bounds__(T) big_k_z4(BigDev d, int in, int out, int init_only) { big_b_z4(d, in, out, init_only); }
+
+// the extent of a problem's own launch (big_launch_*), per kernel
+__device__ __forceinline__ int ext_cols(const BigDev &d) { return d.G; }
+__device__ __forceinline__ int ext_y(const BigDev &d) { return d.G > d.Gl ? d.G : d.Gl; }
+__device__ __forceinline__ int ext_rows(const BigDev &d) { return d.P > 1 ? d.Glr : d.Gl; }
+__device__ __forceinline__ int ext_z4(const BigDev &d) { return d.Gl; }
+
+__global__ void big_kb_set_window(const BigDev *__restrict__ devs, int in, int out, int iter_start, int iter_end) { big_b_set_window(devs[blockIdx.y], in, out, iter_start, iter_end, 0); }
+__global__ void big_kb_resume(const BigDev *__restrict__ devs, int in, int out, int reset_pcg_max) { big_b_resume(devs[blockIdx.y], in, out, reset_pcg_max); }
+__global__ void __launch_bounds__(T) big_kb_prep(const BigDev *__restrict__ devs, int in, int out, int do_prep) { const BigDev &d = devs[blockIdx.y]; if ((int)blockIdx.x >= ext_cols(d)) return; big_b_prep(d, in, out, do_prep); }
+__global__ void __launch_bounds__(T) big_kb_y(const BigDev *__restrict__ devs, int in, int out) { const BigDev &d = devs[blockIdx.y]; if ((int)blockIdx.x >= ext_y(d)) return; big_b_y(d, in, out); }
+__global__ void __launch_bounds__(T) big_kb_rhs_cols(const BigDev *__restrict__ devs, int in, int out) { const BigDev &d = devs[blockIdx.y]; if ((int)blockIdx.x >= ext_cols(d)) return; big_b_rhs_cols(d, in, out); }
+__global__ void __launch_bounds__(T) big_kb_rows(const BigDev *__restrict__ devs, int in, int out, int mode) { const BigDev &d = devs[blockIdx.y]; if ((int)blockIdx.x >= ext_rows(d)) return; big_b_rows(d, in, out, mode); }
+__global__ void __launch_bounds__(T) big_kb_resid(const BigDev *__restrict__ devs, int in, int out) { const BigDev &d = devs[blockIdx.y]; if ((int)blockIdx.x >= ext_cols(d)) return; big_b_resid(d, in, out); }
+__global__ void __launch_bounds__(T) big_kb_pcg_cols(const BigDev *__restrict__ devs, int in, int out) { const BigDev &d = devs[blockIdx.y]; if ((int)blockIdx.x >= ext_cols(d)) return; big_b_pcg_cols(d, in, out); }
+__global__ void __launch_bounds__(T) big_kb_pcg_upd(const BigDev *__restrict__ devs, int in, int out) { const BigDev &d = devs[blockIdx.y]; if ((int)blockIdx.x >= ext_cols(d)) return; big_b_pcg_upd(d, in, out); }
+__global__ void __launch_bounds__(T) big_kb_post(const BigDev *__restrict__ devs, int in, int out) { const BigDev &d = devs[blockIdx.y]; if ((int)blockIdx.x >= ext_cols(d)) return; big_b_post(d, in, out); }
+__global__ void __launch_bounds__(T) big_kb_z4(const BigDev *__restrict__ devs, int in, int out) { const BigDev &d = devs[blockIdx.y]; if ((int)blockIdx.x >= ext_z4(d)) return; big_b_z4(d, in, out, 0); }
+__global__ void big_kb_collect(const BigDev *__restrict__ devs, int parity, BigState *out) { out[blockIdx.x] = devs[blockIdx.x].st[parity]; }
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -908,3 +944,53 @@ hipError_t big_launch_pcg_cols(const BigDev &d, int *parity, hipStream_t s) { BI
 hipError_t big_launch_pcg_upd(const BigDev &d, int *parity, hipStream_t s) { BIG_LAUNCH(big_k_pcg_upd, d.G); return hipGetLastError(); }
 hipError_t big_launch_post(const BigDev &d, int *parity, hipStream_t s) { BIG_LAUNCH(big_k_post, d.G); return hipGetLastError(); }
 hipError_t big_launch_z4(const BigDev &d, int init_only, int *parity, hipStream_t s) { BIG_LAUNCH(big_k_z4, d.Gl, init_only); return hipGetLastError(); }
+
+// ---- a batch in lockstep: grid (X, B), X = BigBatchGrid's maximum of that kernel's own extent over the B problems ----
+#define BIGB_LAUNCH(kernel, X, ...)                                                                              \
+    do {                                                                                                         \
+        hipLaunchKernelGGL(kernel, dim3(X, g.B), dim3(T), 0, s, devs, *parity, *parity ^ 1, ##__VA_ARGS__);      \
+        *parity ^= 1;                                                                                            \
+    } while (0)
+
+hipError_t bigb_launch_set_window(const BigDev *devs, const BigBatchGrid &g, int iter_start, int iter_end, int *parity, hipStream_t s) {
+    hipLaunchKernelGGL(big_kb_set_window, dim3(1, g.B), dim3(1), 0, s, devs, *parity, *parity ^ 1, iter_start, iter_end);
+    *parity ^= 1;
+    return hipGetLastError();
+}
+hipError_t bigb_launch_resume(const BigDev *devs, const BigBatchGrid &g, int reset_pcg_max, int *parity, hipStream_t s) {
+    hipLaunchKernelGGL(big_kb_resume, dim3(1, g.B), dim3(1), 0, s, devs, *parity, *parity ^ 1, reset_pcg_max);
+    *parity ^= 1;
+    return hipGetLastError();
+}
+hipError_t bigb_launch_prep(const BigDev *devs, const BigBatchGrid &g, int do_prep, int *parity, hipStream_t s) { BIGB_LAUNCH(big_kb_prep, g.cols, do_prep); return hipGetLastError(); }
+hipError_t bigb_enqueue_pcg(const BigDev *devs, const BigBatchGrid &g, int pairs, int *parity, hipStream_t s) {
+    for (int k = 0; k < pairs; k++) {
+        BIGB_LAUNCH(big_kb_rows, g.rows, 1);
+        BIGB_LAUNCH(big_kb_pcg_cols, g.cols);
+        BIGB_LAUNCH(big_kb_pcg_upd, g.cols);
+    }
+    return hipGetLastError();
+}
+hipError_t bigb_enqueue_tail(const BigDev *devs, const BigBatchGrid &g, int *parity, hipStream_t s) {
+    BIGB_LAUNCH(big_kb_post, g.cols);
+    BIGB_LAUNCH(big_kb_rows, g.rows, 0);
+    BIGB_LAUNCH(big_kb_z4, g.z4);
+    return hipGetLastError();
+}
+hipError_t bigb_enqueue_iterations(const BigDev *devs, const BigBatchGrid &g, int iters, int kmax, int *parity, hipStream_t s) {
+    for (int it = 0; it < iters; it++) {
+        BIGB_LAUNCH(big_kb_prep, g.cols, 1);
+        BIGB_LAUNCH(big_kb_y, g.y);
+        BIGB_LAUNCH(big_kb_rhs_cols, g.cols);
+        BIGB_LAUNCH(big_kb_rows, g.rows, 0);
+        BIGB_LAUNCH(big_kb_resid, g.cols);
+        hipError_t e = bigb_enqueue_pcg(devs, g, kmax, parity, s);
+        if (e == hipSuccess) e = bigb_enqueue_tail(devs, g, parity, s);
+        if (e != hipSuccess) return e;
+    }
+    return hipGetLastError();
+}
+hipError_t bigb_collect_states(const BigDev *devs, const BigBatchGrid &g, int parity, BigState *out, hipStream_t s) {
+    hipLaunchKernelGGL(big_kb_collect, dim3(g.B), dim3(1), 0, s, devs, parity, out);
+    return hipGetLastError();
+}

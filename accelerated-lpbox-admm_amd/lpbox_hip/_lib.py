@@ -120,6 +120,11 @@ SYMBOLS = {
     "lpbox_big_get_vec": (C.c_int, [C.c_void_p, C.c_char_p, _dp, C.c_long]),
     "lpbox_big_get_scalar": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_double)]),
     "lpbox_big_check_infeasible": (C.c_int, [C.c_void_p, C.c_int]),
+    "lpbox_big_batch_create": (C.c_void_p, [C.c_void_p, C.c_int]),
+    "lpbox_big_batch_destroy": (None, [C.c_void_p]),
+    "lpbox_big_batch_init": (C.c_int, [C.c_void_p]),
+    "lpbox_big_batch_iterate": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "lpbox_big_batch_get_scalar": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_double)]),
     "lpbox_bqp_create": (C.c_void_p, [C.c_int]),
     "lpbox_bqp_destroy": (None, [C.c_void_p]),
     "lpbox_bqp_preset": (C.c_int, [C.c_void_p, C.c_int]),

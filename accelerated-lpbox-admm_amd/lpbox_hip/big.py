@@ -214,3 +214,81 @@ class BigLp:
         out = np.zeros(self.c1 - self.c0)
         check(self._L.lpbox_big_get_x_sol(self._h, out), "lpbox_big_get_x_sol")
         return out
+
+
+def _is_problem(p):
+    return isinstance(p, dict) and all(k in p for k in ("n", "l", "colptr", "rowidx", "b"))
+
+
+class BigLpBatch:
+    """A batch of large-route instances through ONE launch chain in lockstep (lpbox_big_batch_* in include/lpbox_hip.h): plain windows
+    of all members at once, each member on its own control state, bit for bit what `BigLp.solve_iter` gives it alone.
+
+    members: problem dicts (a `BigLp` is built for each and closed with the batch) and / or `BigLp` objects (borrowed: one rank, no
+    transport, default order, reference PCG).  `batch[k]` is member k's `BigLp`: its getters, and a `solve_iter` of its own, work between
+    the batch's windows."""
+
+    def __init__(self, members, device=0):
+        members = list(members) if members is not None else []
+        if not members:
+            raise ValueError("BigLpBatch needs at least one problem")
+        for k, m in enumerate(members):
+            if not isinstance(m, BigLp) and not _is_problem(m):
+                raise ValueError(f"member {k} is neither a BigLp nor a problem dict (n, l, colptr, rowidx, b)")
+        self._L = _lib.load()
+        self._own = [not isinstance(m, BigLp) for m in members]
+        self.solvers = [m if isinstance(m, BigLp) else BigLp(m, device=device) for m in members]
+        arr = (C.c_void_p * len(self.solvers))(*[s._h for s in self.solvers])
+        h = self._L.lpbox_big_batch_create(arr, len(self.solvers))
+        if not h:
+            rc = self._L.lpbox_last_status()
+            for s, own in zip(self.solvers, self._own):
+                if own:
+                    s.close()
+            check(rc if rc < 0 else -2, "lpbox_big_batch_create")
+        self._h = C.c_void_p(h)
+
+    def __len__(self):
+        return len(self.solvers)
+
+    def __getitem__(self, k):
+        return self.solvers[k]
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.lpbox_big_batch_destroy(self._h)
+            self._h = None
+            for s, own in zip(self.solvers, self._own):
+                if own:
+                    s.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def solve_init(self):
+        return check(self._L.lpbox_big_batch_init(self._h), "lpbox_big_batch_init")
+
+    def solve_iter(self, i, j):
+        """Iterations [i, j) of every member (ADMM_lp_iters); the members' return values as an int32 array."""
+        rets = np.zeros(len(self.solvers), np.int32)
+        check(self._L.lpbox_big_batch_iterate(self._h, int(i), int(j), rets.ctypes.data_as(C.c_void_p)), "lpbox_big_batch_iterate")
+        return rets
+
+    def scalar(self, name):
+        v = C.c_double()
+        check(self._L.lpbox_big_batch_get_scalar(self._h, name.encode(), C.byref(v)), "lpbox_big_batch_get_scalar")
+        return v.value
+
+
+def solve_many(problems, max_iters=20000, device=0):
+    """Solve every problem to its own stop in one lockstep chain: (rets, binary solutions, objectives cal_Obj())."""
+    batch = BigLpBatch(problems, device=device)
+    try:
+        batch.solve_init()
+        rets = batch.solve_iter(0, int(max_iters))
+        return rets, [s.local_x_sol() for s in batch.solvers], np.array([s.cal_Obj() for s in batch.solvers])
+    finally:
+        batch.close()

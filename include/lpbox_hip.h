@@ -382,6 +382,23 @@ int lpbox_big_get_vec(lpbox_big_t *h, const char *name, double *out, long cap); 
 int lpbox_big_check_infeasible(lpbox_big_t *h, int which);
 int lpbox_big_get_scalar(lpbox_big_t *h, const char *name, double *out);        /* "cur_obj","iter","stop","outer_total","pcg_total",... */
 
+/* A batch of large-route handles through ONE launch chain in lockstep: plain windows (lpbox_big_iterate) of all members at once, every
+ * launch on a grid (workgroups, members).  Each member keeps its own control state and falls through once it has stopped; per member
+ * the results are those of lpbox_big_iterate on its own, bit for bit.  The handles are borrowed: they stay ordinary handles, their
+ * getters and a later lpbox_big_iterate of their own work as if the windows had been their own.  A member must run on one rank without
+ * a transport, in the default summation order with the reference's PCG, with folded reductions (at most 1024 workgroups), without
+ * recording and without fixed variables (LPBOX_E_UNSUPPORTED otherwise); all members on one device, no handle twice (LPBOX_E_BADARG).
+ * A refused call leaves the batch and its members as they were.  LPBOX_BIG_KMAX / LPBOX_BIG_KMARGIN are read at create;
+ * LPBOX_BIG_BATCH_GRAPH=1 replays captured iterations instead of eager launches. */
+typedef struct lpbox_big_batch lpbox_big_batch_t;
+lpbox_big_batch_t *lpbox_big_batch_create(lpbox_big_t **handles, int count);
+void lpbox_big_batch_destroy(lpbox_big_batch_t *b);
+int lpbox_big_batch_init(lpbox_big_batch_t *b);                                  /* lpbox_big_init on every member */
+int lpbox_big_batch_iterate(lpbox_big_batch_t *b, int iter_start, int iter_end, int *rets);   /* ADMM_lp_iters per member; rets[count] */
+/* "count", "launches", "kernel_ms", "kmax", "graph", "parity_copies", "grid_cols" / "grid_y" / "grid_rows" / "grid_z4" (the x-extents
+ * of the launches), "pcg_resumes_<i>" (member i) */
+int lpbox_big_batch_get_scalar(lpbox_big_batch_t *b, const char *name, double *out);
+
 /* ---- generic constrained binary QP: min x'Ax + b'x  s.t.  Cx = d, Ex <= f, x in {0,1}^n -----------------------------------------
  * The reference's ADMM_bqp (Segmentation/.../LPboxADMMsolver.cpp:1384-1832) behind ADMM_bqp_unconstrained / _linear_eq / _linear_ineq /
  * _linear_eq_and_uneq (:1834-2109; C++ only, not in the pyx).  Matrices are CSR with ascending columns; A must store every diagonal

@@ -73,25 +73,28 @@ struct BigDev {
     BigState *st;                         // st[0], st[1]
 };
 
-// launch helpers (lpbox_big_kernels.hip); every state-carrying launch reads st[*parity], writes st[*parity^1], flips *parity
-hipError_t big_launch_init(const BigDev &d, double c1, hipStream_t s);      // state, x = 1, partial b.x0 -> red[0]
+// launch helpers (lpbox_big_kernels.hip); every state-carrying launch reads st[*parity], writes st[*parity^1], flips *parity.
+// rf: nullptr in the default order; the reference-order descriptor (below) otherwise -- the same launch over the same grid, with the
+// phase's terms staged for the walker instead of summed per workgroup, and with the stored values where rf->valued.
+struct BigRef;
+hipError_t big_launch_init(const BigDev &d, const BigRef *rf, double c1, hipStream_t s);      // state, x = 1, b.x0: partial -> red[0], or staged (the caller ranks and walks)
 hipError_t big_launch_init2(const BigDev &d, hipStream_t s);               // best_bin_obj = red[0] (after the all-reduce)
 hipError_t big_launch_set_window(const BigDev &d, int iter_start, int iter_end, int l2f, int *parity, hipStream_t s);
-hipError_t big_launch_fix1(const BigDev &d, hipStream_t s);                          // gsrc = newly fixed values, partial b.x2 (:1237)
-hipError_t big_launch_fix2(const BigDev &d, int *parity, hipStream_t s);              // f -= E2 x2 (:1278), mask, partial |x_live|^2
-hipError_t big_launch_fix3(const BigDev &d, long n_live_new, double c1_new, int *parity, hipStream_t s);   // state + update_expression (:1329)
+hipError_t big_launch_fix1(const BigDev &d, const BigRef *rf, hipStream_t s);                          // gsrc = newly fixed values, terms of b.x2 (:1237)
+hipError_t big_launch_fix2(const BigDev &d, const BigRef *rf, int *parity, hipStream_t s);              // f -= E2 x2 (:1278), mask, terms of |x_live|^2
+hipError_t big_launch_fix3(const BigDev &d, const BigRef *rf, long n_live_new, double c1_new, int *parity, hipStream_t s);   // state + update_expression (:1329)
 hipError_t big_launch_pack_xiters(const BigDev &d, const int *live_idx, int rows, int ws, double *out, hipStream_t s);
-hipError_t big_launch_prep(const BigDev &d, int do_prep, int *parity, hipStream_t s);
+hipError_t big_launch_prep(const BigDev &d, const BigRef *rf, int do_prep, int *parity, hipStream_t s);
 hipError_t big_launch_fin(const BigDev &d, int nv, int phase, hipStream_t s);         // partials of a phase -> red[0..nv)
-hipError_t big_launch_y(const BigDev &d, int *parity, hipStream_t s);                 // y1, y2, refresh, rhs base, y3 (all rows)
-hipError_t big_launch_rhs_cols(const BigDev &d, int *parity, hipStream_t s);          // rhs += r4Et E^T(f-y3) - E^T z4
-hipError_t big_launch_rows(const BigDev &d, int mode, int *parity, hipStream_t s);    // q = E[:,shard] * v  (mode 0: gsrc, 1: PCG p)
-hipError_t big_launch_resid(const BigDev &d, int *parity, hipStream_t s);
-hipError_t big_launch_pcg_cols(const BigDev &d, int *parity, hipStream_t s);
-hipError_t big_launch_pcg_upd(const BigDev &d, int *parity, hipStream_t s);
+hipError_t big_launch_y(const BigDev &d, const BigRef *rf, int *parity, hipStream_t s);                 // y1, y2, refresh, rhs base, y3 (all rows)
+hipError_t big_launch_rhs_cols(const BigDev &d, const BigRef *rf, int *parity, hipStream_t s);          // rhs += r4Et E^T(f-y3) - E^T z4
+hipError_t big_launch_rows(const BigDev &d, const BigRef *rf, int mode, int *parity, hipStream_t s);    // q = E[:,shard] * v  (mode 0: gsrc, 1: PCG p)
+hipError_t big_launch_resid(const BigDev &d, const BigRef *rf, int *parity, hipStream_t s);
+hipError_t big_launch_pcg_cols(const BigDev &d, const BigRef *rf, int *parity, hipStream_t s);
+hipError_t big_launch_pcg_upd(const BigDev &d, const BigRef *rf, int *parity, hipStream_t s);
 hipError_t big_launch_pcg_lean(const BigDev &d, int *parity, hipStream_t s);          // comm-lean mode: tmp = M p, alpha from p.p and q.q, x / r / z updates, partials (r.r, r.z)
 hipError_t big_launch_rank_sum_qq(const double *g, int W, long count, long stride, double *out, double *qq_part, hipStream_t s);   // rank-ordered sum of a row block + q.q partials per 256 rows
-hipError_t big_launch_post(const BigDev &d, int *parity, hipStream_t s);              // duals z1,z2, partials(5), gsrc = x
+hipError_t big_launch_post(const BigDev &d, const BigRef *rf, int *parity, hipStream_t s);              // duals z1,z2, terms(5), gsrc = x
 hipError_t big_launch_z4(const BigDev &d, int init_only, int *parity, hipStream_t s); // Ex = q [, z4 update]
 hipError_t big_launch_resume(const BigDev &d, int reset_pcg_max, int *parity, hipStream_t s);
 hipError_t big_launch_rank_sum(const double *g, int W, long count, long stride, double *out, hipStream_t s);   // rank-ordered sum of W gathered contributions
@@ -139,15 +142,18 @@ hipError_t bigref_launch_rank(const BigDev &d, const BigRef &rf, int mode, hipSt
 // red[phase][0..nv) = redux over the first cnt[which] staged terms.  sidx >= 0: skipped when st[sidx] shows that the producer fell through
 // (halted chain; for the PCG phases C and D also a finished PCG) -- red[] keeps the totals a resumed PCG needs.
 hipError_t bigref_launch_walk(const BigDev &d, const BigRef &rf, int nv, int phase, int which, int sidx, hipStream_t s);
-hipError_t bigref_launch_init(const BigDev &d, const BigRef &rf, double c1, hipStream_t s);
-hipError_t bigref_launch_fix1(const BigDev &d, const BigRef &rf, hipStream_t s);
-hipError_t bigref_launch_fix2(const BigDev &d, const BigRef &rf, int *parity, hipStream_t s);
-hipError_t bigref_launch_fix3(const BigDev &d, const BigRef &rf, long n_live_new, double c1_new, int *parity, hipStream_t s);
-hipError_t bigref_launch_prep(const BigDev &d, const BigRef &rf, int do_prep, int *parity, hipStream_t s);
-hipError_t bigref_launch_y(const BigDev &d, const BigRef &rf, int *parity, hipStream_t s);
-hipError_t bigref_launch_rhs_cols(const BigDev &d, const BigRef &rf, int *parity, hipStream_t s);
-hipError_t bigref_launch_rows(const BigDev &d, const BigRef &rf, int mode, int *parity, hipStream_t s);
-hipError_t bigref_launch_resid(const BigDev &d, const BigRef &rf, int *parity, hipStream_t s);
-hipError_t bigref_launch_pcg_cols(const BigDev &d, const BigRef &rf, int *parity, hipStream_t s);
-hipError_t bigref_launch_pcg_upd(const BigDev &d, const BigRef &rf, int *parity, hipStream_t s);
-hipError_t bigref_launch_post(const BigDev &d, const BigRef &rf, int *parity, hipStream_t s);
+// the staged entries (defined in lpbox_big_ref_kernels.hip, launched by the big_launch_* helpers); _v: the VALUED instantiation
+__global__ void bigref_k_init(BigDev d, BigRef rf, double c1);
+__global__ void bigref_k_prep(BigDev d, BigRef rf, int in, int out, int do_prep);
+__global__ void bigref_k_y_v(BigDev d, BigRef rf, int in, int out);
+__global__ void bigref_k_rhs_cols_v(BigDev d, BigRef rf, int in, int out);
+__global__ void bigref_k_rows_v(BigDev d, BigRef rf, int in, int out, int mode);
+__global__ void bigref_k_resid(BigDev d, BigRef rf, int in, int out);
+__global__ void bigref_k_resid_v(BigDev d, BigRef rf, int in, int out);
+__global__ void bigref_k_pcg_cols(BigDev d, BigRef rf, int in, int out);
+__global__ void bigref_k_pcg_cols_v(BigDev d, BigRef rf, int in, int out);
+__global__ void bigref_k_pcg_upd(BigDev d, BigRef rf, int in, int out);
+__global__ void bigref_k_post(BigDev d, BigRef rf, int in, int out);
+__global__ void bigref_k_fix1(BigDev d, BigRef rf);
+__global__ void bigref_k_fix2(BigDev d, BigRef rf, int in, int out);
+__global__ void bigref_k_fix3_v(BigDev d, BigRef rf, int in, int out, long n_live_new, double c1_new);

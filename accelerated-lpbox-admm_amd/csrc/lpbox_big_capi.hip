@@ -95,11 +95,13 @@ struct lpbox_big {
     DevBuf<double> d_vcsc, d_vcsr, r4v, stage;
     DevBuf<int> d_rank, d_frank, d_cnt;
 
-    BigRef rf() const {
-        BigRef r;
+    BigRef rfd;
+    const BigRef *rf() {                  // what the big_launch_* helpers take: nullptr in the default order
+        if (!ref) return nullptr;
+        BigRef &r = rfd;
         r.valued = valued ? 1 : 0; r.vcsr = d_vcsr.p; r.vcsc = d_vcsc.p; r.r4v = r4v.p; r.stage = stage.p;
         r.rank = d_rank.p; r.frank = d_frank.p; r.cnt = d_cnt.p;
-        return r;
+        return &r;
     }
 
     BigDev dev() const {
@@ -190,14 +192,13 @@ int gather_partials(lpbox_big *h, const BigDev &d, int phase, int nv) {
     h->collectives++;
     return LPBOX_OK;
 }
-// reference order: the walker in the place of the reduction launch (no folding, one rank); the launches of the chain go to their
-// reference-order counterparts (KL)
-#define KL(name, ...) (h->ref ? bigref_launch_##name(d, h->rf(), ##__VA_ARGS__) : big_launch_##name(d, ##__VA_ARGS__))
-#define WALK(nv, phase, which, sidx) do { HIPCHK(bigref_launch_walk(d, h->rf(), nv, phase, which, sidx, h->stream)); h->launches++; } while (0)
+// reference order: the walker in the place of the reduction launch (no folding, one rank); every other launch of the chain is the same
+// big_launch_* call in both orders, with h->rf()
+#define WALK(nv, phase, which, sidx) do { HIPCHK(bigref_launch_walk(d, *h->rf(), nv, phase, which, sidx, h->stream)); h->launches++; } while (0)
 #define FIN(nv, phase) do { if (h->ref) WALK(nv, phase, 0, h->parity); else if (h->fold) { if (h->gpart.p) CHK(gather_partials(h, d, phase, nv)); } \
                             else { HIPCHK(big_launch_fin(d, nv, phase, h->stream)); h->launches++; CHK(allreduce(h, d.red + (phase) * BIG_NPART, nv)); } } while (0)
 #define FINX(nv) do { HIPCHK(big_launch_fin(d, nv, BIG_PH_X, h->stream)); h->launches++; CHK(allreduce(h, d.red + BIG_PH_X * BIG_NPART, nv)); } while (0)
-#define ROWS(mode) do { HIPCHK(KL(rows, mode, &h->parity, h->stream)); h->launches++; CHK(allreduce(h, d.q, h->l)); } while (0)
+#define ROWS(mode) do { HIPCHK(big_launch_rows(d, h->rf(), mode, &h->parity, h->stream)); h->launches++; CHK(allreduce(h, d.q, h->l)); } while (0)
 
 // comm-lean PCG, W > 1: the q exchange of allreduce() with the scalars riding along -- the row blocks go to their owners (one grouped
 // send/recv), the owner adds its block in rank order and squares it (big_k_rank_sum_qq: q.q partials behind the p.p partials the row
@@ -237,7 +238,7 @@ int exchange_q_lean(lpbox_big *h, const BigDev &d) {
 int enqueue_pcg(lpbox_big *h, const BigDev &d, int pairs) {
     if (h->lean) {
         for (int k = 0; k < pairs; k++) {
-            HIPCHK(big_launch_rows(d, 1, &h->parity, h->stream)); h->launches++;
+            HIPCHK(big_launch_rows(d, h->rf(), 1, &h->parity, h->stream)); h->launches++;
             if (h->world > 1 || h->comm) CHK(exchange_q_lean(h, d));
             HIPCHK(big_launch_pcg_lean(d, &h->parity, h->stream)); h->launches++;
             FIN(2, BIG_PH_D);
@@ -246,16 +247,16 @@ int enqueue_pcg(lpbox_big *h, const BigDev &d, int pairs) {
     }
     for (int k = 0; k < pairs; k++) {
         ROWS(1);
-        HIPCHK(KL(pcg_cols, &h->parity, h->stream)); h->launches++;
+        HIPCHK(big_launch_pcg_cols(d, h->rf(), &h->parity, h->stream)); h->launches++;
         FIN(1, BIG_PH_C);
-        HIPCHK(KL(pcg_upd, &h->parity, h->stream)); h->launches++;
+        HIPCHK(big_launch_pcg_upd(d, h->rf(), &h->parity, h->stream)); h->launches++;
         FIN(2, BIG_PH_D);
     }
     return LPBOX_OK;
 }
 
 int enqueue_tail(lpbox_big *h, const BigDev &d) {
-    HIPCHK(KL(post, &h->parity, h->stream)); h->launches++;
+    HIPCHK(big_launch_post(d, h->rf(), &h->parity, h->stream)); h->launches++;
     FIN(5, BIG_PH_E);
     ROWS(0);
     HIPCHK(big_launch_z4(d, 0, &h->parity, h->stream)); h->launches++;
@@ -263,12 +264,12 @@ int enqueue_tail(lpbox_big *h, const BigDev &d) {
 }
 
 int enqueue_iteration(lpbox_big *h, const BigDev &d) {
-    HIPCHK(KL(prep, 1, &h->parity, h->stream)); h->launches++;
+    HIPCHK(big_launch_prep(d, h->rf(), 1, &h->parity, h->stream)); h->launches++;
     FIN(1, BIG_PH_A);
-    HIPCHK(KL(y, &h->parity, h->stream)); h->launches++;
-    HIPCHK(KL(rhs_cols, &h->parity, h->stream)); h->launches++;
+    HIPCHK(big_launch_y(d, h->rf(), &h->parity, h->stream)); h->launches++;
+    HIPCHK(big_launch_rhs_cols(d, h->rf(), &h->parity, h->stream)); h->launches++;
     ROWS(0);
-    HIPCHK(KL(resid, &h->parity, h->stream)); h->launches++;
+    HIPCHK(big_launch_resid(d, h->rf(), &h->parity, h->stream)); h->launches++;
     FIN(3, BIG_PH_B);
     CHK(enqueue_pcg(h, d, h->chain.kmax));
     return enqueue_tail(h, d);
@@ -293,7 +294,7 @@ struct BigChainOps {
     }
     int batch_head() { HIPCHK(big_launch_resume(d, 1, &h->parity, h->stream)); return LPBOX_OK; }
     int enqueue(int n) { for (int it = 0; it < n; it++) CHK(enqueue_iteration(h, d)); return LPBOX_OK; }
-    int finalize() { HIPCHK(KL(prep, 0, &h->parity, h->stream)); h->launches++; return LPBOX_OK; }
+    int finalize() { HIPCHK(big_launch_prep(d, h->rf(), 0, &h->parity, h->stream)); h->launches++; return LPBOX_OK; }
 };
 
 }  // namespace
@@ -571,14 +572,11 @@ int lpbox_big_init(lpbox_big_t *h) {
     h->n_live_glob = h->n_glob; h->xi_valid = false;
     const BigDev d = h->dev();
     h->parity = 0;
+    HIPCHK(big_launch_init(d, h->rf(), h->ref ? ref_c1(h->n_glob) : std::pow((double)h->n_glob, 1.0 / 2), h->stream));   // pow(n, 1/p), p = 2 (LPcpp:427,503), n = ALL variables
     if (h->ref) {
-        HIPCHK(bigref_launch_init(d, h->rf(), ref_c1(h->n_glob), h->stream));
-        HIPCHK(bigref_launch_rank(d, h->rf(), 0, h->stream));                       // every variable is live: rank = index
-        HIPCHK(bigref_launch_walk(d, h->rf(), 1, BIG_PH_X, 0, -1, h->stream));      // b.x0 (:727)
-    } else {
-    HIPCHK(big_launch_init(d, std::pow((double)h->n_glob, 1.0 / 2), h->stream));   // pow(n, 1/p), p = 2 (LPcpp:427,503), n = ALL variables
-    CHK(allreduce(h, d.red + BIG_PH_X * BIG_NPART, 1));
-    }
+        HIPCHK(bigref_launch_rank(d, *h->rf(), 0, h->stream));                      // every variable is live: rank = index
+        HIPCHK(bigref_launch_walk(d, *h->rf(), 1, BIG_PH_X, 0, -1, h->stream));     // b.x0 (:727)
+    } else CHK(allreduce(h, d.red + BIG_PH_X * BIG_NPART, 1));
     HIPCHK(big_launch_init2(d, h->stream));
     ROWS(0);                                                                        // E * x0 for the first y3 (:720)
     HIPCHK(big_launch_z4(d, 1, &h->parity, h->stream));
@@ -664,22 +662,14 @@ int lpbox_big_iterate_l2f(lpbox_big_t *h, int iter_start, int iter_end, const do
     if (num_global != 0) {
         const long n_live_new = h->n_live_glob - num_global;
         HIPCHK(hipMemcpyAsync(h->newfix.p, nf.data(), nf.size(), hipMemcpyHostToDevice, h->stream));
-        if (h->ref) {
-            HIPCHK(bigref_launch_rank(d, h->rf(), 1, h->stream)); h->launches++;    // rank among the newly fixed
-            HIPCHK(bigref_launch_fix1(d, h->rf(), h->stream)); h->launches++;
-            WALK(1, BIG_PH_X, 1, -1);                                               // fix_obj = b2.x2, redux over the newly fixed
-            ROWS(0);                                                                // q = E2 * x2
-            HIPCHK(bigref_launch_rank(d, h->rf(), 2, h->stream)); h->launches++;    // the live ranks after this fix
-            HIPCHK(bigref_launch_fix2(d, h->rf(), &h->parity, h->stream)); h->launches++;
-            WALK(1, BIG_PH_X, 0, -1);                                               // |x_live|^2
-        } else {
-        HIPCHK(big_launch_fix1(d, h->stream)); h->launches++;
-        FINX(1);                                                                    // fix_obj = b2.x2
+        if (h->ref) { HIPCHK(bigref_launch_rank(d, *h->rf(), 1, h->stream)); h->launches++; }    // rank among the newly fixed
+        HIPCHK(big_launch_fix1(d, h->rf(), h->stream)); h->launches++;
+        if (h->ref) WALK(1, BIG_PH_X, 1, -1); else FINX(1);                         // fix_obj = b2.x2 (reference order: redux over the newly fixed)
         ROWS(0);                                                                    // q = E2 * x2
-        HIPCHK(big_launch_fix2(d, &h->parity, h->stream)); h->launches++;
-        FINX(1);                                                                    // |x_live|^2
-        }
-        HIPCHK(KL(fix3, n_live_new, h->ref ? ref_c1(n_live_new) : std::pow((double)n_live_new, 1.0 / 2), &h->parity, h->stream)); h->launches++;
+        if (h->ref) { HIPCHK(bigref_launch_rank(d, *h->rf(), 2, h->stream)); h->launches++; }    // the live ranks after this fix
+        HIPCHK(big_launch_fix2(d, h->rf(), &h->parity, h->stream)); h->launches++;
+        if (h->ref) WALK(1, BIG_PH_X, 0, -1); else FINX(1);                         // |x_live|^2
+        HIPCHK(big_launch_fix3(d, h->rf(), n_live_new, h->ref ? ref_c1(n_live_new) : std::pow((double)n_live_new, 1.0 / 2), &h->parity, h->stream)); h->launches++;
         if (n_live_new != 0) {
             ROWS(0);                                                                // E * x (live columns) for the first y3
             HIPCHK(big_launch_z4(d, 1, &h->parity, h->stream)); h->launches++;

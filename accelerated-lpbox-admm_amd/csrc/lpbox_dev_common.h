@@ -38,6 +38,18 @@ struct RowSwap {            // r0 = rows [a0, b0, a2, b2], r1 = rows [a1, b1, a3
 template <typename SWAP>
 __device__ __forceinline__ double pair_step(double a, double b) { double r0, r1; SWAP::run(a, b, r0, r1); return r0 + r1; }
 
+// A wide step whose result is read in the lower half / the even rows only: the partner operand of the swap is a register with no defined
+// content (an empty asm output, so the compiler neither copies v to feed the swap (v, v) nor reasons about the value).  The lower half /
+// the even rows receive exactly what pair_step<SWAP>(a, a) gives them; the upper half / the odd rows hold garbage.
+__device__ __forceinline__ double undefined_f64() {
+    int lo, hi;                      // (volatile: every call defines registers of its own -- merged into one, the swaps would copy it)
+    asm volatile("" : "=v"(lo));
+    asm volatile("" : "=v"(hi));
+    return __hiloint2double(hi, lo);
+}
+template <typename SWAP>
+__device__ __forceinline__ double pair_step_low(double a) { double r0, r1; SWAP::run(a, undefined_f64(), r0, r1); return r0 + r1; }
+
 __device__ __forceinline__ double row_allreduce(double v) {      // inside each row of 16 lanes: pairs, quads, 8, 16
     v = v + dpp_mov<0xB1>(v);    // quad_perm [1,0,3,2]
     v = v + dpp_mov<0x4E>(v);    // quad_perm [2,3,0,1]
@@ -90,18 +102,35 @@ constexpr int RED_MAXW = 16;   // waves per workgroup
 constexpr int RED_STAGE_BCAST = 0;   // every lane reads all W partials (broadcast reads) and adds them in registers: the default
 constexpr int RED_STAGE_PAIRS = 1;   // W = 8: lane reads the pair (p[2j], p[2j+1]), j = lane & 3, with one ds_read_b128 per value
                                      // and adds it (the tree's "pairs" level); two quad_perm steps finish the tree
+constexpr int RED_STAGE_PAIRS_LOW = 2;   // RED_STAGE_PAIRS whose first stage runs the wide steps of 1, 2 and 3 values without register copies
 
 // First stage of RED_STAGE_PAIRS: the wave butterflies of block_sum, then ONE predicated store per butterfly -- the first lane
 // of every row of 16 lanes writes what its row holds (rows [v0, v2, v1, v3]; with fewer than four values a row that repeats a value
 // writes it to a slot nobody reads), instead of one exec-mask region per value.
-template <int NV>
+// LOW (RED_STAGE_PAIRS_LOW): only the first lane of row 0 (one value), of rows 0 and 2 (two values), of rows 0, 2, 1 (three) is read back,
+// so a wide step that would swap a value against itself -- both of one value, the row step of two, the half step of the third of
+// three -- swaps it against an undefined register instead (pair_step_low): no v_mov copies in front of the swap.  The stored lanes
+// receive the same sums in the same association; the other owner lanes write garbage to the slots nobody reads (values >= NV of the
+// same parity half, as before).  Six values keep the copies: the rows of their second butterfly share two slots.
+template <int NV, bool LOW = false>
 __device__ __forceinline__ void wave_partials_store(const double *v, double *buf, int lane, int w) {
     const int row = lane >> 4, k = ((row & 1) << 1) | (row >> 1);    // value index of this lane's row after wave_reduce_scatter<3 or 4>;
     const bool owner = (lane & 15) == 0;                              // after <2> rows 0, 1 hold value 0 and rows 2, 3 value 1: slots 0, 2, 1, 3
     double *at = buf + k * RED_MAXW + w;                         // loop-invariant up to the parity offset
     if constexpr (NV == 1) {
-        const double t0 = wave_allreduce_sum(v[0]);                   // every lane holds it: the slots of k = 1..3 get copies
+        double t0;
+        if constexpr (LOW) t0 = row_allreduce(pair_step_low<RowSwap>(pair_step_low<HalfSwap>(v[0])));   // row 0 holds it
+        else t0 = wave_allreduce_sum(v[0]);                           // every lane holds it: the slots of k = 1..3 get copies
         if (owner) *at = t0;
+    } else if constexpr (LOW && NV == 2) {
+        const double x = pair_step<HalfSwap>(v[0], v[1]);
+        const double sc = row_allreduce(pair_step_low<RowSwap>(x));   // rows 0 and 2 hold values 0 and 1: slots 0 and 1
+        if (owner) *at = sc;
+    } else if constexpr (LOW && NV == 3) {
+        const double x = pair_step<HalfSwap>(v[0], v[1]);
+        const double y = pair_step_low<HalfSwap>(v[2]);               // rows 0, 1 hold the halves of value 2
+        const double sc = row_allreduce(pair_step<RowSwap>(x, y));    // rows [v0, v2, v1, garbage]
+        if (owner) *at = sc;
     } else {
         constexpr int NS4 = NV > 4 ? 4 : NV;
         const double sc = wave_reduce_scatter<NS4>(v);
@@ -131,8 +160,8 @@ __device__ __forceinline__ void block_sum(double (&v)[NV], double *red, int &par
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     double *buf = red + parity * (RED_MAXV * RED_MAXW);
     if constexpr (STAGE != RED_STAGE_BCAST) {
-        static_assert(W == 8 && STAGE == RED_STAGE_PAIRS, "built for eight waves");
-        wave_partials_store<NV>(v, buf, lane, w);
+        static_assert(W == 8 && (STAGE == RED_STAGE_PAIRS || STAGE == RED_STAGE_PAIRS_LOW), "built for eight waves");
+        wave_partials_store<NV, STAGE == RED_STAGE_PAIRS_LOW>(v, buf, lane, w);
         __syncthreads();
         double2 t[NV];
 #pragma unroll

@@ -22,6 +22,7 @@
 // Built with -ffp-contract=off: the reference is compiled without FMA (plain g++ -O3 on x86-64).
 #include "lpbox_lp.h"
 #include "lpbox_dev_common.h"
+#include "lpbox_lp_stoptest.h"
 
 #include <float.h>
 
@@ -70,6 +71,28 @@ namespace {
 #else
 #define LPBOX_OUTER_FUSED 0
 #endif
+// Instruction-stream savings of the 512 x 1 kernel ("Lazy stop tests and a leaner PCG instruction stream"); each
+// goes with the fused outer iteration and can be switched off on its own for an A/B (make variant NAME=x EXTRA=-DLPBOX_LP_LAZYSTOP=0):
+//   LAZYSTOP   the quotients of the two stop tests are formed only when a cheap filter cannot decide the test (lpbox_lp_stoptest.h)
+//   DEADZERO   fixed variables carry r = p = dinv = +0.0 through the PCG instead of being masked at every use
+//   REDLOW     wide butterfly steps of block_sum without register copies (RED_STAGE_PAIRS_LOW)
+//   MPDIRECT   M p = dI p + t without the leading 0 +
+//   MEANPREFIX the first nine additions of the objective window's mean ahead of the residual reduction
+#ifndef LPBOX_LP_LAZYSTOP
+#define LPBOX_LP_LAZYSTOP 1
+#endif
+#ifndef LPBOX_LP_MEANPREFIX
+#define LPBOX_LP_MEANPREFIX 1
+#endif
+#ifndef LPBOX_LP_DEADZERO
+#define LPBOX_LP_DEADZERO 1
+#endif
+#ifndef LPBOX_LP_REDLOW
+#define LPBOX_LP_REDLOW 1
+#endif
+#ifndef LPBOX_LP_MPDIRECT
+#define LPBOX_LP_MPDIRECT 1
+#endif
 
 // ------------------------------------------------------------------------------------------------
 // LDS carve-up shared by the launcher (size) and the kernel (pointers)
@@ -108,6 +131,10 @@ __host__ __device__ constexpr bool lp_is_lean(int T, int EPT) { return EPT >= 4 
 // second stage of block_sum per geometry of lp_window_kernel (each measured on its own)
 __host__ __device__ constexpr int lp_red_stage(int T, int EPT) {
     return T == 512 && EPT == 1 ? RED_STAGE_PAIRS : RED_STAGE_BCAST;     // (512 x 4: 81.5 vs 77.4 us per iteration with PAIRS, it keeps the default)
+}
+// the leaner instruction stream, per step: the kernel with the fused outer iteration only
+__host__ __device__ constexpr bool lp_lean_stream(int T, int EPT, bool direct, bool log, int step_on) {
+    return LPBOX_OUTER_FUSED != 0 && step_on != 0 && T == 512 && EPT == 1 && !direct && !log;
 }
 
 // PCG loop of lp_window_kernel per geometry.  512 x 1 (not DIRECT, not LOG): the exit tests are made wave-uniform for the compiler (a
@@ -543,7 +570,10 @@ struct RowVec {
 template <int T, int EPT, typename RCAPS, typename CCAPS, typename HCAPS, bool DIRECT = false, bool LOG = false>
 __global__ void __launch_bounds__(T) lp_window_kernel(LpBatchDev bd, int iter_start, int iter_end, int mode) {
     const int l2f = mode & 1, rec = mode & 2;     // rec: keep x after every iteration in xhist (x_iters of the l2f loop; print_fix_info 2/3 of the plain loop)
-    constexpr int RS = (DIRECT || LOG) ? RED_STAGE_BCAST : lp_red_stage(T, EPT);    // second stage of every block_sum of this kernel
+    constexpr bool LAZY = lp_lean_stream(T, EPT, DIRECT, LOG, LPBOX_LP_LAZYSTOP), DEADZ = lp_lean_stream(T, EPT, DIRECT, LOG, LPBOX_LP_DEADZERO);
+    constexpr bool MPDIR = lp_lean_stream(T, EPT, DIRECT, LOG, LPBOX_LP_MPDIRECT), MEANPRE = lp_lean_stream(T, EPT, DIRECT, LOG, LPBOX_LP_MEANPREFIX);
+    constexpr int RS = (DIRECT || LOG) ? RED_STAGE_BCAST                            // second stage of every block_sum of this kernel
+                     : lp_lean_stream(T, EPT, DIRECT, LOG, LPBOX_LP_REDLOW) ? RED_STAGE_PAIRS_LOW : lp_red_stage(T, EPT);
     constexpr bool SCALAR_LOOP = lp_pcg_scalar_loop(T, EPT, DIRECT, LOG), SPEC = lp_pcg_spec_geometry(T, EPT, DIRECT, LOG);
     constexpr bool FUSED = lp_outer_fused(T, EPT, DIRECT, LOG);
     // A test on a value that came out of block_sum is the same in every lane, which the compiler cannot see: it builds the PCG loop as a
@@ -666,6 +696,12 @@ __global__ void __launch_bounds__(T) lp_window_kernel(LpBatchDev bd, int iter_st
     }
     const double learning_fact = LP_LEARNING_FACT;
     int ret = 0, stop = LP_STOP_NONE, parity = 0;
+    // Lazy stop tests (LAZY): while a filter of lpbox_lp_stoptest.h decides a test, cvg1 / cvg2 resp. std_obj are not formed; their
+    // operands (uniform values) stay here and the exact expressions run where the value is read -- the state write-back below.
+    // (std_obj is also read by the test of an iteration with hist_n < LP_HIST; hist_n never falls inside a launch and std_pending is
+    // set only at hist_n >= LP_HIST, so that read always sees the value the launch started with, as before.)
+    bool cvg_pending = false, std_pending = false;
+    double pend_a1 = 0.0, pend_a2 = 0.0, pend_c = 0.0, pend_devq = 0.0, pend_h9 = 0.0;
 
     __syncthreads();   // index sets staged
 
@@ -1114,6 +1150,8 @@ __global__ void __launch_bounds__(T) lp_window_kernel(LpBatchDev bd, int iter_st
                 const double t = tcol[s];
                 xt[s] = y1[s];
                 double Mx = 0.0;
+                if constexpr (MPDIR) Mx = dI * (1.0 * xt[s]);         // (see M p in the loop: t is never -0.0)
+                else
                 Mx += dI * (1.0 * xt[s]);
                 Mx += t;
                 r[s] = rhs[s] - Mx;                                   // :268
@@ -1122,6 +1160,17 @@ __global__ void __launch_bounds__(T) lp_window_kernel(LpBatchDev bd, int iter_st
                 p3[1] = p3[1] + (live[s] ? r[s] * r[s] : 0.0);        // residualNorm2 :282
                 p3[2] = p3[2] + (live[s] ? r[s] * p[s] : 0.0);        // absNew :294
             }
+            // DEADZ: a fixed variable carries r = p = +0.0 and a preconditioner entry of +0.0 through the PCG, so the loop needs no
+            // mask where a masked term was "live ? v : 0.0" in front of a sum that starts at +0.0.  For a fixed lane and finite alpha, beta,
+            // M p:  p stays +0.0, the value the masked store published (z = (+0.0) * r is +0.0 or -0.0; beta = absNew / absOld >= +0.0, both
+            // being sums from +0.0 of r^2 / pd with pd > 0, so beta * (+0.0) = +0.0, and (+-0.0) + (+0.0) = +0.0);  p * tmp = (+0.0) * tmp
+            // and r * z = r * (+-0.0) are +0.0 or -0.0, and acc + (+-0.0) = acc + (+0.0) for every acc that is not -0.0 -- the
+            // accumulators start at +0.0 and a sum from +0.0 never becomes -0.0 -- so the sums are what the mask gave.
+            // r * r keeps its mask: r = -(alpha * tmp) of a fixed lane is NOT zero (tmp holds the column sum of the live rows).
+            // A non-finite alpha or beta (a reduction that under- or overflowed) turns these zeros into NaN one step before the live
+            // lanes' own inf - inf does; from there every iterate is NaN on either path.
+            double dz[1] = {0.0};                                     // (DEADZ kernels have one slot)
+            if constexpr (DEADZ) { r[0] = live[0] ? r[0] : 0.0; p[0] = live[0] ? p[0] : 0.0; dz[0] = live[0] ? dinv[0] : 0.0; }
             block_sum<T, 3, RS>(p3, red, parity);
             STAMP(2)
             const double rhsNorm2 = p3[0];
@@ -1142,7 +1191,7 @@ __global__ void __launch_bounds__(T) lp_window_kernel(LpBatchDev bd, int iter_st
                         static_assert((RK >= 0) == (CK >= 0) && (RK >= 0) == (HK >= 0) && (RK < 0 || EPT == 1), "all three lists or none");
                         while (k_it < LP_PCG_MAXITERS) {                  // :296
 #pragma unroll
-                            for (int s = 0; s < EPT; s++) gx[s * T + tid] = live[s] ? p[s] : 0.0;
+                            for (int s = 0; s < EPT; s++) gx[s * T + tid] = (DEADZ || live[s]) ? p[s] : 0.0;
                             __syncthreads();
                             {
                                 double q[EPT];
@@ -1178,10 +1227,14 @@ __global__ void __launch_bounds__(T) lp_window_kernel(LpBatchDev bd, int iter_st
                             for (int s = 0; s < EPT; s++) {               // tmp = M p (:298), fused p.tmp
                                 const double t = tcol[s];
                                 double Mp = 0.0;
+                                // MPDIR: (0.0 + dI p) + t differs from dI p + t only where dI p and t are both -0.0, and t is a sum
+                                // that starts at +0.0 (list_sum, own + quad_sum): never -0.0
+                                if constexpr (MPDIR) Mp = dI * (1.0 * p[s]);
+                                else
                                 Mp += dI * (1.0 * p[s]);
                                 Mp += t;
                                 tmp[s] = Mp;
-                                p1[0] = p1[0] + (live[s] ? p[s] * tmp[s] : 0.0);
+                                p1[0] = p1[0] + ((DEADZ || live[s]) ? p[s] * tmp[s] : 0.0);
                             }
                             block_sum<T, 1, RS>(p1, red, parity);
                             const double alpha = absNew / p1[0];          // :300
@@ -1192,9 +1245,9 @@ __global__ void __launch_bounds__(T) lp_window_kernel(LpBatchDev bd, int iter_st
                             for (int s = 0; s < EPT; s++) {
                                 xt[s] += alpha * p[s];                    // :302
                                 r[s] -= alpha * tmp[s];                   // :304
-                                z[s] = dinv[s] * r[s];                    // :314
+                                z[s] = (DEADZ ? dz[0] : dinv[s]) * r[s];  // :314
                                 p2[0] = p2[0] + (live[s] ? r[s] * r[s] : 0.0);   // :305
-                                p2[1] = p2[1] + (live[s] ? r[s] * z[s] : 0.0);   // :317
+                                p2[1] = p2[1] + ((DEADZ || live[s]) ? r[s] * z[s] : 0.0);   // :317
                             }
                             block_sum<T, 2, RS>(p2, red, parity);
                             residualNorm2 = p2[0];
@@ -1403,18 +1456,36 @@ __global__ void __launch_bounds__(T) lp_window_kernel(LpBatchDev bd, int iter_st
                 p5[3] = p5[3] + (live[s] ? b.get(s) * x[s] : 0.0);
                 p5[4] = p5[4] + (live[s] ? b.get(s) * xb : 0.0);
             }
+            // MEANPRE: with a full window the first nine terms of the mean below are old history values; their (ordered) sum is formed
+            // here, ahead of the reduction, and one addition remains behind it
+            bool hist_full = false;
+            double mean_pre = 0.0;
+            if constexpr (MEANPRE) {
+                hist_full = hist_n >= LP_HIST;
+                if (hist_full) {
+#pragma unroll
+                    for (int k = 1; k < LP_HIST; k++) mean_pre += h_reg[LEAN ? 0 : k];
+                }
+            }
             STAMP_POST(12)
             block_sum<T, 6, RS>(p5, red, parity);
             if constexpr (LOG) block_sum<T, 6, RS>(lg, red, parity);
             pnorm = p5[5];
             STAMP_POST(13)
+            if constexpr (LAZY) {
+                // one of the two quotients is above the threshold for certain: the test fails whatever the other one is, and neither
+                // is formed (their operands stay pending); else the exact code below
+                cvg_pending = uni(lp_cvg_certainly_above(p5[1], p5[0], LP_STOP_THRESHOLD) || lp_cvg_certainly_above(p5[2], p5[0], LP_STOP_THRESHOLD));
+                pend_a1 = p5[1]; pend_a2 = p5[2]; pend_c = p5[0];
+            }
+            if (!cvg_pending)
             {
                 const double xn = sqrt(p5[0]);
                 const double temp0 = (xn < 2.2204e-16) ? 2.2204e-16 : xn;
                 cvg1 = sqrt(p5[1]) / temp0;
                 cvg2 = sqrt(p5[2]) / temp0;
             }
-            if (cvg1 <= LP_STOP_THRESHOLD && cvg2 <= LP_STOP_THRESHOLD && (l2f || it != iter_start)) {
+            if (!cvg_pending && cvg1 <= LP_STOP_THRESHOLD && cvg2 <= LP_STOP_THRESHOLD && (l2f || it != iter_start)) {
                 if (l2f) ret = 1;                                     // :1505 (plain loop: ret stays 0, :934-949)
                 stop = LP_STOP_Y1Y2;
                 break;
@@ -1461,17 +1532,32 @@ __global__ void __launch_bounds__(T) lp_window_kernel(LpBatchDev bd, int iter_st
             if (hist_n < 0x3fffffff) hist_n++;
             if (hist_n >= LP_HIST) {                                  // compute_std_obj :459-469, std_dev :358-377
                 double mean = 0;
+                if constexpr (MEANPRE) {
+                    if (hist_full) mean = mean_pre + h[LP_HIST - 1];  // h[0..8] are the old h[1..9]
+                    else {
+#pragma unroll
+                        for (int k = 0; k < LP_HIST; k++) mean += h[k];
+                    }
+                } else {
 #pragma unroll
                 for (int k = 0; k < LP_HIST; k++) mean += h[k];
+                }
                 mean /= (double)LP_HIST;
                 double dev = 0;
 #pragma unroll
                 for (int k = 0; k < LP_HIST; k++) dev += (h[k] - mean) * (h[k] - mean);
                 dev /= (double)(LP_HIST - 1);
+                if constexpr (LAZY) {                                 // std_obj is above its threshold for certain: not formed, operands pending
+                    std_pending = uni(lp_std_certainly_above(dev, h[LP_HIST - 1], LP_STD_THRESHOLD));
+                    pend_devq = dev; pend_h9 = h[LP_HIST - 1];
+                }
+                if (!std_pending)
+                {
                 const double sd = (dev == 0) ? 0.0 : sqrt(dev);
                 std_obj = sd / fabs(h[LP_HIST - 1]);
+                }
             }
-            if (std_obj <= LP_STD_THRESHOLD) { ret = 1; stop = LP_STOP_OBJSTD; break; }   // :977
+            if (!std_pending && std_obj <= LP_STD_THRESHOLD) { ret = 1; stop = LP_STOP_OBJSTD; break; }   // :977
             cur_obj = p5[4];                                          // :1001-1003
             if (best_bin_obj >= cur_obj) best_bin_obj = cur_obj;
             if constexpr (LOG) {                                      // the reference logs the iterations that did not break (:1013-1067)
@@ -1496,6 +1582,10 @@ __global__ void __launch_bounds__(T) lp_window_kernel(LpBatchDev bd, int iter_st
     }
 
     // ---- write the state back ----
+    if constexpr (LAZY) {                                             // every exit of the loop passes here: the skipped values, from their operands
+        if (cvg_pending) { cvg1 = lp_cvg_exact(pend_a1, pend_c); cvg2 = lp_cvg_exact(pend_a2, pend_c); }
+        if (std_pending) std_obj = lp_std_exact(pend_devq, pend_h9);
+    }
     z1.store(); z2.store(); pd.store();
 #pragma unroll
     for (int s = 0; s < EPT; s++) {
@@ -1568,7 +1658,7 @@ hipError_t lp_launch_debug_block_sum(int T, int NV, int stage, int groups, int r
     }
 #define CALL_DBG_NV(TT, SS) CALL_DBG(TT, 1, SS) CALL_DBG(TT, 2, SS) CALL_DBG(TT, 3, SS) CALL_DBG(TT, 6, SS)
     CALL_DBG_NV(256, RED_STAGE_BCAST) CALL_DBG_NV(512, RED_STAGE_BCAST) CALL_DBG_NV(1024, RED_STAGE_BCAST)
-    CALL_DBG_NV(512, RED_STAGE_PAIRS)
+    CALL_DBG_NV(512, RED_STAGE_PAIRS) CALL_DBG_NV(512, RED_STAGE_PAIRS_LOW)
 #undef CALL_DBG_NV
 #undef CALL_DBG
     return hipErrorInvalidConfiguration;

@@ -118,6 +118,28 @@ hipError_t bigb_enqueue_tail(const BigDev *devs, const BigBatchGrid &g, int *par
 hipError_t bigb_enqueue_iterations(const BigDev *devs, const BigBatchGrid &g, int iters, int kmax, int *parity, hipStream_t s);   // 8 + 3 kmax launches each
 hipError_t bigb_collect_states(const BigDev *devs, const BigBatchGrid &g, int parity, BigState *out, hipStream_t s);   // out[i] = st[parity] of problem i
 
+// ---- early-fixing windows (lpbox_big_iterate_l2f) of a batch: lpbox_big_batch_iterate_l2f / _l2f_scores / _get_x_iters_device ----
+// One record per ACTIVE member and window, in the order of devs, uploaded in one copy.  c1_new = pow(n_live_new, 1/2) comes from the
+// host's libm as in the one-problem call: a device sqrt is not the same number now and then.
+#define BIG_CT 1024        // threads of the live-list compaction ...
+#define BIG_CE 4           // ... and entries per thread: chunks of BIG_CT * BIG_CE entries
+struct BigFixPar {
+    int apply;             // the member fixes in this window (0: it falls through the prologue)
+    int clear;             // apply == 0, but fix codes sit in newfix (the guard held the fix back): the compaction launch clears them
+    int rows, row0;        // entries of live_idx before this window's fix; first row in the packed buffer / the code staging
+    long n_live_new;
+    double c1_new;
+    int *live_idx;         // the member's live-index list on the device (ascending original indices)
+};
+hipError_t bigb_launch_set_window_l2f(const BigDev *devs, const BigBatchGrid &g, int iter_start, int iter_end, int *parity, hipStream_t s);
+// fix1, fin, rows(gsrc), fix2, fin, fix3, rows(gsrc), z4(init_only): 8 launches, 5 of them move the parity
+hipError_t bigb_enqueue_fix(const BigDev *devs, const BigFixPar *par, const BigBatchGrid &g, int *parity, hipStream_t s);
+hipError_t bigb_launch_clear_xhist(const BigDev *devs, const BigBatchGrid &g, long max_total, hipStream_t s);      // x_iters = Zero, all ws_cap columns
+hipError_t bigb_launch_decide(const BigDev *devs, const BigFixPar *par, const BigBatchGrid &g, int max_rows, const float *scores, const uint8_t *codes,
+                              double hi, double lo, int *counts, hipStream_t s);       // newfix codes from scores or host codes; counts[2 * member + {ones, zeros}]
+hipError_t bigb_launch_compact(const BigDev *devs, const BigFixPar *par, const BigBatchGrid &g, hipStream_t s);     // live lists in place, codes cleared
+hipError_t bigb_launch_pack(const BigDev *devs, const BigFixPar *par, const BigBatchGrid &g, int max_rows, int ws, double *out, hipStream_t s);
+
 // ---- reference-order mode of this path (lpbox_big_set_order(LPBOX_ORDER_REFERENCE), one rank; lpbox_big_ref_kernels.hip) ----
 // Every reduction over the live variables follows Eigen's redux (oracle/lpbox_oracle.c redux_sum_eigen): the producers write their
 // per-variable terms into `stage` at the variable's LIVE RANK instead of summing them per workgroup, a walker kernel adds them up in

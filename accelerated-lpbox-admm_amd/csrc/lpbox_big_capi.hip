@@ -86,6 +86,10 @@ struct lpbox_big {
     long n_live_glob = 0;                 // live variables over all ranks
     int ws_cap = 0, xi_rows = 0;
     bool xi_valid = false;
+    // a batch's device-decided fix (lpbox_big_batch_iterate_l2f_scores) compacts d_live_idx on the device: left_idx then follows on demand
+    // (refresh_left).  dlive_valid: d_live_idx holds the current live list.  win_serial counts the windows (a batch's pack refers to one).
+    bool left_stale = false, dlive_valid = false;
+    long win_serial = 0;
     bool record = false, xi_plain = false;   // lpbox_big_set_record: the plain loop stages every iterate; the last staged window came from it
     DevBuf<BigState> st;
     BigState hst;
@@ -153,6 +157,16 @@ int allreduce(lpbox_big *h, double *ptr, long count) {
     }
     HIPCHK(big_launch_rank_sum(h->gath.p, W, count, count, ptr, h->stream));
     h->collectives++;
+    return LPBOX_OK;
+}
+
+// the host's live list after a fix that was decided on the device: one copy of the device's list, where the host list is read
+int refresh_left(lpbox_big *h) {
+    if (!h->left_stale) return LPBOX_OK;
+    CHK(use_device(h->device));
+    h->left_idx.resize((size_t)h->n_live_glob);
+    if (h->n_live_glob) HIPCHK(hipMemcpy(h->left_idx.data(), h->d_live_idx.p, sizeof(int) * (size_t)h->n_live_glob, hipMemcpyDeviceToHost));
+    h->left_stale = false;
     return LPBOX_OK;
 }
 
@@ -570,6 +584,7 @@ int lpbox_big_init(lpbox_big_t *h) {
     h->left_idx.resize(h->n_loc);
     for (int j = 0; j < h->n_loc; j++) h->left_idx[j] = j;
     h->n_live_glob = h->n_glob; h->xi_valid = false;
+    h->left_stale = false; h->dlive_valid = false; h->win_serial++;
     const BigDev d = h->dev();
     h->parity = 0;
     HIPCHK(big_launch_init(d, h->rf(), h->ref ? ref_c1(h->n_glob) : std::pow((double)h->n_glob, 1.0 / 2), h->stream));   // pow(n, 1/p), p = 2 (LPcpp:427,503), n = ALL variables
@@ -600,7 +615,9 @@ int lpbox_big_iterate(lpbox_big_t *h, int iter_start, int iter_end, int *ret) { 
     CHK(use_device(h->device));
     const int ws = iter_end - iter_start;
     const bool rec = h->record && ws > 0;
+    h->win_serial++;
     if (rec) {
+        CHK(refresh_left(h));
         if ((double)ws * h->n_loc * sizeof(double) > 4294967296.0)
             return lpbox_fail(LPBOX_E_UNSUPPORTED, "recording %d iterations of %d variables needs more than 4 GiB", ws, h->n_loc);
         if (h->ws_cap < ws || !h->xhist.p) {
@@ -612,6 +629,7 @@ int lpbox_big_iterate(lpbox_big_t *h, int iter_start, int iter_end, int *ret) { 
         HIPCHK(hipMemsetAsync(h->xhist.p, 0, sizeof(double) * (size_t)h->ws_cap * h->n_loc, h->stream));
         h->xi_left = h->left_idx; h->xi_rows = (int)h->left_idx.size();
         if (h->xi_rows) HIPCHK(hipMemcpyAsync(h->d_live_idx.p, h->xi_left.data(), sizeof(int) * (size_t)h->xi_rows, hipMemcpyHostToDevice, h->stream));
+        h->dlive_valid = true;
     }
     const BigDev d = h->dev();
     HIPCHK(big_launch_set_window(d, iter_start, iter_end, rec ? 2 : 0, &h->parity, h->stream));
@@ -630,6 +648,7 @@ int lpbox_big_iterate_l2f(lpbox_big_t *h, int iter_start, int iter_end, const do
     if (ws > LP_XITERS_COLS) return lpbox_fail(LPBOX_E_BADARG, "window of %d iterations exceeds the %d columns of x_iters (LPcpp:1113)", ws, LP_XITERS_COLS);
     if (num_global < 0 || num_global > h->n_live_glob) return lpbox_fail(LPBOX_E_BADARG, "fix count %ld outside [0,%ld]", num_global, h->n_live_glob);
     CHK(use_device(h->device));
+    CHK(refresh_left(h));
     const int n_live_loc = (int)h->left_idx.size();
     std::vector<uint8_t> nf;
     std::vector<int> keep;
@@ -681,13 +700,14 @@ int lpbox_big_iterate_l2f(lpbox_big_t *h, int iter_start, int iter_end, const do
     if (h->ws_cap > 0) HIPCHK(hipMemsetAsync(h->xhist.p, 0, sizeof(double) * (size_t)h->ws_cap * h->n_loc, h->stream));   // x_iters = Zero (:1113): ALL staged columns, also those of an earlier, longer window
     if (h->xi_rows) HIPCHK(hipMemcpyAsync(h->d_live_idx.p, h->xi_left.data(), sizeof(int) * (size_t)h->xi_rows, hipMemcpyHostToDevice, h->stream));
     CHK(run_window(h, d, iter_end));        // synchronises: nf / xi_left stay alive until here
-    h->xi_valid = true; h->xi_plain = false;
+    h->xi_valid = true; h->xi_plain = false; h->dlive_valid = true; h->win_serial++;
     if (ret) *ret = h->hst.ret;
     return LPBOX_OK;
 }
 
 int lpbox_big_get_n(lpbox_big_t *h) {                                               // live variables of this rank
     if (!h || !h->inited) return lpbox_fail(LPBOX_E_STATE, "not initialised");
+    CHK(refresh_left(h));
     return (int)h->left_idx.size();
 }
 
@@ -839,13 +859,23 @@ struct lpbox_big_batch {
     std::vector<BigDev> h_devs;                     // host side of devs (alive until the stream has taken it)
     std::vector<BigState> h_states;
     double kernel_ms = 0.0; long long launches = 0, collectives = 0, parity_copies = 0;
+    // early-fixing windows
+    std::vector<uint8_t> active;                    // lpbox_big_batch_set_active; governs the l2f calls and the pack only
+    int graph_B = 0;                                // members in the captured launches' grid
+    DevBuf<BigFixPar> par; std::vector<BigFixPar> h_par;
+    DevBuf<int> counts; DevBuf<uint8_t> codes; DevBuf<double> pack;
+    uint8_t *h_codes = nullptr; size_t h_codes_cap = 0;     // pinned staging of the host-vector form: one code per live row of every fixing member
+    // the most recent pack: rows of member i = [row_off[i], row_off[i+1]), taken after window pack_serial[i] of that member (-1: not packed)
+    std::vector<long> row_off, pack_serial;
+    bool pack_valid = false;
+    long long fix_launches = 0, packs = 0;
 };
 
 namespace {
 
 // what a member must be for the lockstep chain; `i` names it in the message.  Checked at create, init and iterate: a handle can be
 // changed between the calls (recording switched on, an early-fixing window of its own).
-int bigb_member_ok(const lpbox_big *h, int i) {
+int bigb_member_ok(const lpbox_big *h, int i, bool allow_fixed = false) {      // allow_fixed: the early-fixing calls
     if (!h || !h->has_problem) return lpbox_fail(LPBOX_E_STATE, "problem %d of the batch has no problem", i);
     if (h->ref) return lpbox_fail(LPBOX_E_UNSUPPORTED, "problem %d of the batch runs in the reference summation order; the batch runs the default order", i);
     if (h->world != 1) return lpbox_fail(LPBOX_E_UNSUPPORTED, "problem %d of the batch is sharded over %d ranks; the batch runs one rank per problem", i, h->world);
@@ -854,35 +884,39 @@ int bigb_member_ok(const lpbox_big *h, int i) {
     if (h->record) return lpbox_fail(LPBOX_E_UNSUPPORTED, "problem %d of the batch is recording; recording is per handle (lpbox_big_iterate)", i);
     if (h->uploaded && !h->fold)
         return lpbox_fail(LPBOX_E_UNSUPPORTED, "problem %d of the batch runs without folded reductions (LPBOX_BIG_NOFOLD, or more than %d workgroups)", i, BIG_FOLD_U * BIG_T);
-    if (h->inited && h->n_live_glob != h->n_glob)
+    if (!allow_fixed && h->inited && h->n_live_glob != h->n_glob)
         return lpbox_fail(LPBOX_E_UNSUPPORTED, "problem %d of the batch has fixed variables; early-fixing windows are per handle (lpbox_big_iterate_l2f)", i);
     return LPBOX_OK;
 }
 
-int bigb_collect(lpbox_big_batch *b, int parity) {
-    HIPCHK(bigb_collect_states(b->devs.p, b->grid, parity, b->dstates.p, b->stream));
-    HIPCHK(hipMemcpyAsync(b->h_states.data(), b->dstates.p, sizeof(BigState) * (size_t)b->B, hipMemcpyDeviceToHost, b->stream));
+int bigb_collect(lpbox_big_batch *b, const BigBatchGrid &g, int parity) {
+    HIPCHK(bigb_collect_states(b->devs.p, g, parity, b->dstates.p, b->stream));
+    HIPCHK(hipMemcpyAsync(b->h_states.data(), b->dstates.p, sizeof(BigState) * (size_t)g.B, hipMemcpyDeviceToHost, b->stream));
     HIPCHK(hipStreamSynchronize(b->stream));
     return LPBOX_OK;
 }
 
 // The lockstep chain up to iter_end (the window already set); the loop of batch_run_chain in lpbox_seg_capi.hip with this route's
-// launches.  b->h_states receives the final states; resumes[i] is raised for every member whose own state showed the halt at a resume.
-int bigb_run_chain(lpbox_big_batch *b, int iter_end, int *parity, long long *resumes) {
+// launches.  The chain runs the A members whose descriptors stand in b->devs (act[k]: the member behind descriptor k; nullptr: all, in
+// order); the grid extents stay the maxima over all members.  b->h_states[k] receives the final states; resumes[k] is raised for every
+// member whose own state showed the halt at a resume.
+int bigb_run_chain(lpbox_big_batch *b, int A, const int *act, int iter_end, int *parity, long long *resumes) {
     const ChainRules &rules = b->rules;
     const BigDev *devs = b->devs.p;
-    const BigBatchGrid &g = b->grid;
+    BigBatchGrid g = b->grid;
+    g.B = A;
+    if (b->graph_B != A) { b->graphs.clear(); b->graph_B = A; }     // the captured launches carry the member count
     hipStream_t st = b->stream;
-    std::vector<int> resumed(b->B, 0);                              // per member: resumes since one of its outer iterations last completed
+    std::vector<int> resumed(A, 0);                                 // per member: resumes since one of its outer iterations last completed
     for (;;) {
-        CHK(bigb_collect(b, *parity));
+        CHK(bigb_collect(b, g, *parity));
         bool more = false, any_run = false;
         int remaining = 0, vote = 0, pcg_k = 0;
-        for (int i = 0; i < b->B; i++) {
+        for (int i = 0; i < A; i++) {
             const BigState &h = b->h_states[i];
             if (h.halt == BIG_HALT_PCG_MORE) {
                 if (++resumed[i] > rules.resume_limit())
-                    return lpbox_fail(LPBOX_E_STATE, "problem %d of the batch, iteration %d: the PCG is still halted at k = %d after %d resumes in a row", i, h.iter, h.pcg_k, resumed[i] - 1);
+                    return lpbox_fail(LPBOX_E_STATE, "problem %d of the batch, iteration %d: the PCG is still halted at k = %d after %d resumes in a row", act ? act[i] : i, h.iter, h.pcg_k, resumed[i] - 1);
                 resumes[i]++; more = true; pcg_k = std::max(pcg_k, h.pcg_k);
                 continue;
             }
@@ -929,6 +963,193 @@ int bigb_run_chain(lpbox_big_batch *b, int iter_end, int *parity, long long *res
     return LPBOX_OK;
 }
 
+std::vector<int> bigb_active(const lpbox_big_batch *b) {
+    std::vector<int> act;
+    for (int i = 0; i < b->B; i++) if (b->active[i]) act.push_back(i);
+    return act;
+}
+
+// descriptors (b->h_devs) and records (b->h_par) of the first A slots -> device, one copy each
+int bigb_upload_devs(lpbox_big_batch *b, int A) {
+    HIPCHK(hipMemcpyAsync(b->devs.p, b->h_devs.data(), sizeof(BigDev) * (size_t)A, hipMemcpyHostToDevice, b->stream));
+    return LPBOX_OK;
+}
+int bigb_upload_par(lpbox_big_batch *b, int A) {
+    HIPCHK(hipMemcpyAsync(b->par.p, b->h_par.data(), sizeof(BigFixPar) * (size_t)A, hipMemcpyHostToDevice, b->stream));
+    return LPBOX_OK;
+}
+
+// One early-fixing window (ADMM_lp_iters_l2f, LPcpp:1098-1574) of all active members.  Host-vector form: vecs /
+// nums, the caller has decided; score form: scores (device, float32, one per packed row of the last pack) or NULL, the rule runs on the
+// device.  Everything is validated before anything changes.
+int bigb_window(lpbox_big_batch *b, int iter_start, int iter_end, bool score_form, const double *vecs, long vec_stride, const long *nums,
+                const float *scores, double hi, double lo, int min_fix, int *rets, int *fixed) {
+    const int ws = iter_end - iter_start;
+    if (ws > LP_XITERS_COLS) return lpbox_fail(LPBOX_E_BADARG, "window of %d iterations exceeds the %d columns of x_iters (LPcpp:1113)", ws, LP_XITERS_COLS);
+    const std::vector<int> act = bigb_active(b);
+    const int A = (int)act.size();
+    std::vector<long> live(A), num(A, 0);
+    for (int k = 0; k < A; k++) { const lpbox_big *h = b->hs[act[k]]; live[k] = h && h->inited ? h->n_live_glob : (h ? h->n_glob : 0); }
+    if (!score_form)
+        for (int k = 0; k < A; k++) {
+            const int i = act[k];
+            num[k] = nums ? nums[i] : 0;
+            if (num[k] < 0 || num[k] > live[k]) return lpbox_fail(LPBOX_E_BADARG, "problem %d of the batch: fix count %ld outside [0,%ld]", i, num[k], live[k]);
+            if (num[k] == 0) continue;
+            if (!vecs) return lpbox_fail(LPBOX_E_BADARG, "problem %d of the batch: fix vector missing", i);
+            if (vec_stride < live[k]) return lpbox_fail(LPBOX_E_BADARG, "problem %d of the batch: fix vector holds %ld entries, %ld live variables", i, vec_stride, live[k]);
+            const double *vec = vecs + (size_t)i * vec_stride;
+            long cnt = 0;
+            for (long q = 0; q < live[k]; q++) if (vec[q] == 1 || vec[q] == 0) cnt++;
+            if (cnt != num[k]) return lpbox_fail(LPBOX_E_BADARG, "problem %d of the batch: vec fixes %ld variables but num = %ld", i, cnt, num[k]);
+        }
+    if (!b->inited) return lpbox_fail(LPBOX_E_STATE, "lpbox_big_batch_init has not been called");
+    for (int k = 0; k < A; k++) {
+        CHK(bigb_member_ok(b->hs[act[k]], act[k], true));
+        if (!b->hs[act[k]]->inited) return lpbox_fail(LPBOX_E_STATE, "problem %d of the batch: solve_init has not been called", act[k]);
+    }
+    if (score_form && scores) {
+        if (!b->pack_valid) return lpbox_fail(LPBOX_E_STATE, "scores given, but lpbox_big_batch_get_x_iters_device has not been called since the last window");
+        for (int k = 0; k < A; k++) {
+            const int i = act[k];
+            if (b->pack_serial[i] < 0 || b->pack_serial[i] != b->hs[i]->win_serial || b->row_off[i + 1] - b->row_off[i] != live[k])
+                return lpbox_fail(LPBOX_E_STATE, "problem %d of the batch is active but its window is not in the packed buffer the scores refer to", i);
+        }
+    }
+    CHK(use_device(b->device));
+    if (A == 0) return LPBOX_OK;
+    hipStream_t st = b->stream;
+    for (int k = 0; k < A; k++) HIPCHK(hipStreamSynchronize(b->hs[act[k]]->stream));     // windows of its own in between have completed
+
+    // host-vector form: one code per live row of every fixing member in pinned memory, and the new host lists
+    std::vector<std::vector<int>> kept(A);
+    std::vector<long> row0(A, 0);
+    long code_rows = 0;
+    if (!score_form) {
+        for (int k = 0; k < A; k++) if (num[k]) { row0[k] = code_rows; code_rows += live[k]; }
+        if ((size_t)code_rows > b->h_codes_cap) {
+            if (b->h_codes) HIPCHK(hipHostFree(b->h_codes));
+            b->h_codes = nullptr; b->h_codes_cap = 0;
+            size_t cap = 0;
+            for (int i = 0; i < b->B; i++) cap += (size_t)b->hs[i]->n_loc;
+            HIPCHK(hipHostMalloc((void **)&b->h_codes, cap));
+            HIPCHK(b->codes.alloc(cap));
+            b->h_codes_cap = cap;
+        }
+        for (int k = 0; k < A; k++) {
+            if (!num[k]) continue;
+            lpbox_big *h = b->hs[act[k]];
+            CHK(refresh_left(h));
+            const double *vec = vecs + (size_t)act[k] * vec_stride;
+            uint8_t *code = b->h_codes + row0[k];
+            kept[k].reserve((size_t)(live[k] - num[k]));
+            for (long q = 0; q < live[k]; q++) {
+                code[q] = vec[q] == 1 ? 2 : (vec[q] == 0 ? 1 : 0);
+                if (!code[q]) kept[k].push_back(h->left_idx[q]);
+            }
+        }
+    }
+    // the staged window of a member grows on the host, only when this window is longer than any before it; the member's live list
+    // goes up once, when its device copy is not current
+    for (int k = 0; k < A; k++) {
+        lpbox_big *h = b->hs[act[k]];
+        if (ws > 0 && (h->ws_cap < ws || !h->xhist.p)) {
+            HIPCHK(h->xhist.alloc((size_t)ws * h->n_loc));
+            h->graphs.clear();                                                      // the captured launches carry the old window buffer
+            h->ws_cap = ws;
+        }
+        if (!h->dlive_valid) {
+            if (!h->left_idx.empty()) HIPCHK(hipMemcpyAsync(h->d_live_idx.p, h->left_idx.data(), sizeof(int) * h->left_idx.size(), hipMemcpyHostToDevice, st));
+            h->dlive_valid = true;
+        }
+    }
+    // one ping-pong parity for the chain (section 28)
+    int parity = b->hs[act[0]]->parity;
+    long long copies = 0;
+    for (int k = 1; k < A; k++) {
+        lpbox_big *h = b->hs[act[k]];
+        if (h->parity != parity) { HIPCHK(big_launch_resume(h->dev(), 0, &h->parity, st)); copies++; }
+    }
+    BigBatchGrid g = b->grid;
+    g.B = A;
+    long max_rows = 0, max_stage = 0;
+    for (int k = 0; k < A; k++) {
+        const lpbox_big *h = b->hs[act[k]];
+        b->h_devs[k] = h->dev();
+        BigFixPar &p = b->h_par[k];
+        p.apply = !score_form && num[k] ? 1 : 0; p.clear = 0;
+        p.rows = score_form || num[k] ? (int)live[k] : 0;
+        p.row0 = score_form ? (scores ? (int)b->row_off[act[k]] : 0) : (int)row0[k];
+        p.n_live_new = live[k] - num[k];
+        p.c1_new = std::pow((double)p.n_live_new, 1.0 / 2);         // on the host, as lpbox_big_iterate_l2f
+        p.live_idx = h->d_live_idx.p;
+        max_rows = std::max<long>(max_rows, p.rows);
+        max_stage = std::max<long>(max_stage, h->xhist.p ? (long)h->ws_cap * h->n_loc : 0);
+    }
+    CHK(bigb_upload_devs(b, A));
+    CHK(bigb_upload_par(b, A));
+    HIPCHK(b->timer.start(st));
+    const long long l0 = b->launches;
+    b->launches += copies; b->parity_copies += copies;
+    HIPCHK(bigb_launch_set_window_l2f(b->devs.p, g, iter_start, iter_end, &parity, st));
+    b->launches++;
+
+    std::vector<long> applied(num);
+    bool any = false, any_clear = false;
+    if (score_form && scores) {
+        std::vector<int> hc(2 * (size_t)A, 0);
+        HIPCHK(hipMemsetAsync(b->counts.p, 0, sizeof(int) * hc.size(), st));
+        HIPCHK(bigb_launch_decide(b->devs.p, b->par.p, g, (int)max_rows, scores, nullptr, hi, lo, b->counts.p, st));
+        HIPCHK(hipMemcpyAsync(hc.data(), b->counts.p, sizeof(int) * hc.size(), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        b->launches++;
+        for (int k = 0; k < A; k++) {
+            const long kf = (long)hc[2 * k] + hc[2 * k + 1];
+            BigFixPar &p = b->h_par[k];
+            if (kf > min_fix) {                                                     // LP/trainer.py:533-535
+                applied[k] = kf; p.apply = 1; p.n_live_new = live[k] - kf;
+                p.c1_new = std::pow((double)p.n_live_new, 1.0 / 2);
+            } else if (kf > 0) { p.clear = 1; any_clear = true; }
+        }
+        CHK(bigb_upload_par(b, A));                                                 // the decision: the one extra copy of this form
+    } else if (!score_form && code_rows > 0) {
+        HIPCHK(hipMemcpyAsync(b->codes.p, b->h_codes, (size_t)code_rows, hipMemcpyHostToDevice, st));
+        HIPCHK(bigb_launch_decide(b->devs.p, b->par.p, g, (int)max_rows, nullptr, b->codes.p, 0.0, 0.0, b->counts.p, st));
+        b->launches++;
+    }
+    for (int k = 0; k < A; k++) any |= applied[k] > 0;
+    if (any) {                                                                      // no member fixes: no prologue at all
+        HIPCHK(bigb_enqueue_fix(b->devs.p, b->par.p, g, &parity, st));
+        b->launches += 8; b->fix_launches += 8;
+    }
+    if (any || any_clear) { HIPCHK(bigb_launch_compact(b->devs.p, b->par.p, g, st)); b->launches++; }
+    if (max_stage > 0) { HIPCHK(bigb_launch_clear_xhist(b->devs.p, g, max_stage, st)); b->launches++; }     // x_iters = Zero (:1113)
+
+    std::vector<long long> resumes(A, 0);
+    const int rc = bigb_run_chain(b, A, act.data(), iter_end, &parity, resumes.data());
+    double ms = 0.0;
+    const hipError_t e = b->timer.stop_sync(st, &ms);
+    if (rc < 0) return rc;
+    HIPCHK(e);
+    b->kernel_ms += ms;
+    for (int k = 0; k < A; k++) {
+        lpbox_big *h = b->hs[act[k]];
+        h->hst = b->h_states[k]; h->parity = parity;
+        h->chain.pcg_resumes += resumes[k];
+        h->n_live_glob = live[k] - applied[k];
+        h->xi_rows = (int)h->n_live_glob; h->xi_valid = true; h->xi_plain = false; h->win_serial++;
+        if (applied[k]) {
+            if (score_form) h->left_stale = true;                                   // fixed on the device: the host list follows on demand
+            else h->left_idx.swap(kept[k]);
+        }
+        if (rets) rets[act[k]] = h->hst.ret;
+        if (fixed) fixed[act[k]] = (int)applied[k];
+    }
+    b->hs[act[0]]->kernel_ms += ms; b->hs[act[0]]->launches += b->launches - l0;
+    b->pack_valid = false;
+    return LPBOX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -944,6 +1165,7 @@ lpbox_big_batch_t *lpbox_big_batch_create(lpbox_big_t **handles, int count) {
     }
     lpbox_big_batch *b = new lpbox_big_batch();
     b->hs.assign(handles, handles + count); b->B = count; b->device = handles[0]->device;
+    b->active.assign(count, 1); b->row_off.assign((size_t)count + 1, 0); b->pack_serial.assign(count, -1);
     if (const char *e = getenv("LPBOX_BIG_KMAX")) { int v = atoi(e); if (v >= 1 && v <= 1000) { b->kmax = v; b->adaptive = false; } }
     if (const char *e = getenv("LPBOX_BIG_KMARGIN")) b->rules.margin = std::max(0, atoi(e));
     if (const char *e = getenv("LPBOX_BIG_BATCH_GRAPH")) b->use_graph = atoi(e) != 0;     // replay captured iterations instead of eager launches
@@ -957,6 +1179,7 @@ void lpbox_big_batch_destroy(lpbox_big_batch_t *b) {
         (void)hipStreamSynchronize(b->stream);
         b->graphs.clear();
         b->timer.destroy();
+        if (b->h_codes) (void)hipHostFree(b->h_codes);
         (void)hipStreamDestroy(b->stream);
     }
     delete b;
@@ -974,8 +1197,8 @@ int lpbox_big_batch_init(lpbox_big_batch_t *b) {
     if (!b->stream) {
         HIPCHK(hipStreamCreate(&b->stream));
         HIPCHK(b->timer.create());
-        HIPCHK(b->devs.alloc(b->B)); HIPCHK(b->dstates.alloc(b->B));
-        b->h_devs.resize(b->B); b->h_states.resize(b->B);
+        HIPCHK(b->devs.alloc(b->B)); HIPCHK(b->dstates.alloc(b->B)); HIPCHK(b->par.alloc(b->B)); HIPCHK(b->counts.alloc(2 * (size_t)b->B));
+        b->h_devs.resize(b->B); b->h_states.resize(b->B); b->h_par.resize(b->B);
     }
     BigBatchGrid g{b->B, 0, 0, 0, 0};
     for (int i = 0; i < b->B; i++) {
@@ -985,6 +1208,7 @@ int lpbox_big_batch_init(lpbox_big_batch_t *b) {
     }
     if (g.cols != b->grid.cols || g.y != b->grid.y || g.rows != b->grid.rows || g.z4 != b->grid.z4) b->graphs.clear();
     b->grid = g;
+    b->pack_valid = false;
     b->inited = true;
     return 1;
 }
@@ -1015,7 +1239,7 @@ int lpbox_big_batch_iterate(lpbox_big_batch_t *b, int iter_start, int iter_end, 
     HIPCHK(bigb_launch_set_window(b->devs.p, b->grid, iter_start, iter_end, &parity, st));
     b->launches++;
     std::vector<long long> resumes(b->B, 0);
-    const int rc = bigb_run_chain(b, iter_end, &parity, resumes.data());
+    const int rc = bigb_run_chain(b, b->B, nullptr, iter_end, &parity, resumes.data());
     double ms = 0.0;
     const hipError_t e = b->timer.stop_sync(st, &ms);
     if (rc < 0) return rc;
@@ -1023,11 +1247,75 @@ int lpbox_big_batch_iterate(lpbox_big_batch_t *b, int iter_start, int iter_end, 
     b->kernel_ms += ms;
     for (int i = 0; i < b->B; i++) {
         lpbox_big *h = b->hs[i];
-        h->hst = b->h_states[i]; h->parity = parity;
+        h->hst = b->h_states[i]; h->parity = parity; h->win_serial++;
         h->chain.pcg_resumes += resumes[i];
         if (rets) rets[i] = h->hst.ret;
     }
     b->hs[0]->kernel_ms += ms; b->hs[0]->launches += b->launches - l0;      // the chain's launches are nobody's in particular: booked on member 0
+    return LPBOX_OK;
+}
+
+int lpbox_big_batch_set_active(lpbox_big_batch_t *b, const unsigned char *active) {
+    if (!b) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
+    for (int i = 0; i < b->B; i++) b->active[i] = active ? (active[i] ? 1 : 0) : 1;
+    return LPBOX_OK;
+}
+
+int lpbox_big_batch_iterate_l2f(lpbox_big_batch_t *b, int iter_start, int iter_end, const double *vecs, long vec_stride, const long *nums, int *rets) {
+    if (!b) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
+    return bigb_window(b, iter_start, iter_end, false, vecs, vec_stride, nums, nullptr, 0.0, 0.0, 0, rets, nullptr);
+}
+
+int lpbox_big_batch_iterate_l2f_scores(lpbox_big_batch_t *b, int iter_start, int iter_end, const float *scores_dev, double hi, double lo, int min_fix,
+                                       int *rets, int *fixed) {
+    if (!b) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
+    return bigb_window(b, iter_start, iter_end, true, nullptr, 0, nullptr, scores_dev, hi, lo, min_fix, rets, fixed);
+}
+
+// the (rows x ws) windows of all active members, one after the other, in ONE buffer of the batch (one launch)
+int lpbox_big_batch_get_x_iters_device(lpbox_big_batch_t *b, int ws, void **dev_ptr, long *row_off) {
+    if (!b) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
+    if (ws <= 0 || ws > LP_XITERS_COLS) return lpbox_fail(LPBOX_E_BADARG, "ws = %d outside (0,%d]", ws, LP_XITERS_COLS);
+    if (!b->inited) return lpbox_fail(LPBOX_E_STATE, "lpbox_big_batch_init has not been called");
+    const std::vector<int> act = bigb_active(b);
+    const int A = (int)act.size();
+    for (int k = 0; k < A; k++) {
+        const lpbox_big *h = b->hs[act[k]];
+        if (!h->inited || !h->xi_valid || h->xi_plain || !h->dlive_valid)
+            return lpbox_fail(LPBOX_E_STATE, "problem %d of the batch: solve_iter_l2f has not been called", act[k]);
+    }
+    CHK(use_device(b->device));
+    std::fill(b->pack_serial.begin(), b->pack_serial.end(), -1L);
+    long tot = 0, max_rows = 0;
+    for (int i = 0, k = 0; i < b->B; i++) {
+        b->row_off[i] = tot;
+        if (k < A && act[k] == i) {
+            const lpbox_big *h = b->hs[i];
+            HIPCHK(hipStreamSynchronize(h->stream));
+            b->h_devs[k] = h->dev();
+            BigFixPar &p = b->h_par[k];
+            p.apply = 0; p.clear = 0; p.rows = h->xi_rows; p.row0 = (int)tot; p.n_live_new = h->xi_rows; p.c1_new = 0.0; p.live_idx = h->d_live_idx.p;
+            tot += h->xi_rows; max_rows = std::max<long>(max_rows, h->xi_rows);
+            b->pack_serial[i] = h->win_serial; k++;
+        }
+    }
+    b->row_off[b->B] = tot;
+    if ((double)tot * ws > 2147483647.0) return lpbox_fail(LPBOX_E_TOOLARGE, "%ld rows of %d iterates exceed the packed buffer's 2^31 - 1 entries", tot, ws);
+    const size_t need = (size_t)std::max<long>(tot, 1) * ws;
+    if (b->pack.count < need) { HIPCHK(hipStreamSynchronize(b->stream)); HIPCHK(b->pack.alloc(need)); }       // grows on demand
+    if (A > 0 && tot > 0) {
+        BigBatchGrid g = b->grid;
+        g.B = A;
+        CHK(bigb_upload_devs(b, A));
+        CHK(bigb_upload_par(b, A));
+        HIPCHK(bigb_launch_pack(b->devs.p, b->par.p, g, (int)max_rows, ws, b->pack.p, b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));
+        b->launches++; b->hs[act[0]]->launches++;
+    }
+    b->packs++;
+    b->pack_valid = true;
+    if (dev_ptr) *dev_ptr = b->pack.p;
+    if (row_off) for (int i = 0; i <= b->B; i++) row_off[i] = b->row_off[i];
     return LPBOX_OK;
 }
 
@@ -1044,6 +1332,8 @@ int lpbox_big_batch_get_scalar(lpbox_big_batch_t *b, const char *name, double *o
         {"count", (double)b->B}, {"launches", (double)b->launches}, {"kernel_ms", b->kernel_ms}, {"kmax", (double)b->kmax},
         {"graph", b->use_graph ? 1.0 : 0.0}, {"parity_copies", (double)b->parity_copies},
         {"grid_cols", (double)b->grid.cols}, {"grid_y", (double)b->grid.y}, {"grid_rows", (double)b->grid.rows}, {"grid_z4", (double)b->grid.z4},
+        {"active", (double)std::count(b->active.begin(), b->active.end(), (uint8_t)1)}, {"fix_launches", (double)b->fix_launches},
+        {"packs", (double)b->packs}, {"compact_chunk", (double)(BIG_CT * BIG_CE)},
     };
     for (auto &e : tab) if (!strcmp(e.n, name)) { *out = e.v; return LPBOX_OK; }
     return lpbox_fail(LPBOX_E_BADARG, "unknown scalar '%s'", name);

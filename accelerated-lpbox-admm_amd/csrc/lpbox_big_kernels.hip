@@ -190,6 +190,138 @@ __global__ void __launch_bounds__(T) big_kb_post(const BigDev *__restrict__ devs
 __global__ void __launch_bounds__(T) big_kb_z4(const BigDev *__restrict__ devs, int in, int out) { const BigDev &d = devs[blockIdx.y]; if ((int)blockIdx.x >= ext_z4(d)) return; big_b_z4(d, in, out, 0); }
 __global__ void big_kb_collect(const BigDev *__restrict__ devs, int parity, BigState *out) { out[blockIdx.x] = devs[blockIdx.x].st[parity]; }
 
+// ---- early-fixing windows of a batch: the prologue of lpbox_big_iterate_l2f (fix1, fin, rows, fix2, fin, fix3, rows, z4) over (X, members).
+// par[blockIdx.y] is the member's record of this window.  A member with apply == 0 falls through: the whole workgroup leaves before the
+// first barrier and before any store; in the launches that move the ping-pong parity its leader copies st[in] to st[out], so that one
+// parity serves the chain.  A member whose fix leaves nothing live (n_live_new == 0) is halted by fix3 and falls through the two
+// launches behind it the same way, as the one-problem call does not enqueue them.
+__global__ void big_kb_set_window_l2f(const BigDev *__restrict__ devs, int in, int out, int iter_start, int iter_end) { big_b_set_window(devs[blockIdx.y], in, out, iter_start, iter_end, 1); }
+__global__ void __launch_bounds__(T) big_kb_fix1(const BigDev *__restrict__ devs, const BigFixPar *__restrict__ par) {
+    if (!par[blockIdx.y].apply) return;
+    const BigDev &d = devs[blockIdx.y];
+    if ((int)blockIdx.x >= ext_cols(d)) return;
+    big_b_fix1(d, WgSums{});
+}
+__global__ void __launch_bounds__(T) big_kb_fin(const BigDev *__restrict__ devs, const BigFixPar *__restrict__ par, int nv, int phase) {
+    __shared__ double red[2 * RED_MAXV * RED_MAXW];
+    if (!par[blockIdx.y].apply) return;
+    const BigDev &d = devs[blockIdx.y];
+    int parity = 0;
+    fin_reduce<T>(part_ptr(d, phase), d.G, nv, d.red + phase * BIG_NPART, red, parity, d.Gs);
+}
+__global__ void __launch_bounds__(T) big_kb_fix_rows(const BigDev *__restrict__ devs, const BigFixPar *__restrict__ par, int in, int out, int after_fix3) {
+    const BigDev &d = devs[blockIdx.y];
+    const BigFixPar &p = par[blockIdx.y];
+    if (!p.apply || (after_fix3 && p.n_live_new == 0)) { forward_state(d, in, out); return; }
+    if ((int)blockIdx.x >= ext_rows(d)) return;
+    big_b_rows<WgSums, false>(d, WgSums{}, in, out, 0);
+}
+__global__ void __launch_bounds__(T) big_kb_fix2(const BigDev *__restrict__ devs, const BigFixPar *__restrict__ par, int in, int out) {
+    const BigDev &d = devs[blockIdx.y];
+    if (!par[blockIdx.y].apply) { forward_state(d, in, out); return; }
+    if ((int)blockIdx.x >= ext_y(d)) return;
+    big_b_fix2(d, WgSums{}, in, out);
+}
+__global__ void __launch_bounds__(T) big_kb_fix3(const BigDev *__restrict__ devs, const BigFixPar *__restrict__ par, int in, int out) {
+    const BigDev &d = devs[blockIdx.y];
+    const BigFixPar &p = par[blockIdx.y];
+    if (!p.apply) { forward_state(d, in, out); return; }
+    if ((int)blockIdx.x >= ext_cols(d)) return;
+    big_b_fix3<WgSums, false>(d, WgSums{}, in, out, p.n_live_new, p.c1_new);
+}
+__global__ void __launch_bounds__(T) big_kb_z4_init(const BigDev *__restrict__ devs, const BigFixPar *__restrict__ par, int in, int out) {
+    const BigDev &d = devs[blockIdx.y];
+    const BigFixPar &p = par[blockIdx.y];
+    if (!p.apply || p.n_live_new == 0) { forward_state(d, in, out); return; }
+    if ((int)blockIdx.x >= ext_z4(d)) return;
+    big_b_z4(d, in, out, 1);
+}
+
+// x_iters = Zero (LPcpp:1113) for every member: all ws_cap staged columns, as the one-problem call's memset
+__global__ void big_kb_clear_xhist(const BigDev *__restrict__ devs) {
+    const BigDev &d = devs[blockIdx.y];
+    if (!d.xhist) return;
+    const size_t total = (size_t)d.ws_cap * d.n_loc;
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) d.xhist[e] = 0.0;
+}
+
+// The fix decision per packed row q of member y (original index live_idx[q]) -> its newfix code, and the member's counts of fixes to one
+// / to zero (integer atomics: the sums do not depend on the order).  scores: deter_fix_2 on the float32 score of row row0 + q, widened to
+// double (s > hi -> 1, s < lo -> 0, NaN -> neither); codes: the host's decision, one byte per row (the host-vector form).
+__global__ void __launch_bounds__(T) big_kb_decide(const BigDev *__restrict__ devs, const BigFixPar *__restrict__ par, const float *__restrict__ scores,
+                                                   const uint8_t *__restrict__ codes, double hi, double lo, int *counts) {
+    const BigDev &d = devs[blockIdx.y];
+    const BigFixPar &a = par[blockIdx.y];
+    uint8_t *newfix = const_cast<uint8_t *>(d.newfix);
+    __shared__ int cnt[2];
+    if (threadIdx.x < 2) cnt[threadIdx.x] = 0;
+    __syncthreads();
+    for (int q = blockIdx.x * T + threadIdx.x; q < a.rows; q += gridDim.x * T) {
+        int code;
+        if (codes) code = codes[(size_t)a.row0 + q];
+        else { const double s = (double)scores[(size_t)a.row0 + q]; code = s > hi ? 2 : (s < lo ? 1 : 0); }
+        newfix[a.live_idx[q]] = (uint8_t)code;
+        if (code) atomicAdd(&cnt[code == 2 ? 0 : 1], 1);
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 && cnt[threadIdx.x]) atomicAdd(&counts[2 * blockIdx.y + threadIdx.x], cnt[threadIdx.x]);
+}
+
+// Ordered stream compaction of a member's live list after a fix: the entries whose newfix code is 0 stay, in the same (ascending) order,
+// in place; the codes are cleared on the way (every non-zero code sits at an entry of the old list), which is the one-problem call's
+// memset.  One workgroup per member walks the list in chunks of BIG_CT * BIG_CE entries: wave64 prefix by shuffles, wave totals through
+// LDS, a carried offset; a chunk's writes land at or before its own entries, which were all read before its first write.  A member with
+// clear != 0 (codes on the device, but the guard left the fix unapplied) gets its codes cleared and keeps its list.
+__global__ void __launch_bounds__(BIG_CT) big_kb_compact(const BigDev *__restrict__ devs, const BigFixPar *__restrict__ par) {
+    const BigDev &d = devs[blockIdx.x];
+    const BigFixPar &a = par[blockIdx.x];
+    if (!a.apply && !a.clear) return;
+    const bool move = a.apply != 0;
+    uint8_t *newfix = const_cast<uint8_t *>(d.newfix);
+    __shared__ int wsum[BIG_CT / 64 + 1];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int carried = 0;
+    for (int base = 0; base < a.rows; base += BIG_CT * BIG_CE) {
+        int org[BIG_CE], keep[BIG_CE], c = 0;
+#pragma unroll
+        for (int k = 0; k < BIG_CE; k++) {
+            const int q = base + threadIdx.x * BIG_CE + k;
+            org[k] = q < a.rows ? a.live_idx[q] : -1;
+            keep[k] = 0;
+            if (org[k] >= 0) {
+                if (newfix[org[k]]) newfix[org[k]] = 0; else keep[k] = 1;
+            }
+            c += keep[k];
+        }
+        if (!move) continue;                                                  // uniform over the workgroup
+        int v = c;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) { const int t = __shfl_up(v, off, 64); if (lane >= off) v += t; }
+        if (lane == 63) wsum[w + 1] = v;
+        __syncthreads();
+        if (threadIdx.x == 0) { wsum[0] = 0; for (int k = 1; k <= BIG_CT / 64; k++) wsum[k] += wsum[k - 1]; }
+        __syncthreads();
+        int pos = carried + wsum[w] + v - c;
+        const int total = wsum[BIG_CT / 64];
+#pragma unroll
+        for (int k = 0; k < BIG_CE; k++) if (keep[k]) a.live_idx[pos++] = org[k];
+        carried += total;
+        __syncthreads();
+    }
+}
+
+// big_k_pack_xiters per member: member y's (rows x ws) window goes to out + row0 * ws
+__global__ void big_kb_pack(const BigDev *__restrict__ devs, const BigFixPar *__restrict__ par, int ws, double *out) {
+    const BigDev &d = devs[blockIdx.y];
+    const BigFixPar &a = par[blockIdx.y];
+    const long total = (long)a.rows * ws;
+    double *o = out + (size_t)a.row0 * ws;
+    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+        const int r = (int)(e / ws), c = (int)(e % ws);
+        o[e] = c < d.ws_cap ? d.xhist[(size_t)c * d.n_loc + a.live_idx[r]] : 0.0;
+    }
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -350,5 +482,51 @@ hipError_t bigb_enqueue_iterations(const BigDev *devs, const BigBatchGrid &g, in
 }
 hipError_t bigb_collect_states(const BigDev *devs, const BigBatchGrid &g, int parity, BigState *out, hipStream_t s) {
     hipLaunchKernelGGL(big_kb_collect, dim3(g.B), dim3(1), 0, s, devs, parity, out);
+    return hipGetLastError();
+}
+
+// ---- early-fixing windows of a batch ----
+hipError_t bigb_launch_set_window_l2f(const BigDev *devs, const BigBatchGrid &g, int iter_start, int iter_end, int *parity, hipStream_t s) {
+    hipLaunchKernelGGL(big_kb_set_window_l2f, dim3(1, g.B), dim3(1), 0, s, devs, *parity, *parity ^ 1, iter_start, iter_end);
+    *parity ^= 1;
+    return hipGetLastError();
+}
+#define BIGB_FIX_LAUNCH(kernel, X, ...)                                                                               \
+    do {                                                                                                              \
+        hipLaunchKernelGGL(kernel, dim3(X, g.B), dim3(T), 0, s, devs, par, *parity, *parity ^ 1, ##__VA_ARGS__);      \
+        *parity ^= 1;                                                                                                 \
+    } while (0)
+hipError_t bigb_enqueue_fix(const BigDev *devs, const BigFixPar *par, const BigBatchGrid &g, int *parity, hipStream_t s) {
+    hipLaunchKernelGGL(big_kb_fix1, dim3(g.cols, g.B), dim3(T), 0, s, devs, par);
+    hipLaunchKernelGGL(big_kb_fin, dim3(1, g.B), dim3(T), 0, s, devs, par, 1, BIG_PH_X);      // fix_obj = b2.x2
+    BIGB_FIX_LAUNCH(big_kb_fix_rows, g.rows, 0);                                               // q = E2 * x2
+    BIGB_FIX_LAUNCH(big_kb_fix2, g.y);
+    hipLaunchKernelGGL(big_kb_fin, dim3(1, g.B), dim3(T), 0, s, devs, par, 1, BIG_PH_X);      // |x_live|^2
+    BIGB_FIX_LAUNCH(big_kb_fix3, g.cols);
+    BIGB_FIX_LAUNCH(big_kb_fix_rows, g.rows, 1);                                               // E * x (live columns) for the first y3
+    BIGB_FIX_LAUNCH(big_kb_z4_init, g.z4);
+    return hipGetLastError();
+}
+hipError_t bigb_launch_clear_xhist(const BigDev *devs, const BigBatchGrid &g, long max_total, hipStream_t s) {
+    if (max_total <= 0) return hipSuccess;
+    const int X = (int)std::min<long>((max_total + 1023) / 1024, 1024);
+    hipLaunchKernelGGL(big_kb_clear_xhist, dim3(X, g.B), dim3(256), 0, s, devs);
+    return hipGetLastError();
+}
+hipError_t bigb_launch_decide(const BigDev *devs, const BigFixPar *par, const BigBatchGrid &g, int max_rows, const float *scores, const uint8_t *codes,
+                              double hi, double lo, int *counts, hipStream_t s) {
+    if (max_rows <= 0) return hipSuccess;
+    const int X = std::min((max_rows + T - 1) / T, 1024);
+    hipLaunchKernelGGL(big_kb_decide, dim3(X, g.B), dim3(T), 0, s, devs, par, scores, codes, hi, lo, counts);
+    return hipGetLastError();
+}
+hipError_t bigb_launch_compact(const BigDev *devs, const BigFixPar *par, const BigBatchGrid &g, hipStream_t s) {
+    hipLaunchKernelGGL(big_kb_compact, dim3(g.B), dim3(BIG_CT), 0, s, devs, par);
+    return hipGetLastError();
+}
+hipError_t bigb_launch_pack(const BigDev *devs, const BigFixPar *par, const BigBatchGrid &g, int max_rows, int ws, double *out, hipStream_t s) {
+    if (max_rows <= 0 || ws <= 0) return hipSuccess;
+    const int X = (int)std::min<long>(((long)max_rows * ws + 255) / 256, 4096);
+    hipLaunchKernelGGL(big_kb_pack, dim3(X, g.B), dim3(256), 0, s, devs, par, ws, out);
     return hipGetLastError();
 }

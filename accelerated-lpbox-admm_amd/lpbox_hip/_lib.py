@@ -125,6 +125,11 @@ SYMBOLS = {
     "lpbox_big_batch_init": (C.c_int, [C.c_void_p]),
     "lpbox_big_batch_iterate": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "lpbox_big_batch_get_scalar": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_double)]),
+    "lpbox_big_batch_set_active": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "lpbox_big_batch_iterate_l2f": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p]),
+    "lpbox_big_batch_get_x_iters_device": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]),
+    "lpbox_big_batch_iterate_l2f_scores": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_void_p,
+                                                     C.c_void_p]),
     "lpbox_bqp_create": (C.c_void_p, [C.c_int]),
     "lpbox_bqp_destroy": (None, [C.c_void_p]),
     "lpbox_bqp_preset": (C.c_int, [C.c_void_p, C.c_int]),

@@ -282,6 +282,80 @@ class BigLpBatch:
         check(self._L.lpbox_big_batch_get_scalar(self._h, name.encode(), C.byref(v)), "lpbox_big_batch_get_scalar")
         return v.value
 
+    # ---- early-fixing windows of all active members in one lockstep chain (lpbox_big_batch_iterate_l2f* in include/lpbox_hip.h) ----
+    def set_active(self, mask):
+        """mask: one truth value per member, or None for all.  It governs solve_iter_l2f, x_iters_torch and solve_iter_l2f_scores;
+        solve_iter keeps running every member."""
+        if mask is None:
+            return check(self._L.lpbox_big_batch_set_active(self._h, None), "lpbox_big_batch_set_active")
+        m = np.ascontiguousarray(np.asarray(mask).astype(bool).astype(np.uint8))
+        if m.shape != (len(self.solvers),):
+            raise ValueError("mask must have one entry per member")
+        return check(self._L.lpbox_big_batch_set_active(self._h, m.ctypes.data_as(C.c_void_p)), "lpbox_big_batch_set_active")
+
+    def solve_iter_l2f(self, i, j, vecs, nums):
+        """vecs: one fix vector per member over its live variables (1 / 0 fix, anything else leave) or None, or None for all; nums: the
+        members' fix counts.  Returns the int32 array of return values (entries of inactive members stay 0)."""
+        B = len(self.solvers)
+        nums = np.ascontiguousarray(nums, np.int64).ravel()
+        if nums.shape[0] != B:
+            raise ValueError("nums must have one entry per member")
+        ptr, stride = None, 0
+        if vecs is not None:
+            vecs = list(vecs)
+            if len(vecs) != B:
+                raise ValueError("vecs must have one entry (an array or None) per member")
+            vecs = [None if v is None else np.asarray(v, np.float64).ravel() for v in vecs]
+            stride = max([v.shape[0] for v in vecs if v is not None], default=0)
+            if stride:
+                flat = np.full((B, stride), -1.0)
+                for k, v in enumerate(vecs):
+                    if v is not None:
+                        flat[k, :v.shape[0]] = v
+                ptr = flat.ctypes.data_as(C.c_void_p)
+        rets = np.zeros(B, np.int32)
+        check(self._L.lpbox_big_batch_iterate_l2f(self._h, int(i), int(j), ptr, stride, nums.ctypes.data_as(C.c_void_p),
+                                                  rets.ctypes.data_as(C.c_void_p)), "lpbox_big_batch_iterate_l2f")
+        return rets
+
+    def x_iters_torch(self, ws):
+        """(tensor (rows, ws) float64, zero-copy on the device; row_off int64 (members + 1)): rows row_off[k] .. row_off[k+1] are member
+        k's live variables when its window started, in ascending original index (none for an inactive member).  Valid until the next call
+        on the batch."""
+        import torch
+        ws = int(ws)
+        ptr = C.c_void_p()
+        off = np.zeros(len(self.solvers) + 1, np.int64)
+        check(self._L.lpbox_big_batch_get_x_iters_device(self._h, ws, C.byref(ptr), off.ctypes.data_as(C.c_void_p)),
+              "lpbox_big_batch_get_x_iters_device")
+        rows = int(off[-1])
+        self._packed_rows = rows
+        if rows == 0:
+            return torch.zeros((0, ws), dtype=torch.float64, device="cuda"), off
+        return _dev_tensor(ptr.value, rows * ws).view(rows, ws), off
+
+    def solve_iter_l2f_scores(self, i, j, scores, C=0.9, min_fix=10):
+        """The window with deter_fix_2 (threshold C: hi = C, lo = 1 - C) and the `<= min_fix -> none` guard applied on the device:
+        scores = float32 CUDA tensor, one score per row of the last x_iters_torch(), or None (fix nothing).  Returns (rets, fixed),
+        int32 arrays."""
+        import ctypes
+        ptr = None
+        if scores is not None:
+            import torch
+            if not (scores.is_cuda and scores.dtype == torch.float32):
+                raise TypeError("scores must be a float32 CUDA tensor")
+            scores = scores.contiguous().reshape(-1)
+            if scores.numel() != getattr(self, "_packed_rows", -1):
+                raise ValueError("scores must hold one entry per row of the last x_iters_torch()")
+            torch.cuda.current_stream(scores.device).synchronize()      # the batch runs on a stream of its own
+            ptr = ctypes.c_void_p(scores.data_ptr())
+        B = len(self.solvers)
+        rets, fixed = np.zeros(B, np.int32), np.zeros(B, np.int32)
+        check(self._L.lpbox_big_batch_iterate_l2f_scores(self._h, int(i), int(j), ptr, float(C), 1 - float(C), int(min_fix),
+                                                         rets.ctypes.data_as(ctypes.c_void_p), fixed.ctypes.data_as(ctypes.c_void_p)),
+              "lpbox_big_batch_iterate_l2f_scores")
+        return rets, fixed
+
 
 def solve_many(problems, max_iters=20000, device=0):
     """Solve every problem to its own stop in one lockstep chain: (rets, binary solutions, objectives cal_Obj())."""

@@ -260,3 +260,48 @@ def run_l2f_big(big, score_fn_torch, ws=100, max_iter=10000, tokens=20, min_fix=
         else:
             vec = v
     return dict(objective=-big.cal_Obj(), windows=windows, fixed=fixed, live=big.scalar("n_live"))
+
+
+def run_l2f_big_batch(problems_or_batch, policy, ws=100, max_iter=10000, tokens=20, min_fix=10, C=0.9):
+    """The loop of run_l2f_big for all members at once (lpbox_hip.big.BigLpBatch; problem dicts / BigLp objects, for which the batch is
+    built and initialised here, or a BigLpBatch after solve_init()): per window ONE lockstep launch chain over the unfinished members,
+    one pack, ONE policy call over the packed rows of all of them, and the fix decided on the device from the scores, which never leave
+    it.  policy: a FusedEarlyFixPolicy (called through scores_from_xiters) or a plain torch callable on the float32
+    (rows, tokens, ws // tokens) view.  A member whose window returned non-zero is deactivated.  Returns one dict per member with the keys
+    of run_l2f_big: objective, windows, fixed, live."""
+    from .big import BigLpBatch
+    own = not isinstance(problems_or_batch, BigLpBatch)
+    batch = BigLpBatch(problems_or_batch) if own else problems_or_batch
+    try:
+        import torch
+        B = len(batch)
+        if own:
+            batch.solve_init()
+        done = np.zeros(B, bool)
+        windows, fixed = np.zeros(B, int), np.zeros(B, int)
+        sig = None
+        for w in range(int(max_iter / ws)):
+            batch.set_active(~done)
+            rets, fx = batch.solve_iter_l2f_scores(ws * w, ws * (w + 1), sig, C, min_fix)
+            windows[~done] += 1
+            fixed[~done] += fx[~done]
+            done |= rets != 0
+            if done.all():
+                break
+            batch.set_active(~done)
+            X, _ = batch.x_iters_torch(ws)
+            if hasattr(policy, "scores_from_xiters"):
+                off = torch.arange(X.shape[0], device=X.device, dtype=torch.int64) * ws
+                sig = policy.scores_from_xiters(X.reshape(-1), off, ws // tokens)
+            elif X.shape[0]:
+                sig = policy(X.view(-1, tokens, ws // tokens).to(torch.float32))
+            else:
+                sig = torch.zeros(0, device=X.device)
+            sig = sig.reshape(-1).to(torch.float32)
+        out = [dict(objective=-s.cal_Obj(), windows=int(windows[k]), fixed=int(fixed[k]), live=s.scalar("n_live"))
+               for k, s in enumerate(batch.solvers)]
+    finally:
+        batch.set_active(None)
+        if own:
+            batch.close()
+    return out

@@ -395,8 +395,37 @@ lpbox_big_batch_t *lpbox_big_batch_create(lpbox_big_t **handles, int count);
 void lpbox_big_batch_destroy(lpbox_big_batch_t *b);
 int lpbox_big_batch_init(lpbox_big_batch_t *b);                                  /* lpbox_big_init on every member */
 int lpbox_big_batch_iterate(lpbox_big_batch_t *b, int iter_start, int iter_end, int *rets);   /* ADMM_lp_iters per member; rets[count] */
+/* The early-fixing windows of lpbox_big_iterate_l2f (LPcpp:1098-1574; the loop of LP/trainer.py:504-545) for the batch: the fix
+ * prologue, the window, the pack of the iterates and the fix decision of all active members each run in launches over a
+ * (workgroups, members) grid.  Per member every result is that of lpbox_big_iterate_l2f on its own with the same fix vectors, bit for
+ * bit; fixed variables are allowed here (lpbox_big_batch_create / _init and the plain lpbox_big_batch_iterate keep refusing them), the
+ * other member conditions are those above.  After any batched window every member answers every getter and may go on with windows of
+ * its own.
+ * _set_active: active[count], NULL = all.  It governs the three calls below only (lpbox_big_batch_iterate runs every member).  An
+ *   inactive member is not touched by them: state, vectors, staged window, counters, rets[i] / fixed[i].
+ * _iterate_l2f: member i fixes by vecs + i * vec_stride over its live variables in ascending order (1 / 0 = fix, anything else =
+ *   leave) and nums[i], validated as lpbox_big_iterate_l2f does on one rank (count mismatch, nums[i] outside [0, n_live], missing
+ *   vector, window longer than the 500 columns of x_iters); vecs may be NULL when every nums[i] is 0.  All members are validated before
+ *   anything changes; a refusal names the member.  Refusals in this order: arguments (LPBOX_E_BADARG), call order (LPBOX_E_STATE before
+ *   _init), the member conditions (LPBOX_E_UNSUPPORTED).  rets[count].
+ * _get_x_iters_device: one launch packs the (rows x ws) row-major windows of all active members into one buffer of the batch: member
+ *   i's rows are [row_off[i], row_off[i+1]) (row_off[count + 1]; no rows for an inactive member), row q = its q-th live variable when
+ *   the window started, in ascending original index -- the row order of lpbox_big_get_x_iters.  The buffer grows on demand and stays
+ *   valid until the next call on the batch.
+ * _iterate_l2f_scores: the same window with the fix decided on the device.  scores_dev[r] = float32 score of packed row r of the most
+ *   recent _get_x_iters_device (LPBOX_E_STATE: none since the last window, or a member active now that was not packed then); NULL =
+ *   fix nothing.  Per member deter_fix_2 with the trainer's guard: the score widened to double, s > hi -> 1, s < lo -> 0, NaN ->
+ *   nothing, k = number of fixes, k <= min_fix -> nothing fixed.  fixed[count] = fixes applied.  The caller orders its own work on
+ *   scores_dev before the call (the batch runs on a stream of its own). */
+int lpbox_big_batch_set_active(lpbox_big_batch_t *b, const unsigned char *active);
+int lpbox_big_batch_iterate_l2f(lpbox_big_batch_t *b, int iter_start, int iter_end,
+                                const double *vecs, long vec_stride, const long *nums, int *rets);
+int lpbox_big_batch_get_x_iters_device(lpbox_big_batch_t *b, int ws, void **dev_ptr, long *row_off);
+int lpbox_big_batch_iterate_l2f_scores(lpbox_big_batch_t *b, int iter_start, int iter_end, const float *scores_dev,
+                                       double hi, double lo, int min_fix, int *rets, int *fixed);
 /* "count", "launches", "kernel_ms", "kmax", "graph", "parity_copies", "grid_cols" / "grid_y" / "grid_rows" / "grid_z4" (the x-extents
- * of the launches), "pcg_resumes_<i>" (member i) */
+ * of the launches), "pcg_resumes_<i>" (member i); "active" (members), "fix_launches" (launches of the fix prologue), "packs",
+ * "compact_chunk" (entries per pass of the live-list compaction) */
 int lpbox_big_batch_get_scalar(lpbox_big_batch_t *b, const char *name, double *out);
 
 /* ---- generic constrained binary QP: min x'Ax + b'x  s.t.  Cx = d, Ex <= f, x in {0,1}^n -----------------------------------------

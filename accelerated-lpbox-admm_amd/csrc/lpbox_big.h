@@ -116,6 +116,7 @@ hipError_t bigb_launch_prep(const BigDev *devs, const BigBatchGrid &g, int do_pr
 hipError_t bigb_enqueue_pcg(const BigDev *devs, const BigBatchGrid &g, int pairs, int *parity, hipStream_t s);      // pairs x (rows(1), pcg_cols, pcg_upd)
 hipError_t bigb_enqueue_tail(const BigDev *devs, const BigBatchGrid &g, int *parity, hipStream_t s);                // post, rows(0), z4
 hipError_t bigb_enqueue_iterations(const BigDev *devs, const BigBatchGrid &g, int iters, int kmax, int *parity, hipStream_t s);   // 8 + 3 kmax launches each
+hipError_t bigb_launch_z4(const BigDev *devs, const BigBatchGrid &g, int *parity, hipStream_t s);                  // the tail's last launch alone
 hipError_t bigb_collect_states(const BigDev *devs, const BigBatchGrid &g, int parity, BigState *out, hipStream_t s);   // out[i] = st[parity] of problem i
 
 // ---- early-fixing windows (lpbox_big_iterate_l2f) of a batch: lpbox_big_batch_iterate_l2f / _l2f_scores / _get_x_iters_device ----
@@ -179,3 +180,15 @@ __global__ void bigref_k_post(BigDev d, BigRef rf, int in, int out);
 __global__ void bigref_k_fix1(BigDev d, BigRef rf);
 __global__ void bigref_k_fix2(BigDev d, BigRef rf, int in, int out);
 __global__ void bigref_k_fix3_v(BigDev d, BigRef rf, int in, int out, long n_live_new, double c1_new);
+
+// ---- a batch in lockstep in the reference order (lpbox_big_batch_* whose members all run it) ----
+// refs: device array parallel to devs.  The launches are the solo reference chain's, launch for launch, over the grids of BigBatchGrid; a
+// walk (bigref_kb_walk, grid (1, B): one walker per member) stands wherever the solo chain has one.  set_window, resume, z4 and collect
+// are the bigb_* launches above: no order changes them.
+hipError_t bigrefb_launch_prep(const BigDev *devs, const BigRef *refs, const BigBatchGrid &g, int do_prep, int *parity, hipStream_t s);
+hipError_t bigrefb_enqueue_pcg(const BigDev *devs, const BigRef *refs, const BigBatchGrid &g, int pairs, int *parity, hipStream_t s);     // pairs x (rows(1), pcg_cols, WALK(1,C), pcg_upd, WALK(2,D))
+hipError_t bigrefb_enqueue_tail(const BigDev *devs, const BigRef *refs, const BigBatchGrid &g, int *parity, hipStream_t s);               // post, WALK(5,E), rows(0), z4
+// kinds: which kinds of member the batch has.  Unit and valued members share every launch but y, which has an entry per kind.  An
+// iteration is 11 + 5 kmax launches, 3 + 2 kmax of them walks; one more (the second y) when the batch has both kinds.
+enum { BIGREF_KIND_UNIT = 1, BIGREF_KIND_VALUED = 2 };
+hipError_t bigrefb_enqueue_iterations(const BigDev *devs, const BigRef *refs, const BigBatchGrid &g, int kinds, int iters, int kmax, int *parity, hipStream_t s);

@@ -857,6 +857,12 @@ struct lpbox_big_batch {
     BigBatchGrid grid{0, 0, 0, 0, 0};
     DevBuf<BigDev> devs; DevBuf<BigState> dstates;
     std::vector<BigDev> h_devs;                     // host side of devs (alive until the stream has taken it)
+    // the batch's summation order is member 0's at create; reference order: the members' BigRef descriptors in a
+    // device array parallel to devs, uploaded with it, and the walker launches counted
+    bool ref = false;
+    DevBuf<BigRef> refs; std::vector<BigRef> h_refs;
+    long long walks = 0;
+    int kinds = 0;                                  // BIGREF_KIND_*: the kinds of member of the window being run
     std::vector<BigState> h_states;
     double kernel_ms = 0.0; long long launches = 0, collectives = 0, parity_copies = 0;
     // early-fixing windows
@@ -875,14 +881,15 @@ namespace {
 
 // what a member must be for the lockstep chain; `i` names it in the message.  Checked at create, init and iterate: a handle can be
 // changed between the calls (recording switched on, an early-fixing window of its own).
-int bigb_member_ok(const lpbox_big *h, int i, bool allow_fixed = false) {      // allow_fixed: the early-fixing calls
+int bigb_member_ok(const lpbox_big *h, int i, bool ref_batch, bool allow_fixed = false) {      // ref_batch: the batch's order; allow_fixed: the early-fixing calls
     if (!h || !h->has_problem) return lpbox_fail(LPBOX_E_STATE, "problem %d of the batch has no problem", i);
-    if (h->ref) return lpbox_fail(LPBOX_E_UNSUPPORTED, "problem %d of the batch runs in the reference summation order; the batch runs the default order", i);
+    if (h->ref && !ref_batch) return lpbox_fail(LPBOX_E_UNSUPPORTED, "problem %d of the batch runs in the reference summation order; the batch runs the default order", i);
+    if (!h->ref && ref_batch) return lpbox_fail(LPBOX_E_UNSUPPORTED, "problem %d of the batch runs in the default order; the batch runs the reference summation order (problem 0's)", i);
     if (h->world != 1) return lpbox_fail(LPBOX_E_UNSUPPORTED, "problem %d of the batch is sharded over %d ranks; the batch runs one rank per problem", i, h->world);
     if (h->comm || h->ag) return lpbox_fail(LPBOX_E_UNSUPPORTED, "problem %d of the batch has a transport; the batch issues no collectives", i);
     if (h->lean) return lpbox_fail(LPBOX_E_UNSUPPORTED, "problem %d of the batch uses the comm-lean PCG", i);
     if (h->record) return lpbox_fail(LPBOX_E_UNSUPPORTED, "problem %d of the batch is recording; recording is per handle (lpbox_big_iterate)", i);
-    if (h->uploaded && !h->fold)
+    if (!ref_batch && h->uploaded && !h->fold)             // (the reference order runs with the fold off: its walker writes the totals)
         return lpbox_fail(LPBOX_E_UNSUPPORTED, "problem %d of the batch runs without folded reductions (LPBOX_BIG_NOFOLD, or more than %d workgroups)", i, BIG_FOLD_U * BIG_T);
     if (!allow_fixed && h->inited && h->n_live_glob != h->n_glob)
         return lpbox_fail(LPBOX_E_UNSUPPORTED, "problem %d of the batch has fixed variables; early-fixing windows are per handle (lpbox_big_iterate_l2f)", i);
@@ -903,6 +910,8 @@ int bigb_collect(lpbox_big_batch *b, const BigBatchGrid &g, int parity) {
 int bigb_run_chain(lpbox_big_batch *b, int A, const int *act, int iter_end, int *parity, long long *resumes) {
     const ChainRules &rules = b->rules;
     const BigDev *devs = b->devs.p;
+    const BigRef *refs = b->refs.p;
+    const bool ref = b->ref;                                        // reference order: the solo chain's launches with a BigRef, launch for launch
     BigBatchGrid g = b->grid;
     g.B = A;
     if (b->graph_B != A) { b->graphs.clear(); b->graph_B = A; }     // the captured launches carry the member count
@@ -929,9 +938,15 @@ int bigb_run_chain(lpbox_big_batch *b, int A, const int *act, int iter_end, int 
         }
         if (more) {                                                 // some PCG ran out of launch groups: resume it (the others fall through)
             HIPCHK(bigb_launch_resume(devs, g, 0, parity, st));
-            HIPCHK(bigb_enqueue_pcg(devs, g, CHAIN_PAIRS_PER_RESUME, parity, st));
-            HIPCHK(bigb_enqueue_tail(devs, g, parity, st));
-            b->launches += 4 + 3 * CHAIN_PAIRS_PER_RESUME;
+            if (ref) {
+                HIPCHK(bigrefb_enqueue_pcg(devs, refs, g, CHAIN_PAIRS_PER_RESUME, parity, st));
+                HIPCHK(bigrefb_enqueue_tail(devs, refs, g, parity, st));
+                b->launches += 5 + 5 * CHAIN_PAIRS_PER_RESUME; b->walks += 1 + 2 * CHAIN_PAIRS_PER_RESUME;
+            } else {
+                HIPCHK(bigb_enqueue_pcg(devs, g, CHAIN_PAIRS_PER_RESUME, parity, st));
+                HIPCHK(bigb_enqueue_tail(devs, g, parity, st));
+                b->launches += 4 + 3 * CHAIN_PAIRS_PER_RESUME;
+            }
             if (b->adaptive) b->kmax = chain_kmax_after_halt(rules, b->kmax, pcg_k);
             continue;
         }
@@ -942,10 +957,16 @@ int bigb_run_chain(lpbox_big_batch *b, int A, const int *act, int iter_end, int 
         int batch = chain_batch_iters(rules, remaining);
         const int per_graph = rules.iters_per_graph;
         auto enqueue = [&](int n) {
-            HIPCHK(bigb_enqueue_iterations(devs, g, n, kmax, parity, st));
-            b->launches += (long long)n * (8 + 3 * kmax);
+            if (ref) {
+                HIPCHK(bigrefb_enqueue_iterations(devs, refs, g, b->kinds, n, kmax, parity, st));
+                b->launches += (long long)n * (11 + 5 * kmax + (b->kinds == (BIGREF_KIND_UNIT | BIGREF_KIND_VALUED) ? 1 : 0));
+            } else {
+                HIPCHK(bigb_enqueue_iterations(devs, g, n, kmax, parity, st));
+                b->launches += (long long)n * (8 + 3 * kmax);
+            }
             return (int)LPBOX_OK;
         };
+        if (ref) b->walks += (long long)batch * (3 + 2 * kmax);         // replayed or eager: every iteration of the batch has them
         if (b->use_graph && batch >= per_graph) {
             ChainIo io{st, *parity, b->launches, b->collectives, b->use_graph, true};
             const GraphCache::Entry *ge = nullptr;
@@ -957,10 +978,15 @@ int bigb_run_chain(lpbox_big_batch *b, int A, const int *act, int iter_end, int 
             }
         }
         if (batch > 0) CHK(enqueue(batch));
-        HIPCHK(bigb_launch_prep(devs, g, 0, parity, st));
+        if (ref) HIPCHK(bigrefb_launch_prep(devs, refs, g, 0, parity, st)); else HIPCHK(bigb_launch_prep(devs, g, 0, parity, st));
         b->launches += 2;
     }
     return LPBOX_OK;
+}
+
+// the early-fixing calls on a batch in the reference order: they would need batched rank passes (bigref_k_rank per fix); nothing changes
+int bigb_no_fixing() {
+    return lpbox_fail(LPBOX_E_UNSUPPORTED, "the early-fixing windows of a batch need the default order; this batch runs the reference summation order (lpbox_big_iterate_l2f per handle)");
 }
 
 std::vector<int> bigb_active(const lpbox_big_batch *b) {
@@ -1005,7 +1031,7 @@ int bigb_window(lpbox_big_batch *b, int iter_start, int iter_end, bool score_for
         }
     if (!b->inited) return lpbox_fail(LPBOX_E_STATE, "lpbox_big_batch_init has not been called");
     for (int k = 0; k < A; k++) {
-        CHK(bigb_member_ok(b->hs[act[k]], act[k], true));
+        CHK(bigb_member_ok(b->hs[act[k]], act[k], false, true));
         if (!b->hs[act[k]]->inited) return lpbox_fail(LPBOX_E_STATE, "problem %d of the batch: solve_init has not been called", act[k]);
     }
     if (score_form && scores) {
@@ -1158,13 +1184,14 @@ lpbox_big_batch_t *lpbox_big_batch_create(lpbox_big_t **handles, int count) {
     auto refuse = [](int) -> lpbox_big_batch * { return nullptr; };        // lpbox_fail has recorded status and text
     if (!handles || count <= 0) return refuse(lpbox_fail(LPBOX_E_BADARG, "empty batch"));
     for (int i = 0; i < count; i++) {                               // no device call
-        if (bigb_member_ok(handles[i], i) < 0) return nullptr;
+        if (bigb_member_ok(handles[i], i, handles[0] && handles[0]->ref) < 0) return nullptr;
         if (handles[i]->device != handles[0]->device) return refuse(lpbox_fail(LPBOX_E_BADARG, "problem %d of the batch lives on another device than problem 0", i));
         for (int k = 0; k < i; k++)
             if (handles[k] == handles[i]) return refuse(lpbox_fail(LPBOX_E_BADARG, "problem %d and problem %d of the batch are the same handle", k, i));
     }
     lpbox_big_batch *b = new lpbox_big_batch();
     b->hs.assign(handles, handles + count); b->B = count; b->device = handles[0]->device;
+    b->ref = handles[0]->ref;
     b->active.assign(count, 1); b->row_off.assign((size_t)count + 1, 0); b->pack_serial.assign(count, -1);
     if (const char *e = getenv("LPBOX_BIG_KMAX")) { int v = atoi(e); if (v >= 1 && v <= 1000) { b->kmax = v; b->adaptive = false; } }
     if (const char *e = getenv("LPBOX_BIG_KMARGIN")) b->rules.margin = std::max(0, atoi(e));
@@ -1188,17 +1215,18 @@ void lpbox_big_batch_destroy(lpbox_big_batch_t *b) {
 // lpbox_big_init on every member (a handful of launches once per solve), then the descriptors of all members in one device array
 int lpbox_big_batch_init(lpbox_big_batch_t *b) {
     if (!b) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
-    for (int i = 0; i < b->B; i++) CHK(bigb_member_ok(b->hs[i], i));
+    for (int i = 0; i < b->B; i++) CHK(bigb_member_ok(b->hs[i], i, b->ref));
     CHK(use_device(b->device));
     b->inited = false;
     for (int i = 0; i < b->B; i++) CHK(lpbox_big_init(b->hs[i]));
-    for (int i = 0; i < b->B; i++) CHK(bigb_member_ok(b->hs[i], i));           // folded reductions are decided by the upload
+    for (int i = 0; i < b->B; i++) CHK(bigb_member_ok(b->hs[i], i, b->ref));   // folded reductions are decided by the upload
     for (int i = 0; i < b->B; i++) HIPCHK(hipStreamSynchronize(b->hs[i]->stream));
     if (!b->stream) {
         HIPCHK(hipStreamCreate(&b->stream));
         HIPCHK(b->timer.create());
         HIPCHK(b->devs.alloc(b->B)); HIPCHK(b->dstates.alloc(b->B)); HIPCHK(b->par.alloc(b->B)); HIPCHK(b->counts.alloc(2 * (size_t)b->B));
         b->h_devs.resize(b->B); b->h_states.resize(b->B); b->h_par.resize(b->B);
+        if (b->ref) { HIPCHK(b->refs.alloc(b->B)); b->h_refs.resize(b->B); }
     }
     BigBatchGrid g{b->B, 0, 0, 0, 0};
     for (int i = 0; i < b->B; i++) {
@@ -1218,7 +1246,7 @@ int lpbox_big_batch_iterate(lpbox_big_batch_t *b, int iter_start, int iter_end, 
     if (!b) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
     if (!b->inited) return lpbox_fail(LPBOX_E_STATE, "lpbox_big_batch_init has not been called");
     for (int i = 0; i < b->B; i++) {
-        CHK(bigb_member_ok(b->hs[i], i));
+        CHK(bigb_member_ok(b->hs[i], i, b->ref));
         if (!b->hs[i]->inited) return lpbox_fail(LPBOX_E_STATE, "problem %d of the batch: solve_init has not been called", i);
     }
     CHK(use_device(b->device));
@@ -1233,6 +1261,13 @@ int lpbox_big_batch_iterate(lpbox_big_batch_t *b, int iter_start, int iter_end, 
     }
     for (int i = 0; i < b->B; i++) b->h_devs[i] = b->hs[i]->dev();
     HIPCHK(hipMemcpyAsync(b->devs.p, b->h_devs.data(), sizeof(BigDev) * (size_t)b->B, hipMemcpyHostToDevice, st));
+    if (b->ref) {
+        int kinds = 0;
+        for (int i = 0; i < b->B; i++) { b->h_refs[i] = *b->hs[i]->rf(); kinds |= b->h_refs[i].valued ? BIGREF_KIND_VALUED : BIGREF_KIND_UNIT; }
+        if (kinds != b->kinds) b->graphs.clear();                // the captured launches carry the y entries of the kinds they were captured with
+        b->kinds = kinds;
+        HIPCHK(hipMemcpyAsync(b->refs.p, b->h_refs.data(), sizeof(BigRef) * (size_t)b->B, hipMemcpyHostToDevice, st));
+    }
     HIPCHK(b->timer.start(st));
     const long long l0 = b->launches;
     b->launches += copies; b->parity_copies += copies;
@@ -1263,18 +1298,21 @@ int lpbox_big_batch_set_active(lpbox_big_batch_t *b, const unsigned char *active
 
 int lpbox_big_batch_iterate_l2f(lpbox_big_batch_t *b, int iter_start, int iter_end, const double *vecs, long vec_stride, const long *nums, int *rets) {
     if (!b) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
+    if (b->ref) return bigb_no_fixing();
     return bigb_window(b, iter_start, iter_end, false, vecs, vec_stride, nums, nullptr, 0.0, 0.0, 0, rets, nullptr);
 }
 
 int lpbox_big_batch_iterate_l2f_scores(lpbox_big_batch_t *b, int iter_start, int iter_end, const float *scores_dev, double hi, double lo, int min_fix,
                                        int *rets, int *fixed) {
     if (!b) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
+    if (b->ref) return bigb_no_fixing();
     return bigb_window(b, iter_start, iter_end, true, nullptr, 0, nullptr, scores_dev, hi, lo, min_fix, rets, fixed);
 }
 
 // the (rows x ws) windows of all active members, one after the other, in ONE buffer of the batch (one launch)
 int lpbox_big_batch_get_x_iters_device(lpbox_big_batch_t *b, int ws, void **dev_ptr, long *row_off) {
     if (!b) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
+    if (b->ref) return bigb_no_fixing();
     if (ws <= 0 || ws > LP_XITERS_COLS) return lpbox_fail(LPBOX_E_BADARG, "ws = %d outside (0,%d]", ws, LP_XITERS_COLS);
     if (!b->inited) return lpbox_fail(LPBOX_E_STATE, "lpbox_big_batch_init has not been called");
     const std::vector<int> act = bigb_active(b);
@@ -1334,6 +1372,8 @@ int lpbox_big_batch_get_scalar(lpbox_big_batch_t *b, const char *name, double *o
         {"grid_cols", (double)b->grid.cols}, {"grid_y", (double)b->grid.y}, {"grid_rows", (double)b->grid.rows}, {"grid_z4", (double)b->grid.z4},
         {"active", (double)std::count(b->active.begin(), b->active.end(), (uint8_t)1)}, {"fix_launches", (double)b->fix_launches},
         {"packs", (double)b->packs}, {"compact_chunk", (double)(BIG_CT * BIG_CE)},
+        {"order", b->ref ? (double)LPBOX_ORDER_REFERENCE : (double)LPBOX_ORDER_DEFAULT},
+        {"valued_members", (double)std::count_if(b->hs.begin(), b->hs.end(), [](const lpbox_big *h) { return h->valued; })}, {"walks", (double)b->walks},
     };
     for (auto &e : tab) if (!strcmp(e.n, name)) { *out = e.v; return LPBOX_OK; }
     return lpbox_fail(LPBOX_E_BADARG, "unknown scalar '%s'", name);

@@ -40,6 +40,12 @@ __device__ __forceinline__ void forward_state(const BigDev &d, int in, int out) 
     if (LEADER) d.st[out] = d.st[in];
 }
 
+// the extent of a problem's own launch (big_launch_*), per kernel: what a lockstep batch's entries (big_kb_*, bigref_kb_*) test blockIdx.x against
+__device__ __forceinline__ int ext_cols(const BigDev &d) { return d.G; }
+__device__ __forceinline__ int ext_y(const BigDev &d) { return d.G > d.Gl ? d.G : d.Gl; }
+__device__ __forceinline__ int ext_rows(const BigDev &d) { return d.P > 1 ? d.Glr : d.Gl; }
+__device__ __forceinline__ int ext_z4(const BigDev &d) { return d.Gl; }
+
 // Workgroup partials of NV values -> d.part; big_k_fin reduces them to d.red in a launch of its own.  Measured alternative: the
 // workgroup that arrives last (ticket counter, __threadfence before and after) reduces them inside the producing kernel -- 41
 // launches per iteration fewer, but 3.05 instead of 1.52 ms per iteration at n = 1e6: a device-scope fence per workgroup writes the

@@ -171,12 +171,6 @@ __global__ void __launch_bounds__(T) big_k_pcg_upd(BigDev d, int in, int out) { 
 __global__ void __launch_bounds__(T) big_k_post(BigDev d, int in, int out) { big_b_post(d, WgSums{}, in, out); }
 __global__ void __launch_bounds__(T) big_k_z4(BigDev d, int in, int out, int init_only) { big_b_z4(d, in, out, init_only); }
 
-// the extent of a problem's own launch (big_launch_*), per kernel
-__device__ __forceinline__ int ext_cols(const BigDev &d) { return d.G; }
-__device__ __forceinline__ int ext_y(const BigDev &d) { return d.G > d.Gl ? d.G : d.Gl; }
-__device__ __forceinline__ int ext_rows(const BigDev &d) { return d.P > 1 ? d.Glr : d.Gl; }
-__device__ __forceinline__ int ext_z4(const BigDev &d) { return d.Gl; }
-
 __global__ void big_kb_set_window(const BigDev *__restrict__ devs, int in, int out, int iter_start, int iter_end) { big_b_set_window(devs[blockIdx.y], in, out, iter_start, iter_end, 0); }
 __global__ void big_kb_resume(const BigDev *__restrict__ devs, int in, int out, int reset_pcg_max) { big_b_resume(devs[blockIdx.y], in, out, reset_pcg_max); }
 __global__ void __launch_bounds__(T) big_kb_prep(const BigDev *__restrict__ devs, int in, int out, int do_prep) { const BigDev &d = devs[blockIdx.y]; if ((int)blockIdx.x >= ext_cols(d)) return; big_b_prep(d, WgSums{}, in, out, do_prep); }
@@ -467,6 +461,7 @@ hipError_t bigb_enqueue_tail(const BigDev *devs, const BigBatchGrid &g, int *par
     BIGB_LAUNCH(big_kb_z4, g.z4);
     return hipGetLastError();
 }
+hipError_t bigb_launch_z4(const BigDev *devs, const BigBatchGrid &g, int *parity, hipStream_t s) { BIGB_LAUNCH(big_kb_z4, g.z4); return hipGetLastError(); }
 hipError_t bigb_enqueue_iterations(const BigDev *devs, const BigBatchGrid &g, int iters, int kmax, int *parity, hipStream_t s) {
     for (int it = 0; it < iters; it++) {
         BIGB_LAUNCH(big_kb_prep, g.cols, 1);

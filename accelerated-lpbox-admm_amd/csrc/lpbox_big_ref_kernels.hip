@@ -6,7 +6,9 @@
 //     (bigref_k_rank) and sums nothing; bigref_k_walk, in the place of big_k_fin, adds them up in Eigen's redux association and writes
 //     BigDev::red, which the consumers read as they do on the route with a reduction launch (BigDev::fold is off);
 //   * the entries of the bodies with that policy (bigref_k_*), and with it and VALUED (bigref_k_*_v): the stored values of E as factors
-//     and rho4_E_transpose per entry (r4v) instead of the scalar r4Et.
+//     and rho4_E_transpose per entry (r4v) instead of the scalar r4Et;
+//   * the same entries for a BATCH of problems in lockstep (bigref_kb_*, grid (X, B); lpbox_big_batch_* with every member in this order),
+//     unit and valued members side by side, with one walker per member (bigref_kb_walk), and their launch helpers (bigrefb_*).
 // Bodies that neither feed a reduction nor touch a value (y, rhs_cols, rows, fix3; z4 and the state kernels) have no staged unit entry:
 // the unit instance runs their default entries, which already sum every row and column by one lane in ascending order from +0.0.
 // The entries have external linkage: the launch helpers of both orders are in lpbox_big_kernels.hip.
@@ -89,7 +91,7 @@ __global__ void __launch_bounds__(T) bigref_k_rank(BigDev d, BigRef rf, int mode
 // LDS and stored to the other LDS buffer after it, so the dependent chain is the addition alone.  Lane v then combines
 // (p0a + p1a) + (p0b + p1b), the left-over pair and the final odd element; sizes 1-3 take the short branches.
 constexpr int WTILE = 1024, WROW = WTILE + 4, WU = WTILE / T;    // row pitch + 4: the chains of different values start on different banks
-__global__ void __launch_bounds__(T) bigref_k_walk(BigDev d, BigRef rf, int nv, int soff, int roff, int which, int sidx, int pcg) {
+__device__ __forceinline__ void bigref_b_walk(const BigDev &d, const BigRef &rf, int nv, int soff, int roff, int which, int sidx, int pcg) {
     __shared__ double tile[2][BIG_REF_MAXV][WROW];
     __shared__ double fin[BIG_REF_MAXV][4];
     if (sidx >= 0) {
@@ -154,6 +156,55 @@ __global__ void __launch_bounds__(T) bigref_k_walk(BigDev d, BigRef rf, int nv, 
         d.red[roff + lane] = res;
     }
 }
+__global__ void __launch_bounds__(T) bigref_k_walk(BigDev d, BigRef rf, int nv, int soff, int roff, int which, int sidx, int pcg) { bigref_b_walk(d, rf, nv, soff, roff, which, sidx, pcg); }
+
+// ---- a BATCH in lockstep (lpbox_big_batch_* with every member in the reference order), grid (X, B) as the
+// big_kb_* entries of lpbox_big_kernels.hip: row blockIdx.y runs member blockIdx.y's own body on devs[blockIdx.y] and refs[blockIdx.y]; a
+// workgroup at or beyond the member's own extent leaves first thing, before any barrier or store.  Unit and valued members share a
+// launch: ONE entry per phase with a branch on the member's `valued`, uniform over the workgroup, between the two instantiations the
+// member's solo chain picks between on the host -- for rhs_cols and rows that is (AtRank, valued) against the default entry's
+// (WgSums, unit) body, which reads d.red because the reference order runs with BigDev::fold off.  The exception is y: with both
+// instantiations in one entry it needs 75 VGPRs, one occupancy step below bigref_k_y_v (71: 7 waves per SIMD), so y has one entry per
+// kind (72 VGPRs each) over the same grid, each leaving first thing on members of the other kind; the host skips the launch of a kind
+// the batch does not have.  No body is touched.
+// The walker: one workgroup per member, grid (1, B).  nv, the offsets, which, sidx and pcg are the same for every member of a lockstep
+// launch; the early-out, the size (the member's own cnt[which]) and n_loc are the member's own.
+#define KB_MEMBER(ext)                                \
+    const BigDev &d = devs[blockIdx.y];               \
+    if ((int)blockIdx.x >= ext(d)) return;            \
+    const BigRef &rf = refs[blockIdx.y]
+__global__ void __launch_bounds__(T) bigref_kb_walk(const BigDev *__restrict__ devs, const BigRef *__restrict__ refs, int nv, int soff, int roff, int which, int sidx, int pcg) {
+    bigref_b_walk(devs[blockIdx.y], refs[blockIdx.y], nv, soff, roff, which, sidx, pcg);
+}
+__global__ void __launch_bounds__(T) bigref_kb_prep(const BigDev *__restrict__ devs, const BigRef *__restrict__ refs, int in, int out, int do_prep) { KB_MEMBER(ext_cols); big_b_prep(d, AtRank{rf}, in, out, do_prep); }
+__global__ void __launch_bounds__(T) bigref_kb_y_u(const BigDev *__restrict__ devs, const BigRef *__restrict__ refs, int in, int out) {
+    KB_MEMBER(ext_y);
+    if (rf.valued) return;
+    big_b_y<WgSums, false>(d, WgSums{}, in, out);
+}
+__global__ void __launch_bounds__(T) bigref_kb_y_v(const BigDev *__restrict__ devs, const BigRef *__restrict__ refs, int in, int out) {
+    KB_MEMBER(ext_y);
+    if (!rf.valued) return;
+    big_b_y<AtRank, true>(d, AtRank{rf}, in, out);
+}
+__global__ void __launch_bounds__(T) bigref_kb_rhs_cols(const BigDev *__restrict__ devs, const BigRef *__restrict__ refs, int in, int out) {
+    KB_MEMBER(ext_cols);
+    if (rf.valued) big_b_rhs_cols<AtRank, true>(d, AtRank{rf}, in, out); else big_b_rhs_cols<WgSums, false>(d, WgSums{}, in, out);
+}
+__global__ void __launch_bounds__(T) bigref_kb_rows(const BigDev *__restrict__ devs, const BigRef *__restrict__ refs, int in, int out, int mode) {
+    KB_MEMBER(ext_rows);
+    if (rf.valued) big_b_rows<AtRank, true>(d, AtRank{rf}, in, out, mode); else big_b_rows<WgSums, false>(d, WgSums{}, in, out, mode);
+}
+__global__ void __launch_bounds__(T) bigref_kb_resid(const BigDev *__restrict__ devs, const BigRef *__restrict__ refs, int in, int out) {
+    KB_MEMBER(ext_cols);
+    if (rf.valued) big_b_resid<AtRank, true>(d, AtRank{rf}, in, out); else big_b_resid<AtRank, false>(d, AtRank{rf}, in, out);
+}
+__global__ void __launch_bounds__(T) bigref_kb_pcg_cols(const BigDev *__restrict__ devs, const BigRef *__restrict__ refs, int in, int out) {
+    KB_MEMBER(ext_cols);
+    if (rf.valued) big_b_pcg_cols<AtRank, true>(d, AtRank{rf}, in, out); else big_b_pcg_cols<AtRank, false>(d, AtRank{rf}, in, out);
+}
+__global__ void __launch_bounds__(T) bigref_kb_pcg_upd(const BigDev *__restrict__ devs, const BigRef *__restrict__ refs, int in, int out) { KB_MEMBER(ext_cols); big_b_pcg_upd(d, AtRank{rf}, in, out); }
+__global__ void __launch_bounds__(T) bigref_kb_post(const BigDev *__restrict__ devs, const BigRef *__restrict__ refs, int in, int out) { KB_MEMBER(ext_cols); big_b_post(d, AtRank{rf}, in, out); }
 
 }  // namespace
 
@@ -183,5 +234,56 @@ hipError_t bigref_launch_walk(const BigDev &d, const BigRef &rf, int nv, int pha
     if (nv < 1 || nv > BIG_REF_MAXV) return hipErrorInvalidValue;
     hipLaunchKernelGGL(bigref_k_walk, dim3(1), dim3(T), 0, s, d, rf, nv, big_ref_stage_off(phase), phase * BIG_NPART, which, sidx,
                        (phase == BIG_PH_C || phase == BIG_PH_D) ? 1 : 0);
+    return hipGetLastError();
+}
+
+// ---- the lockstep batch in the reference order: the launches of enqueue_iteration (lpbox_big_capi.hip) with a BigRef, launch for launch ----
+#define BIGREFB_LAUNCH(kernel, X, ...)                                                                                 \
+    do {                                                                                                               \
+        hipLaunchKernelGGL(kernel, dim3(X, g.B), dim3(T), 0, s, devs, refs, *parity, *parity ^ 1, ##__VA_ARGS__);      \
+        *parity ^= 1;                                                                                                  \
+    } while (0)
+// a walk flips no parity; its sidx is the parity where it is enqueued, i.e. the state its producer has just written
+#define BIGREFB_WALK(nv, phase)                                                                                                         \
+    hipLaunchKernelGGL(bigref_kb_walk, dim3(1, g.B), dim3(T), 0, s, devs, refs, nv, big_ref_stage_off(phase), (phase) * BIG_NPART, 0, *parity, \
+                       ((phase) == BIG_PH_C || (phase) == BIG_PH_D) ? 1 : 0)
+
+hipError_t bigrefb_launch_prep(const BigDev *devs, const BigRef *refs, const BigBatchGrid &g, int do_prep, int *parity, hipStream_t s) {
+    BIGREFB_LAUNCH(bigref_kb_prep, g.cols, do_prep);
+    return hipGetLastError();
+}
+hipError_t bigrefb_enqueue_pcg(const BigDev *devs, const BigRef *refs, const BigBatchGrid &g, int pairs, int *parity, hipStream_t s) {
+    for (int k = 0; k < pairs; k++) {
+        BIGREFB_LAUNCH(bigref_kb_rows, g.rows, 1);
+        BIGREFB_LAUNCH(bigref_kb_pcg_cols, g.cols);
+        BIGREFB_WALK(1, BIG_PH_C);
+        BIGREFB_LAUNCH(bigref_kb_pcg_upd, g.cols);
+        BIGREFB_WALK(2, BIG_PH_D);
+    }
+    return hipGetLastError();
+}
+hipError_t bigrefb_enqueue_tail(const BigDev *devs, const BigRef *refs, const BigBatchGrid &g, int *parity, hipStream_t s) {
+    BIGREFB_LAUNCH(bigref_kb_post, g.cols);
+    BIGREFB_WALK(5, BIG_PH_E);
+    BIGREFB_LAUNCH(bigref_kb_rows, g.rows, 0);
+    return bigb_launch_z4(devs, g, parity, s);
+}
+hipError_t bigrefb_enqueue_iterations(const BigDev *devs, const BigRef *refs, const BigBatchGrid &g, int kinds, int iters, int kmax, int *parity, hipStream_t s) {
+    if (!(kinds & (BIGREF_KIND_UNIT | BIGREF_KIND_VALUED))) return hipErrorInvalidValue;
+    for (int it = 0; it < iters; it++) {
+        BIGREFB_LAUNCH(bigref_kb_prep, g.cols, 1);
+        BIGREFB_WALK(1, BIG_PH_A);
+        // y: one launch per kind of member in the batch, both on the same (in, out) -- every member's state moves once
+        if (kinds & BIGREF_KIND_UNIT) hipLaunchKernelGGL(bigref_kb_y_u, dim3(g.y, g.B), dim3(T), 0, s, devs, refs, *parity, *parity ^ 1);
+        if (kinds & BIGREF_KIND_VALUED) hipLaunchKernelGGL(bigref_kb_y_v, dim3(g.y, g.B), dim3(T), 0, s, devs, refs, *parity, *parity ^ 1);
+        *parity ^= 1;
+        BIGREFB_LAUNCH(bigref_kb_rhs_cols, g.cols);
+        BIGREFB_LAUNCH(bigref_kb_rows, g.rows, 0);
+        BIGREFB_LAUNCH(bigref_kb_resid, g.cols);
+        BIGREFB_WALK(3, BIG_PH_B);
+        hipError_t e = bigrefb_enqueue_pcg(devs, refs, g, kmax, parity, s);
+        if (e == hipSuccess) e = bigrefb_enqueue_tail(devs, refs, g, parity, s);
+        if (e != hipSuccess) return e;
+    }
     return hipGetLastError();
 }

@@ -224,11 +224,16 @@ class BigLpBatch:
     """A batch of large-route instances through ONE launch chain in lockstep (lpbox_big_batch_* in include/lpbox_hip.h): plain windows
     of all members at once, each member on its own control state, bit for bit what `BigLp.solve_iter` gives it alone.
 
-    members: problem dicts (a `BigLp` is built for each and closed with the batch) and / or `BigLp` objects (borrowed: one rank, no
-    transport, default order, reference PCG).  `batch[k]` is member k's `BigLp`: its getters, and a `solve_iter` of its own, work between
-    the batch's windows."""
+    members: problem dicts (a `BigLp(m, device=device, order=order)` is built for each and closed with the batch) and / or `BigLp`
+    objects (borrowed: one rank, no transport, reference PCG; they keep their own order).  All members run in one summation order, member
+    0's: the library refuses a mismatch.  order="reference": per member the bits of `BigLp(order="reference")`, i.e. the oracle's in
+    ORDER_EIGEN; only then may a problem carry `vals`, and the early-fixing calls are refused.  `batch[k]` is member k's `BigLp`: its
+    getters, and a `solve_iter` of its own, work between the batch's windows."""
 
-    def __init__(self, members, device=0):
+    def __init__(self, members, device=0, order="default"):
+        if order not in ("default", "reference"):
+            raise ValueError("order must be 'default' or 'reference'")
+        self.order = order
         members = list(members) if members is not None else []
         if not members:
             raise ValueError("BigLpBatch needs at least one problem")
@@ -237,7 +242,24 @@ class BigLpBatch:
                 raise ValueError(f"member {k} is neither a BigLp nor a problem dict (n, l, colptr, rowidx, b)")
         self._L = _lib.load()
         self._own = [not isinstance(m, BigLp) for m in members]
-        self.solvers = [m if isinstance(m, BigLp) else BigLp(m, device=device) for m in members]
+        self.solvers = []
+        try:
+            for m in members:
+                if isinstance(m, BigLp):
+                    self.solvers.append(m)
+                    continue
+                s = BigLp.__new__(BigLp)
+                try:
+                    s.__init__(m, device=device, order=order)
+                except Exception:                            # BigLp's own error (e.g. stored values in the default order) ...
+                    s.close()                                # ... and its handle does not wait for the garbage collector
+                    raise
+                self.solvers.append(s)
+        except Exception:                                    # no handle of ours stays open
+            for s, own in zip(self.solvers, self._own):
+                if own:
+                    s.close()
+            raise
         arr = (C.c_void_p * len(self.solvers))(*[s._h for s in self.solvers])
         h = self._L.lpbox_big_batch_create(arr, len(self.solvers))
         if not h:
@@ -357,9 +379,9 @@ class BigLpBatch:
         return rets, fixed
 
 
-def solve_many(problems, max_iters=20000, device=0):
-    """Solve every problem to its own stop in one lockstep chain: (rets, binary solutions, objectives cal_Obj())."""
-    batch = BigLpBatch(problems, device=device)
+def solve_many(problems, max_iters=20000, device=0, order="default"):
+    """Solve every problem to its own stop in one lockstep chain: (rets, binary solutions, objectives cal_Obj()).  order: as BigLpBatch."""
+    batch = BigLpBatch(problems, device=device, order=order)
     try:
         batch.solve_init()
         rets = batch.solve_iter(0, int(max_iters))

@@ -386,8 +386,14 @@ int lpbox_big_get_scalar(lpbox_big_t *h, const char *name, double *out);        
  * launch on a grid (workgroups, members).  Each member keeps its own control state and falls through once it has stopped; per member
  * the results are those of lpbox_big_iterate on its own, bit for bit.  The handles are borrowed: they stay ordinary handles, their
  * getters and a later lpbox_big_iterate of their own work as if the windows had been their own.  A member must run on one rank without
- * a transport, in the default summation order with the reference's PCG, with folded reductions (at most 1024 workgroups), without
- * recording and without fixed variables (LPBOX_E_UNSUPPORTED otherwise); all members on one device, no handle twice (LPBOX_E_BADARG).
+ * a transport, with the reference's PCG, without recording and without fixed variables (LPBOX_E_UNSUPPORTED otherwise); all members on
+ * one device, no handle twice (LPBOX_E_BADARG).
+ * Summation order: ALL members run in ONE order, the order of member 0 (lpbox_big_set_order before its problem); a member in the other
+ * order is refused at create, init and every iterate (LPBOX_E_UNSUPPORTED, naming the member).  Default order: folded reductions (at
+ * most 1024 workgroups) and unit values.  Reference order (LPBOX_ORDER_REFERENCE): per member the bits of lpbox_big_iterate in that
+ * order, i.e. the oracle's in ORDER_EIGEN; only there may members carry stored values (lpbox_big_set_problem_vals), unit and valued
+ * members mixed freely.  The early-fixing calls below need the default order: on a batch in the reference order they return
+ * LPBOX_E_UNSUPPORTED and change nothing.
  * A refused call leaves the batch and its members as they were.  LPBOX_BIG_KMAX / LPBOX_BIG_KMARGIN are read at create;
  * LPBOX_BIG_BATCH_GRAPH=1 replays captured iterations instead of eager launches. */
 typedef struct lpbox_big_batch lpbox_big_batch_t;
@@ -425,7 +431,8 @@ int lpbox_big_batch_iterate_l2f_scores(lpbox_big_batch_t *b, int iter_start, int
                                        double hi, double lo, int min_fix, int *rets, int *fixed);
 /* "count", "launches", "kernel_ms", "kmax", "graph", "parity_copies", "grid_cols" / "grid_y" / "grid_rows" / "grid_z4" (the x-extents
  * of the launches), "pcg_resumes_<i>" (member i); "active" (members), "fix_launches" (launches of the fix prologue), "packs",
- * "compact_chunk" (entries per pass of the live-list compaction) */
+ * "compact_chunk" (entries per pass of the live-list compaction); "order" (0 default, 1 reference), "valued_members" (members with
+ * stored values other than 1), "walks" (walker launches so far: reference order only; "launches" counts them too) */
 int lpbox_big_batch_get_scalar(lpbox_big_batch_t *b, const char *name, double *out);
 
 /* ---- generic constrained binary QP: min x'Ax + b'x  s.t.  Cx = d, Ex <= f, x in {0,1}^n -----------------------------------------

@@ -75,8 +75,10 @@ void lp_plan_layout(const LpProblemView &P, const LpGeometry &geo, const LpLayou
 // rs_ptr / rs_col = CSR of E (columns ascending), cs_ptr / cs_row = CSC (rows ascending).
 void lp_plan_identity_layout(const LpProblemView &P, const LpGeometry &geo, LpInstanceLayout *out);
 // Direct x-update: rows with pairwise disjoint columns (D) are inverted in closed form, the rest (G) through a dense |G| x |G| inverse.
-// Greedy choice of D: rows by ascending length (the XOR "dummy item" rows of an auction are short and mutually disjoint).
-// gidx_of_row[r] = dense index of row r among the G rows, -1 = D row; returns |G|.
+// Greedy choice of D: rows by ascending length (the XOR "dummy item" rows of an auction are short and mutually disjoint), rows of equal
+// length by ascending row index; a row is D if none of its columns belongs to a D row chosen before it (an empty row always is).
+// gidx_of_row[r] = dense index of row r among the G rows, numbered in row order, -1 = D row; returns |G|.
+// (tests/direct_cases.py::greedy_split restates the rule; tests/test_direct_edges.py compares the two element for element.)
 int lp_plan_direct_rows(const LpProblemView &P, std::vector<int> *gidx_of_row);
 // Class of one wavefront of the 512 x 1 kernel's PCG loop from the list lengths of its lanes: chunks of two register entries of its
 // longest row, own-column and helper list (what build_list's wlen gives), and whether some lane's list goes beyond the registers.

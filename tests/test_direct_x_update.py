@@ -5,27 +5,10 @@ x-update by Jacobi-PCG to 1e-3 (LPcpp:251-335, :894).  What can be pinned on the
 import numpy as np
 import pytest
 
+from direct_cases import greedy_split
 from helpers import lp_instances
 from oracle import oracle as O
 from oracle.lpbox_numpy import NumpyLpBox
-
-
-def greedy_split(I, ascending=True):
-    """Rows with pairwise disjoint columns -> -1, the rest get dense indices (what lpbox_set_x_update does on the host)."""
-    n, l, cp, ri = I["n"], I["l"], I["colptr"], I["rowidx"]
-    rows = [[] for _ in range(l)]
-    for j in range(n):
-        for e in range(cp[j], cp[j + 1]):
-            rows[ri[e]].append(j)
-    order = sorted(range(l), key=lambda r: len(rows[r]) if ascending else -len(rows[r]))
-    used, is_d = np.zeros(n, bool), np.zeros(l, bool)
-    for r in order:
-        if not used[rows[r]].any():
-            is_d[r] = True
-            used[rows[r]] = True
-    g = -np.ones(l, np.int32)
-    g[~is_d] = np.arange((~is_d).sum())
-    return g
 
 
 def direct_oracle(I, rows=None):

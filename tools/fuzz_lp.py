@@ -1,15 +1,23 @@
 """Differential fuzz of the LP window kernel against the oracle in the kernel's order: random instances with structures the auction
 generator rarely makes -- empty rows, one-entry columns, one row shared by most columns, duplicate columns, sizes that are not multiples
-of anything -- plain and early-fixing windows, every iterate bit for bit.  usage: python tools/fuzz_lp.py [count=120] [seed=0]"""
+of anything -- plain and early-fixing windows, every iterate bit for bit.  usage: python tools/fuzz_lp.py [count=120] [seed=0] [direct]
+With `direct` the cases have n <= 512 and run the opt-in direct x-update (set_x_update("direct")) against the
+oracle's mirror of it; a batch the mode refuses (more than 128 rows of E sharing columns, or more LDS than a CU has) is reported as such."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, 'accelerated-lpbox-admm_amd'), os.path.join(ROOT, 'tests')]
 import numpy as np
 
 
-def random_instance(rs):
+SIZES = [3, 5, 17, 31, 64, 65, 100, 257, 511, 513, 700, 1200, 2048]
+DIRECT_NMAX = 512                                       # the direct x-update is built for the one-slot geometry
+
+
+def random_instance(rs, nmax=None):
+    """nmax: draw n from the sizes <= nmax only (the direct x-update's cases); None: the stream of draws every earlier seed produced."""
     kind = rs.randint(0, 6)
-    n = int(rs.choice([3, 5, 17, 31, 64, 65, 100, 257, 511, 513, 700, 1200, 2048])) if kind != 5 else int(rs.randint(3, 400))
+    sizes = SIZES if nmax is None else [s for s in SIZES if s <= nmax]
+    n = int(rs.choice(sizes)) if kind != 5 else int(rs.randint(3, 400))
     l = max(2, int(n * rs.uniform(0.1, 0.9)))
     cols = []
     heavy = rs.randint(0, l) if kind in (1, 4) else -1
@@ -33,18 +41,27 @@ def random_instance(rs):
 
 
 def main():
-    from helpers import bits_equal, oracle_like, scripted_fix_vec
-    from lpbox_hip.lp import PyLPboxADMMsolver
+    from helpers import bits_equal, oracle_for, oracle_like, scripted_fix_vec
+    from lpbox_hip.lp import LpboxError, PyLPboxADMMsolver
     count = int(sys.argv[1]) if len(sys.argv) > 1 else 120
     rs = np.random.RandomState(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
-    bad = 0
+    direct = len(sys.argv) > 3 and sys.argv[3] == "direct"
+    bad = refused = 0
     for t in range(count):
-        I, kind = random_instance(rs)
-        g = PyLPboxADMMsolver(0); g.set_problem(I["n"], I["l"], I["colptr"], I["rowidx"], I["b"]); g.solve_init()
+        I, kind = random_instance(rs, DIRECT_NMAX if direct else None)
+        g = PyLPboxADMMsolver(0); g.set_problem(I["n"], I["l"], I["colptr"], I["rowidx"], I["b"])
+        if direct:
+            try:
+                g.batch.set_x_update("direct")
+            except LpboxError as err:
+                print("case %3d kind %d n %4d l %4d nnz %5d: refused (%s)" % (t, kind, I["n"], I["l"], len(I["rowidx"]), err), flush=True)
+                refused += 1
+                continue
+        g.solve_init()
         if getattr(g, "large", False):                  # handed to the large-instance path (index sets beyond a CU's LDS): another oracle order,
             print("case %3d kind %d n %4d l %4d nnz %5d: large-instance route, skipped here" % (t, kind, I["n"], I["l"], len(I["rowidx"])), flush=True)
             continue                                    # covered by tests/test_dropin_large_gpu.py
-        o = oracle_like(g, I)
+        o = oracle_for(g.batch, 0, I, x_update="direct", direct_rows=g.batch.direct_rows(0)) if direct else oracle_like(g, I)
         ok = True
         vec, num = np.zeros(I["n"]), 0
         for w in range(2):
@@ -58,7 +75,7 @@ def main():
             ok = g.solve_iter(120, 400) == o.solve_iter(120, 400) and bits_equal(g.batch.debug_vec("z4"), o.vec("z4"))
         print("case %3d kind %d n %4d l %4d nnz %5d: %s" % (t, kind, I["n"], I["l"], len(I["rowidx"]), "ok" if ok else "MISMATCH"), flush=True)
         bad += not ok
-    print("fuzz: %d of %d cases differ" % (bad, count))
+    print("fuzz: %d of %d cases differ%s" % (bad, count, ", %d refused by the direct mode" % refused if direct else ""))
     return 1 if bad else 0
 
 

@@ -1326,6 +1326,30 @@ int lpbox_debug_block_sum(int threads, int nv, int stage, int groups, int rounds
     return LPBOX_OK;
 }
 
+int lpbox_debug_handover(int form, int nv, int l_lo, int l_hi, int groups, int rounds, const int *pos, const double *v0, double *last, double *totals) {
+    if (!pos || !v0 || !last || !totals || groups <= 0 || groups > 1024 || rounds <= 0 || rounds > 100000)
+        return lpbox_fail(LPBOX_E_BADARG, "lpbox_debug_handover: bad argument");
+    if (lpbox_device_count() < 1) return lpbox_fail(LPBOX_E_NODEVICE, "no HIP device");
+    HIPCHK(hipSetDevice(g_device));
+    const size_t T = 512, ntot = (size_t)groups * rounds * (nv == 2 ? 2 : 1);
+    DevBuf<int> dpos;                                                            // freed on every return path
+    DevBuf<double> dv0, dlast, dtot;
+    HIPCHK(dpos.alloc(12 * T));
+    HIPCHK(dv0.alloc(T));
+    HIPCHK(dlast.alloc(groups * T));
+    HIPCHK(dtot.alloc(ntot));
+    HIPCHK(hipMemcpy(dpos.p, pos, 12 * T * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dv0.p, v0, T * sizeof(double), hipMemcpyHostToDevice));
+    hipError_t e = lp_launch_debug_handover(form, nv, l_lo, l_hi, groups, rounds, dpos.p, dv0.p, dlast.p, dtot.p, nullptr);
+    if (e == hipErrorInvalidConfiguration)
+        return lpbox_fail(LPBOX_E_BADARG, "lpbox_debug_handover: no kernel for form %d, %d values, list lengths %d / %d", form, nv, l_lo, l_hi);
+    HIPCHK(e);
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(last, dlast.p, groups * T * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(totals, dtot.p, ntot * sizeof(double), hipMemcpyDeviceToHost));
+    return LPBOX_OK;
+}
+
 // ---- segmentation flavour (SEG pxd = Segmentation/Segmentation/cython/src/LPboxADMMsolver.pxd) ----
 static int seg_handle(lpbox_t *h) {
     if (!valid_handle(h)) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");

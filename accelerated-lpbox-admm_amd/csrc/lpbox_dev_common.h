@@ -94,6 +94,35 @@ __device__ __forceinline__ int wave_max_int(int v) {
     return __builtin_amdgcn_readfirstlane(v);
 }
 
+// ------------------------------------------------------------------------------------------------
+// workgroup barriers
+// ------------------------------------------------------------------------------------------------
+// An LDS hand-over between the waves of a workgroup: a bare s_barrier between two compiler-only memory barriers.  __syncthreads() is a
+// workgroup fence over every address space, so the compiler puts s_waitcnt lgkmcnt(0) in front of its s_barrier: each wave waits for
+// the LDS to acknowledge its ds_write before it signals arrival.  The two asm statements emit no instruction; they keep the compiler
+// from moving an LDS access across the s_barrier, so ds_write / s_barrier / ds_read stay in program order and the wave arrives at the
+// barrier with its write still in flight.
+// Contract (the caller's to keep; DESIGN.md section 5, "LDS hand-overs"):
+//   * both sides of the call touch LDS only -- there is no global or scratch access whose order against these LDS accesses matters
+//     (the LDS counter is what orders LDS against the other memories, and it is not drained here);
+//   * every wave of the workgroup runs on one CU, whose LDS executes the LDS instructions of all its waves in one order: a ds_read
+//     issued behind the barrier follows every ds_write issued in front of it, and a ds_write behind it every ds_read in front of it
+//     (tests/test_lds_handover_gpu.py stresses exactly this);
+//   * the call stands in workgroup-uniform control flow, one for one where a __syncthreads() would stand.
+__device__ __forceinline__ void lds_handover() {
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+}
+constexpr int RED_BAR_SYNC = 0;        // __syncthreads(): the default of every caller
+constexpr int RED_BAR_HANDOVER = 1;    // lds_handover(): the caller keeps its contract for everything around the block_sum
+template <int BAR>
+__device__ __forceinline__ void wg_barrier() {
+    static_assert(BAR == RED_BAR_SYNC || BAR == RED_BAR_HANDOVER, "barrier form");
+    if constexpr (BAR == RED_BAR_HANDOVER) lds_handover();
+    else __syncthreads();
+}
+
 constexpr int RED_MAXV = 6;    // values reduced together
 constexpr int RED_MAXW = 16;   // waves per workgroup
 
@@ -147,8 +176,8 @@ __device__ __forceinline__ void wave_partials_store(const double *v, double *buf
 // Sum NV per-thread partials over the workgroup; every thread receives the totals.  Wave partials go through LDS and
 // are combined by a second butterfly (lane i reads partial i mod W; balanced tree over the wave index), i.e. ONE LDS
 // round trip instead of W dependent reads.  `red` is a ping-pong scratch (2 * RED_MAXV * RED_MAXW doubles, 16-byte aligned): a thread
-// can run at most one block_sum ahead of the slowest one.
-template <int T, int NV, int STAGE = RED_STAGE_BCAST>
+// can run at most one block_sum ahead of the slowest one.  BAR: the form of the barrier between the store and the reads (wg_barrier).
+template <int T, int NV, int STAGE = RED_STAGE_BCAST, int BAR = RED_BAR_SYNC>
 __device__ __forceinline__ void block_sum(double (&v)[NV], double *red, int &parity) {
     constexpr int W = T / 64;
     static_assert(W == 1 || W == 2 || W == 4 || W == 8 || W == 16, "waves per workgroup");
@@ -162,7 +191,7 @@ __device__ __forceinline__ void block_sum(double (&v)[NV], double *red, int &par
     if constexpr (STAGE != RED_STAGE_BCAST) {
         static_assert(W == 8 && (STAGE == RED_STAGE_PAIRS || STAGE == RED_STAGE_PAIRS_LOW), "built for eight waves");
         wave_partials_store<NV, STAGE == RED_STAGE_PAIRS_LOW>(v, buf, lane, w);
-        __syncthreads();
+        wg_barrier<BAR>();
         double2 t[NV];
 #pragma unroll
         for (int k = 0; k < NV; k++) t[k] = *(const double2 *)(buf + k * RED_MAXW + 2 * (lane & 3));
@@ -194,7 +223,7 @@ __device__ __forceinline__ void block_sum(double (&v)[NV], double *red, int &par
             for (int k = 0; k < 2; k++) if (lane == scatter_lane(2, k)) buf[(4 + k) * RED_MAXW + w] = sc2;
         } else static_assert(NV <= 4, "at most six values");
     }
-    __syncthreads();
+    wg_barrier<BAR>();
     if constexpr (W >= 16) {
         // 16 waves (128-register budget): lane i takes the partial of wave i mod 16 and the row of 16 lanes runs the balanced tree
         // over the wave index on DPP -- the same association as the register version below, NV instead of NV * W live values

@@ -89,6 +89,9 @@ hipError_t lp_launch_window(const LpBatchDev &bd, int T, int EPT, size_t lds, in
                             hipStream_t s, bool direct = false, bool log = false);
 // lpbox_debug_block_sum: block_sum<T, NV, stage> `rounds` times in `groups` workgroups; hipErrorInvalidConfiguration = not compiled
 hipError_t lp_launch_debug_block_sum(int T, int NV, int stage, int groups, int rounds, const double *in, double *out, hipStream_t s);
+// lpbox_debug_handover: the LDS hand-over stress kernel, form 0 = __syncthreads(), 1 = lds_handover(); hipErrorInvalidConfiguration = not compiled
+hipError_t lp_launch_debug_handover(int form, int NV, int l_lo, int l_hi, int groups, int rounds, const int *pos, const double *v0,
+                                    double *last, double *totals, hipStream_t s);
 // 512 x 1 kernel: PCG loops compiled per wave class (false: diagnostic builds, other geometries) and the class rule's list capacities
 bool lp_pcg_specialised(int T, int EPT);
 void lp_pcg_list_caps(int *rows, int *cols, int *help);

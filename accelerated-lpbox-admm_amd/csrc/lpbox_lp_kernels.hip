@@ -93,6 +93,14 @@ namespace {
 #ifndef LPBOX_LP_MPDIRECT
 #define LPBOX_LP_MPDIRECT 1
 #endif
+// LDS hand-overs without a drain of the LDS counter in front of the barrier (lds_handover, lpbox_dev_common.h; DESIGN.md section 5, "LDS
+// hand-overs"), in the same kernel only and switched the same way (make variant NAME=x EXTRA=-DLPBOX_LP_HANDOVER_PCG=0 restores the
+// parent's text): the four barriers of a PCG iteration -- behind p, behind r4 q, inside block_sum<1> and block_sum<2>.  Between them the
+// kernel touches LDS only.  Every other barrier keeps __syncthreads(): the staging of the index sets, the prologue and the fix path have a
+// global access on one side, and the three of the outer phases gained nothing measurable.
+#ifndef LPBOX_LP_HANDOVER_PCG
+#define LPBOX_LP_HANDOVER_PCG 1
+#endif
 
 // ------------------------------------------------------------------------------------------------
 // LDS carve-up shared by the launcher (size) and the kernel (pointers)
@@ -576,6 +584,8 @@ __global__ void __launch_bounds__(T) lp_window_kernel(LpBatchDev bd, int iter_st
                      : lp_lean_stream(T, EPT, DIRECT, LOG, LPBOX_LP_REDLOW) ? RED_STAGE_PAIRS_LOW : lp_red_stage(T, EPT);
     constexpr bool SCALAR_LOOP = lp_pcg_scalar_loop(T, EPT, DIRECT, LOG), SPEC = lp_pcg_spec_geometry(T, EPT, DIRECT, LOG);
     constexpr bool FUSED = lp_outer_fused(T, EPT, DIRECT, LOG);
+    // barrier form of the PCG iteration's four hand-overs: between them the kernel touches LDS only
+    constexpr int BP = lp_lean_stream(T, EPT, DIRECT, LOG, LPBOX_LP_HANDOVER_PCG) ? RED_BAR_HANDOVER : RED_BAR_SYNC;
     // A test on a value that came out of block_sum is the same in every lane, which the compiler cannot see: it builds the PCG loop as a
     // divergent one (iteration counter in a vector register, exec-mask save / restore behind both reductions).  Going through the lane
     // mask (v_cmp into a scalar pair, s_cmp_lg_u64) states the uniformity.  All lanes of a wave are active wherever this is used.
@@ -1192,7 +1202,7 @@ __global__ void __launch_bounds__(T) lp_window_kernel(LpBatchDev bd, int iter_st
                         while (k_it < LP_PCG_MAXITERS) {                  // :296
 #pragma unroll
                             for (int s = 0; s < EPT; s++) gx[s * T + tid] = (DEADZ || live[s]) ? p[s] : 0.0;
-                            __syncthreads();
+                            wg_barrier<BP>();
                             {
                                 double q[EPT];
                                 if constexpr (RK >= 0) {
@@ -1207,7 +1217,7 @@ __global__ void __launch_bounds__(T) lp_window_kernel(LpBatchDev bd, int iter_st
                                 // instead of one per entry of E in the gather below; fl(acc + fl(r4 * q_i)) is unchanged bit for bit
                                 for (int s = 0; s < EPT; s++) if (rvalid(s)) gl[3 * rgl(s)] = r4 * q[s];
                             }
-                            __syncthreads();
+                            wg_barrier<BP>();
                             double tmp[EPT];
                             double p1[1] = {0.0};
                             if constexpr (CK >= 0) {                      // entries already carry the factor r4
@@ -1236,7 +1246,7 @@ __global__ void __launch_bounds__(T) lp_window_kernel(LpBatchDev bd, int iter_st
                                 tmp[s] = Mp;
                                 p1[0] = p1[0] + ((DEADZ || live[s]) ? p[s] * tmp[s] : 0.0);
                             }
-                            block_sum<T, 1, RS>(p1, red, parity);
+                            block_sum<T, 1, RS, BP>(p1, red, parity);
                             const double alpha = absNew / p1[0];          // :300
                             if (uni(alpha < 0)) { pcg_fail = true; break; }   // :301
                             double p2[2] = {0.0, 0.0};
@@ -1249,7 +1259,7 @@ __global__ void __launch_bounds__(T) lp_window_kernel(LpBatchDev bd, int iter_st
                                 p2[0] = p2[0] + (live[s] ? r[s] * r[s] : 0.0);   // :305
                                 p2[1] = p2[1] + ((DEADZ || live[s]) ? r[s] * z[s] : 0.0);   // :317
                             }
-                            block_sum<T, 2, RS>(p2, red, parity);
+                            block_sum<T, 2, RS, BP>(p2, red, parity);
                             residualNorm2 = p2[0];
                             if (uni(residualNorm2 < threshold)) { k_it++; break; }    // :309-312
                             const double absOld = absNew;
@@ -1648,7 +1658,74 @@ __global__ void __launch_bounds__(T) debug_block_sum_kernel(const double *in, do
     }
 }
 
+// lpbox_debug_handover: the LDS hand-over of the 512 x 1 window kernel on its own, many rounds on ONE n-vector and one reduction scratch,
+// so that a read that overtakes a write (or a write that overtakes a read) of another wave changes every value after it.  One round:
+//   vec[t] = v;  barrier;  s = vec[pos[0][t]] + ... + vec[pos[L - 1][t]] in this order (L = LLO in waves 0-3, LHI in waves 4-7; positions
+//   in registers);  barrier;  block_sum<NV> of (s) resp. (s, v);  v = frac(s * 1.37 + total0 * 0.113 [+ total1 * 0.0271] + t / 1024).
+// BAR: both barriers and the one inside block_sum are __syncthreads() (RED_BAR_SYNC) or lds_handover() (RED_BAR_HANDOVER).
+// Out: every thread's last v, and per round the totals thread 0 received (a register value stored to memory nothing here reads).
+template <int L>
+__device__ __forceinline__ double debug_handover_gather(const double *vec, const unsigned (&a)[12]) {
+    double g[L];
+#pragma unroll
+    for (int q = 0; q < L; q++) g[q] = vec[a[q]];
+    double s = g[0];
+#pragma unroll
+    for (int q = 1; q < L; q++) s = s + g[q];
+    return s;
+}
+template <int NV, int LLO, int LHI, int BAR>
+__global__ void __launch_bounds__(512) debug_handover_kernel(const int *pos, const double *v0, int rounds, double *last, double *totals) {
+    constexpr int T = 512;
+    __shared__ __attribute__((aligned(16))) double vec[T];
+    __shared__ __attribute__((aligned(16))) double red[2 * RED_MAXV * RED_MAXW];
+    const int tid = threadIdx.x;
+    const bool lower = __builtin_amdgcn_readfirstlane(tid) < T / 2;      // waves 0-3 (wave-uniform: the branch below is a scalar one)
+    unsigned a[12];
+#pragma unroll
+    for (int q = 0; q < 12; q++) a[q] = (unsigned)pos[q * T + tid] & (T - 1);
+    const double ct = (double)tid * (1.0 / 1024.0);
+    double v = v0[tid];
+    int parity = 0;
+    double *tot_out = totals + (size_t)blockIdx.x * rounds * NV;
+    for (int r = 0; r < rounds; r++) {
+        vec[tid] = v;
+        wg_barrier<BAR>();
+        double s;
+        if (lower) s = debug_handover_gather<LLO>(vec, a);
+        else s = debug_handover_gather<LHI>(vec, a);
+        wg_barrier<BAR>();
+        double p[NV];
+        p[0] = s;
+        if constexpr (NV == 2) p[1] = v;
+        block_sum<T, NV, RED_STAGE_PAIRS_LOW, BAR>(p, red, parity);
+        double u = s * 1.37 + p[0] * 0.113;
+        if constexpr (NV == 2) u = u + p[1] * 0.0271;
+        u = u + ct;
+        v = u - floor(u);
+        if (tid == 0) {
+#pragma unroll
+            for (int k = 0; k < NV; k++) tot_out[(size_t)r * NV + k] = p[k];
+        }
+    }
+    last[(size_t)blockIdx.x * T + tid] = v;
+}
+
 }  // namespace
+
+hipError_t lp_launch_debug_handover(int form, int NV, int l_lo, int l_hi, int groups, int rounds, const int *pos, const double *v0,
+                                    double *last, double *totals, hipStream_t s) {
+#define CALL_HO(VV, LO, HI)                                                                                                                      \
+    if (NV == VV && l_lo == LO && l_hi == HI) {                                                                                                  \
+        if (form == RED_BAR_SYNC) hipLaunchKernelGGL((debug_handover_kernel<VV, LO, HI, RED_BAR_SYNC>), dim3(groups), dim3(512), 0, s, pos, v0, rounds, last, totals); \
+        else hipLaunchKernelGGL((debug_handover_kernel<VV, LO, HI, RED_BAR_HANDOVER>), dim3(groups), dim3(512), 0, s, pos, v0, rounds, last, totals); \
+        return hipGetLastError();                                                                                                                \
+    }
+    if (form != RED_BAR_SYNC && form != RED_BAR_HANDOVER) return hipErrorInvalidConfiguration;
+    CALL_HO(1, 1, 1) CALL_HO(1, 2, 2) CALL_HO(1, 12, 12) CALL_HO(1, 12, 1) CALL_HO(1, 1, 12) CALL_HO(2, 12, 12)
+#undef CALL_HO
+    return hipErrorInvalidConfiguration;
+}
 
 hipError_t lp_launch_debug_block_sum(int T, int NV, int stage, int groups, int rounds, const double *in, double *out, hipStream_t s) {
 #define CALL_DBG(TT, VV, SS)                                                                                             \

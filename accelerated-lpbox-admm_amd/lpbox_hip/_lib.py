@@ -95,6 +95,7 @@ SYMBOLS = {
     "lpbox_debug_get_scalar": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.POINTER(C.c_double)]),
     "lpbox_debug_get_lp_table": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, _ip, C.c_int]),
     "lpbox_debug_block_sum": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp]),
+    "lpbox_debug_handover": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _dp, _dp, _dp]),
     "lpbox_set_log": (C.c_int, [C.c_void_p, C.c_int]),
     "lpbox_get_log": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int]),
     "lpbox_big_create": (C.c_void_p, [C.c_int, C.c_int, C.c_int]),

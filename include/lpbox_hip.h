@@ -312,6 +312,14 @@ int lpbox_debug_get_lp_table(lpbox_t *h, int idx, const char *name, int *out, in
  * workgroup g received.  stage: 0 = the default second stage (threads 256 / 512 / 1024), 1 = the one the 512-thread window kernel
  * runs (threads 512); nv = 1, 2, 3 or 6.  Anything else: LPBOX_E_BADARG. */
 int lpbox_debug_block_sum(int threads, int nv, int stage, int groups, int rounds, const double *in, double *out);
+/* Test entry for the LDS hand-over of the 512-thread window kernel (no solver state, used by no product path): `groups` workgroups of 512
+ * threads run `rounds` rounds on ONE 512-vector in LDS.  A round: thread t writes v to element t; barrier; s = the sum, in order, of the
+ * elements pos[q * 512 + t], q = 0 .. L - 1 (L = l_lo in wavefronts 0-3, l_hi in 4-7; pos: 12 x 512 entries in 0 .. 511); barrier; the
+ * workgroup reduction of (s) (nv = 1) or (s, v) (nv = 2) with the window kernel's second stage; v = frac(s * 1.37 + total0 * 0.113
+ * [+ total1 * 0.0271] + t / 1024).  v0[t]: the first v.  form: 0 = every barrier is __syncthreads(), 1 = the bare hand-over barrier.
+ * last[g * 512 + t]: thread t's v after the last round; totals[(g * rounds + r) * nv + k]: the totals of round r.  Built for
+ * (nv, l_lo, l_hi) = (1, 1, 1), (1, 2, 2), (1, 12, 12), (1, 12, 1), (1, 1, 12), (2, 12, 12).  Anything else: LPBOX_E_BADARG. */
+int lpbox_debug_handover(int form, int nv, int l_lo, int l_hi, int groups, int rounds, const int *pos, const double *v0, double *last, double *totals);
 
 /* ---- LARGE single LP, variable-sharded over ranks (BASELINE config 5; no reference counterpart: the reference is one
  * process).  Rank r holds the columns [c0, c0+n_loc) of E (all l rows), its slice of b, and the full f; the l-vectors are

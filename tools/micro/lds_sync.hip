@@ -55,7 +55,63 @@ __global__ void __launch_bounds__(512) k(double *out, unsigned long long *cyc, c
     if (tid == 0) cyc[blockIdx.x] = t1 - t0;
 }
 
-#define RUN(MODE, L, name, per)                                                                                         \
+// The two LDS hand-overs of the solver's PCG iteration as dependent chains, with the barrier in both forms ("LDS
+// hand-overs"): BARE = false is __syncthreads() (s_waitcnt lgkmcnt(0) in front of s_barrier), BARE = true the bare s_barrier between
+// compiler-only memory barriers (lds_handover() of csrc/lpbox_dev_common.h).  One hand-over per round on ping-pong buffers; the value a
+// lane writes in round r + 1 depends on what it read in round r.
+//   KIND 0 "vector": every lane writes an f64, barrier, reads eight gathered entries and adds them in order
+//   KIND 1 "block_sum": lane 0 of each wave writes an f64, barrier, every lane does one ds_read_b128 and adds the pair
+template <bool BARE> __device__ __forceinline__ void bar() {
+    if constexpr (BARE) { asm volatile("" ::: "memory"); __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); }
+    else __syncthreads();
+}
+template <int KIND, bool BARE>
+__global__ void __launch_bounds__(512) kh(double *out, unsigned long long *cyc, const unsigned short *idx, int iters, double seed) {
+    __shared__ __attribute__((aligned(16))) double buf[2][512];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    double v = seed + tid * 1e-3;
+    unsigned a[8];
+    for (int q = 0; q < 8; q++) a[q] = idx[(blockIdx.x % 8) * 512 * 32 + q * 512 + tid] & 511;
+    buf[0][tid] = 0.0; buf[1][tid] = 0.0;
+    __syncthreads();
+    unsigned long long t0 = __builtin_amdgcn_s_memtime();
+    for (int it = 0; it < iters; it++) {
+        double *b = buf[it & 1];
+        if (KIND == 0) {
+            b[tid] = v;
+            bar<BARE>();
+            double g[8];
+#pragma unroll
+            for (int q = 0; q < 8; q++) g[q] = b[a[q]];
+            double acc = g[0];
+#pragma unroll
+            for (int q = 1; q < 8; q++) acc = acc + g[q];
+            v = acc * 0.125;
+        } else {
+            if (lane == 0) b[w] = v;
+            bar<BARE>();
+            const double2 t = *(const double2 *)(b + 2 * (lane & 3));
+            v = (t.x + t.y) * 0.5 + 1e-3;
+        }
+    }
+    unsigned long long t1 = __builtin_amdgcn_s_memtime();
+    out[blockIdx.x * 512 + tid] = v;
+    if (tid == 0) cyc[blockIdx.x] = t1 - t0;
+}
+
+#define RUNH(KIND, BARE, name)                                                                                          \
+    {                                                                                                                   \
+        hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);                                                    \
+        kh<KIND, BARE><<<256, 512>>>(out, cyc, idx, 100, 1.25);                                                         \
+        hipEventRecord(e0); kh<KIND, BARE><<<256, 512>>>(out, cyc, idx, iters, 1.25); hipEventRecord(e1);               \
+        hipDeviceSynchronize(); float ms; hipEventElapsedTime(&ms, e0, e1);                                             \
+        unsigned long long h[256]; hipMemcpy(h, cyc, sizeof(h), hipMemcpyDeviceToHost);                                 \
+        double s = 0; for (int i = 0; i < 256; i++) s += h[i];                                                          \
+        printf("%-46s %8.1f cycles  %7.1f ns  (clock %.2f GHz)\n", name, s / 256 / iters, 1e6 * ms / iters,             \
+               s / 256 / (ms * 1e6));                                                                                   \
+    }
+
+#define RUN(MODE, L, name, per)                                                                                        \
     {                                                                                                                   \
         hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);                                                    \
         k<MODE, L><<<256, 512>>>(out, cyc, idx, 100, 1.25);                                                             \
@@ -85,5 +141,12 @@ int main() {
     RUN(5, 12, "frame + random gather L=12 + add chain", 1)
     RUN(5, 16, "frame + random gather L=16 + add chain", 1)
     RUN(5, 24, "frame + random gather L=24 + add chain", 1)
+    // per hand-over, both barrier forms, each twice in alternation (the difference of a pair is the drain)
+    for (int rep = 0; rep < 2; rep++) {
+        RUNH(0, false, "vector hand-over L=8, __syncthreads()")
+        RUNH(0, true, "vector hand-over L=8, bare s_barrier")
+        RUNH(1, false, "block_sum hand-over b128, __syncthreads()")
+        RUNH(1, true, "block_sum hand-over b128, bare s_barrier")
+    }
     return 0;
 }

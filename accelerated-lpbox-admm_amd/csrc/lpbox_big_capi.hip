@@ -1,8 +1,8 @@
 // lpbox_big_capi.hip -- host side + C-ABI of the LARGE-instance LP path (lpbox_big_* in include/lpbox_hip.h):
 // one LP, variable-sharded over ranks (one process per GPU).  The library launches the kernels; where the algorithm needs a
 // sum over all variables it calls the caller-supplied all-reduce (RCCL through torch.distributed in lpbox_hip/big.py) on
-// the same HIP stream.  With one rank no collective is issued.  The host loop of the launch chain is chain_run of lpbox_host.h with the
-// rules of lpbox_chain.h (CHAIN_RULES_BIG); the graph cache, the device buffer, the timer and the error-check macros are there too.
+// the same HIP stream.  With one rank no collective is issued.  The host loops of the launch chains are chain_run (one handle) and
+// chain_run_lockstep (a batch) of lpbox_host.h with the rules of lpbox_chain.h (CHAIN_RULES_BIG); the graph cache, the device buffer, the timer and the error-check macros are there too.
 #include "../../include/lpbox_hip.h"
 #include "lpbox_big.h"
 #include "lpbox_capi_internal.h"
@@ -848,9 +848,8 @@ struct lpbox_big_batch {
     std::vector<lpbox_big *> hs;
     int B = 0, device = 0;
     bool inited = false;
-    ChainRules rules = CHAIN_RULES_BIG;
-    int kmax = CHAIN_RULES_BIG.kmax_start;
-    bool adaptive = true, use_graph = false;
+    ChainLockstep chain{CHAIN_RULES_BIG, CHAIN_RULES_BIG.kmax_start};   // rules, kmax (carried over the windows), adaptive
+    bool use_graph = false;
     hipStream_t stream = nullptr;
     StreamTimer timer;
     GraphCache graphs;                              // two iterations per (kmax, start parity); the grid extents never change
@@ -896,103 +895,53 @@ int bigb_member_ok(const lpbox_big *h, int i, bool ref_batch, bool allow_fixed =
     return LPBOX_OK;
 }
 
-int bigb_collect(lpbox_big_batch *b, const BigBatchGrid &g, int parity) {
-    HIPCHK(bigb_collect_states(b->devs.p, g, parity, b->dstates.p, b->stream));
-    HIPCHK(hipMemcpyAsync(b->h_states.data(), b->dstates.p, sizeof(BigState) * (size_t)g.B, hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-    return LPBOX_OK;
-}
-
-// The lockstep chain up to iter_end (the window already set); the loop of batch_run_chain in lpbox_seg_capi.hip with this route's
-// launches.  The chain runs the A members whose descriptors stand in b->devs (act[k]: the member behind descriptor k; nullptr: all, in
-// order); the grid extents stay the maxima over all members.  b->h_states[k] receives the final states; resumes[k] is raised for every
-// member whose own state showed the halt at a resume.
-int bigb_run_chain(lpbox_big_batch *b, int A, const int *act, int iter_end, int *parity, long long *resumes) {
-    const ChainRules &rules = b->rules;
-    const BigDev *devs = b->devs.p;
-    const BigRef *refs = b->refs.p;
-    const bool ref = b->ref;                                        // reference order: the solo chain's launches with a BigRef, launch for launch
-    BigBatchGrid g = b->grid;
-    g.B = A;
-    if (b->graph_B != A) { b->graphs.clear(); b->graph_B = A; }     // the captured launches carry the member count
-    hipStream_t st = b->stream;
-    std::vector<int> resumed(A, 0);                                 // per member: resumes since one of its outer iterations last completed
-    for (;;) {
-        CHK(bigb_collect(b, g, *parity));
-        bool more = false, any_run = false;
-        int remaining = 0, vote = 0, pcg_k = 0;
-        for (int i = 0; i < A; i++) {
-            const BigState &h = b->h_states[i];
-            if (h.halt == BIG_HALT_PCG_MORE) {
-                if (++resumed[i] > rules.resume_limit())
-                    return lpbox_fail(LPBOX_E_STATE, "problem %d of the batch, iteration %d: the PCG is still halted at k = %d after %d resumes in a row", act ? act[i] : i, h.iter, h.pcg_k, resumed[i] - 1);
-                resumes[i]++; more = true; pcg_k = std::max(pcg_k, h.pcg_k);
-                continue;
-            }
-            resumed[i] = 0;
-            if (h.halt != BIG_HALT_NONE) continue;
-            const int rem = iter_end - h.iter;
-            if (rem <= 0 && !h.have_prev) continue;
-            any_run = true; remaining = std::max(remaining, rem);
-            vote = std::max(vote, chain_pcg_vote(rules, b->kmax, chain_view(h)));
-        }
-        if (more) {                                                 // some PCG ran out of launch groups: resume it (the others fall through)
-            HIPCHK(bigb_launch_resume(devs, g, 0, parity, st));
-            if (ref) {
-                HIPCHK(bigrefb_enqueue_pcg(devs, refs, g, CHAIN_PAIRS_PER_RESUME, parity, st));
-                HIPCHK(bigrefb_enqueue_tail(devs, refs, g, parity, st));
-                b->launches += 5 + 5 * CHAIN_PAIRS_PER_RESUME; b->walks += 1 + 2 * CHAIN_PAIRS_PER_RESUME;
-            } else {
-                HIPCHK(bigb_enqueue_pcg(devs, g, CHAIN_PAIRS_PER_RESUME, parity, st));
-                HIPCHK(bigb_enqueue_tail(devs, g, parity, st));
-                b->launches += 4 + 3 * CHAIN_PAIRS_PER_RESUME;
-            }
-            if (b->adaptive) b->kmax = chain_kmax_after_halt(rules, b->kmax, pcg_k);
-            continue;
-        }
-        if (!any_run) break;
-        if (b->adaptive) b->kmax = chain_kmax_for_vote(rules, vote);
-        const int kmax = b->kmax;
-        HIPCHK(bigb_launch_resume(devs, g, 1, parity, st));
-        int batch = chain_batch_iters(rules, remaining);
-        const int per_graph = rules.iters_per_graph;
-        auto enqueue = [&](int n) {
-            if (ref) {
-                HIPCHK(bigrefb_enqueue_iterations(devs, refs, g, b->kinds, n, kmax, parity, st));
-                b->launches += (long long)n * (11 + 5 * kmax + (b->kinds == (BIGREF_KIND_UNIT | BIGREF_KIND_VALUED) ? 1 : 0));
-            } else {
-                HIPCHK(bigb_enqueue_iterations(devs, g, n, kmax, parity, st));
-                b->launches += (long long)n * (8 + 3 * kmax);
-            }
-            return (int)LPBOX_OK;
-        };
-        if (ref) b->walks += (long long)batch * (3 + 2 * kmax);         // replayed or eager: every iteration of the batch has them
-        if (b->use_graph && batch >= per_graph) {
-            ChainIo io{st, *parity, b->launches, b->collectives, b->use_graph, true};
-            const GraphCache::Entry *ge = nullptr;
-            if (b->graphs.get(kmax, io, [&] { return enqueue(per_graph); }, &ge) < 0) {     // go on with eager launches for good
-                b->use_graph = false;
-                (void)hipGetLastError();
-            } else {
-                for (; batch >= per_graph; batch -= per_graph) { HIPCHK(hipGraphLaunch(ge->exec, st)); b->launches += ge->launches; }
-            }
-        }
-        if (batch > 0) CHK(enqueue(batch));
-        if (ref) HIPCHK(bigrefb_launch_prep(devs, refs, g, 0, parity, st)); else HIPCHK(bigb_launch_prep(devs, g, 0, parity, st));
-        b->launches += 2;
+// The launches of the lockstep chain (chain_run_lockstep) over the g.B members whose descriptors stand in devs; the grid extents stay the
+// maxima over all members.  Reference order: the solo chain's launches with a BigRef, launch for launch.  b->h_states[k]: the final states.
+struct BigBatchOps {
+    lpbox_big_batch *b; const BigDev *devs; const BigRef *refs; hipStream_t st; BigBatchGrid g; int &parity;
+    int collect(ChainView *v) {
+        HIPCHK(bigb_collect_states(devs, g, parity, b->dstates.p, st));
+        HIPCHK(hipMemcpyAsync(b->h_states.data(), b->dstates.p, sizeof(BigState) * (size_t)g.B, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (int i = 0; i < g.B; i++) v[i] = chain_view(b->h_states[i]);
+        return LPBOX_OK;
     }
-    return LPBOX_OK;
+    int resume_pcg() {
+        HIPCHK(bigb_launch_resume(devs, g, 0, &parity, st));
+        if (b->ref) { HIPCHK(bigrefb_enqueue_pcg(devs, refs, g, CHAIN_PAIRS_PER_RESUME, &parity, st)); HIPCHK(bigrefb_enqueue_tail(devs, refs, g, &parity, st)); }
+        else { HIPCHK(bigb_enqueue_pcg(devs, g, CHAIN_PAIRS_PER_RESUME, &parity, st)); HIPCHK(bigb_enqueue_tail(devs, g, &parity, st)); }
+        b->launches += b->ref ? 5 + 5 * CHAIN_PAIRS_PER_RESUME : 4 + 3 * CHAIN_PAIRS_PER_RESUME;
+        b->walks += b->ref ? 1 + 2 * CHAIN_PAIRS_PER_RESUME : 0;
+        return LPBOX_OK;
+    }
+    int batch_head(int iters, int kmax) {                           // the walks of the batch here: replayed or eager, every iteration has them
+        HIPCHK(bigb_launch_resume(devs, g, 1, &parity, st));
+        b->launches += 1; b->walks += b->ref ? (long long)iters * (3 + 2 * kmax) : 0;
+        return LPBOX_OK;
+    }
+    int enqueue(int n, int kmax) {
+        if (b->ref) HIPCHK(bigrefb_enqueue_iterations(devs, refs, g, b->kinds, n, kmax, &parity, st)); else HIPCHK(bigb_enqueue_iterations(devs, g, n, kmax, &parity, st));
+        b->launches += (long long)n * (b->ref ? 11 + 5 * kmax + (b->kinds == (BIGREF_KIND_UNIT | BIGREF_KIND_VALUED) ? 1 : 0) : 8 + 3 * kmax);
+        return LPBOX_OK;
+    }
+    int finalize() {
+        if (b->ref) HIPCHK(bigrefb_launch_prep(devs, refs, g, 0, &parity, st)); else HIPCHK(bigb_launch_prep(devs, g, 0, &parity, st));
+        b->launches += 1;
+        return LPBOX_OK;
+    }
+};
+
+// the chain up to iter_end (the window already set) over the A members behind b->devs (act[k]: the member behind descriptor k; nullptr: all)
+int bigb_chain(lpbox_big_batch *b, int A, const int *act, int iter_end, int *parity, long long *resumes) {
+    BigBatchGrid g = b->grid; g.B = A;
+    if (b->graph_B != A) { b->graphs.clear(); b->graph_B = A; }     // the captured launches carry the member count
+    return chain_run_lockstep(b->chain, A, act, b->graphs, ChainIo{b->stream, *parity, b->launches, b->collectives, b->use_graph, true}, iter_end,
+                              resumes, BigBatchOps{b, b->devs.p, b->refs.p, b->stream, g, *parity});
 }
 
 // the early-fixing calls on a batch in the reference order: they would need batched rank passes (bigref_k_rank per fix); nothing changes
 int bigb_no_fixing() {
     return lpbox_fail(LPBOX_E_UNSUPPORTED, "the early-fixing windows of a batch need the default order; this batch runs the reference summation order (lpbox_big_iterate_l2f per handle)");
-}
-
-std::vector<int> bigb_active(const lpbox_big_batch *b) {
-    std::vector<int> act;
-    for (int i = 0; i < b->B; i++) if (b->active[i]) act.push_back(i);
-    return act;
 }
 
 // descriptors (b->h_devs) and records (b->h_par) of the first A slots -> device, one copy each
@@ -1012,7 +961,7 @@ int bigb_window(lpbox_big_batch *b, int iter_start, int iter_end, bool score_for
                 const float *scores, double hi, double lo, int min_fix, int *rets, int *fixed) {
     const int ws = iter_end - iter_start;
     if (ws > LP_XITERS_COLS) return lpbox_fail(LPBOX_E_BADARG, "window of %d iterations exceeds the %d columns of x_iters (LPcpp:1113)", ws, LP_XITERS_COLS);
-    const std::vector<int> act = bigb_active(b);
+    const std::vector<int> act = active_members(b->active);
     const int A = (int)act.size();
     std::vector<long> live(A), num(A, 0);
     for (int k = 0; k < A; k++) { const lpbox_big *h = b->hs[act[k]]; live[k] = h && h->inited ? h->n_live_glob : (h ? h->n_glob : 0); }
@@ -1152,7 +1101,7 @@ int bigb_window(lpbox_big_batch *b, int iter_start, int iter_end, bool score_for
     if (max_stage > 0) { HIPCHK(bigb_launch_clear_xhist(b->devs.p, g, max_stage, st)); b->launches++; }     // x_iters = Zero (:1113)
 
     std::vector<long long> resumes(A, 0);
-    const int rc = bigb_run_chain(b, A, act.data(), iter_end, &parity, resumes.data());
+    const int rc = bigb_chain(b, A, act.data(), iter_end, &parity, resumes.data());
     double ms = 0.0;
     const hipError_t e = b->timer.stop_sync(st, &ms);
     if (rc < 0) return rc;
@@ -1193,8 +1142,8 @@ lpbox_big_batch_t *lpbox_big_batch_create(lpbox_big_t **handles, int count) {
     b->hs.assign(handles, handles + count); b->B = count; b->device = handles[0]->device;
     b->ref = handles[0]->ref;
     b->active.assign(count, 1); b->row_off.assign((size_t)count + 1, 0); b->pack_serial.assign(count, -1);
-    if (const char *e = getenv("LPBOX_BIG_KMAX")) { int v = atoi(e); if (v >= 1 && v <= 1000) { b->kmax = v; b->adaptive = false; } }
-    if (const char *e = getenv("LPBOX_BIG_KMARGIN")) b->rules.margin = std::max(0, atoi(e));
+    if (const char *e = getenv("LPBOX_BIG_KMAX")) { int v = atoi(e); if (v >= 1 && v <= 1000) { b->chain.kmax = v; b->chain.adaptive = false; } }
+    if (const char *e = getenv("LPBOX_BIG_KMARGIN")) b->chain.rules.margin = std::max(0, atoi(e));
     if (const char *e = getenv("LPBOX_BIG_BATCH_GRAPH")) b->use_graph = atoi(e) != 0;     // replay captured iterations instead of eager launches
     return b;
 }
@@ -1274,7 +1223,7 @@ int lpbox_big_batch_iterate(lpbox_big_batch_t *b, int iter_start, int iter_end, 
     HIPCHK(bigb_launch_set_window(b->devs.p, b->grid, iter_start, iter_end, &parity, st));
     b->launches++;
     std::vector<long long> resumes(b->B, 0);
-    const int rc = bigb_run_chain(b, b->B, nullptr, iter_end, &parity, resumes.data());
+    const int rc = bigb_chain(b, b->B, nullptr, iter_end, &parity, resumes.data());
     double ms = 0.0;
     const hipError_t e = b->timer.stop_sync(st, &ms);
     if (rc < 0) return rc;
@@ -1315,7 +1264,7 @@ int lpbox_big_batch_get_x_iters_device(lpbox_big_batch_t *b, int ws, void **dev_
     if (b->ref) return bigb_no_fixing();
     if (ws <= 0 || ws > LP_XITERS_COLS) return lpbox_fail(LPBOX_E_BADARG, "ws = %d outside (0,%d]", ws, LP_XITERS_COLS);
     if (!b->inited) return lpbox_fail(LPBOX_E_STATE, "lpbox_big_batch_init has not been called");
-    const std::vector<int> act = bigb_active(b);
+    const std::vector<int> act = active_members(b->active);
     const int A = (int)act.size();
     for (int k = 0; k < A; k++) {
         const lpbox_big *h = b->hs[act[k]];
@@ -1367,7 +1316,7 @@ int lpbox_big_batch_get_scalar(lpbox_big_batch_t *b, const char *name, double *o
         return LPBOX_OK;
     }
     struct { const char *n; double v; } tab[] = {
-        {"count", (double)b->B}, {"launches", (double)b->launches}, {"kernel_ms", b->kernel_ms}, {"kmax", (double)b->kmax},
+        {"count", (double)b->B}, {"launches", (double)b->launches}, {"kernel_ms", b->kernel_ms}, {"kmax", (double)b->chain.kmax},
         {"graph", b->use_graph ? 1.0 : 0.0}, {"parity_copies", (double)b->parity_copies},
         {"grid_cols", (double)b->grid.cols}, {"grid_y", (double)b->grid.y}, {"grid_rows", (double)b->grid.rows}, {"grid_z4", (double)b->grid.z4},
         {"active", (double)std::count(b->active.begin(), b->active.end(), (uint8_t)1)}, {"fix_launches", (double)b->fix_launches},

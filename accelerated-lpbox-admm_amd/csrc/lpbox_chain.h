@@ -2,9 +2,11 @@
 // builds it, tests/chain_check.cpp runs it under the host sanitizers).  A chain enqueues kmax PCG launch groups per outer iteration; the
 // kernels fall through once a PCG has converged, a PCG that needs more halts the chain (halt = 3) and the host resumes it with 16 more
 // groups.  The segmentation (lpbox_seg_capi.hip), generic BQP (lpbox_gen_capi.hip) and large-LP (lpbox_big_capi.hip) front ends differ
-// in the numbers of ChainRules and in their launches, nothing else; the driver that issues the launches is chain_run in lpbox_host.h.
+// in the numbers of ChainRules and in their launches, nothing else.  ChainController decides for the chain of one problem, ChainLockstep
+// for the one chain a batch shares; the drivers that issue the launches are chain_run and chain_run_lockstep in lpbox_host.h.
 #pragma once
 #include <algorithm>
+#include <vector>
 
 constexpr int CHAIN_HALT_NONE = 0, CHAIN_HALT_PCG_MORE = 3;   // SEG_/GEN_/BIG_HALT_* agree on these two (static_asserts at the front ends)
 constexpr int CHAIN_PAIRS_PER_RESUME = 16;                    // PCG launch groups a resume enqueues
@@ -86,6 +88,44 @@ struct ChainController {
         if (remaining <= 0 && !v.have_prev) return ChainStep{ChainStep::DONE, kmax, 0, 0};
         if (adaptive) kmax = chain_kmax_before_batch(rules, kmax, v);
         if (adaptive && v.outer_total > 0 && v.pcg_max == 0) kept++;
+        return ChainStep{ChainStep::BATCH, kmax, chain_batch_iters(rules, remaining), 0};
+    }
+};
+
+// A members advanced in lockstep by ONE chain (a batch): one launch count for all, every member on its own control state.  A halt of
+// any member resumes the chain (the others fall through); halted members neither vote for kmax nor count towards the iterations left; a
+// batch runs as far as the member that has most left, at the largest vote.  A = 1, kmax inside [floor, cap]: ChainController's steps.
+struct ChainLockstep {
+    ChainRules rules;
+    int kmax;
+    bool adaptive;               // false: kmax is forced and never moves
+    std::vector<int> resumed;    // per member: resumes since one of its outer iterations last completed
+    int stuck_slot = -1, stuck_iter = 0, stuck_pcg_k = 0;   // STUCK: the member that did not come out of its halt, and where it stands
+
+    ChainLockstep(const ChainRules &r, int kmax_, bool adaptive_ = true) : rules(r), kmax(kmax_), adaptive(adaptive_) {}
+    void begin(int A) { resumed.assign((size_t)A, 0); }              // a host loop starts (a window, a solve) over A members
+
+    // v[A]: the members' control states; resumes[A] is raised for every member whose own state shows the halt at a resume
+    ChainStep next(const ChainView *v, int iter_end, long long *resumes) {
+        bool more = false, any_run = false;
+        int remaining = 0, vote = 0, pcg_k = 0;
+        for (int i = 0; i < (int)resumed.size(); i++) {
+            if (v[i].halt == CHAIN_HALT_PCG_MORE) {
+                if (++resumed[i] <= rules.resume_limit()) { resumes[i]++; more = true; pcg_k = std::max(pcg_k, v[i].pcg_k); continue; }
+                stuck_slot = i; stuck_iter = v[i].iter; stuck_pcg_k = v[i].pcg_k;
+                return ChainStep{ChainStep::STUCK, kmax, 0, resumed[i] - 1};
+            }
+            resumed[i] = 0;
+            if (v[i].halt != CHAIN_HALT_NONE) continue;
+            const int rem = iter_end - v[i].iter;
+            if (rem <= 0 && !v[i].have_prev) continue;
+            any_run = true; remaining = std::max(remaining, rem);
+            vote = std::max(vote, chain_pcg_vote(rules, kmax, v[i]));
+        }
+        if (more && adaptive) kmax = chain_kmax_after_halt(rules, kmax, pcg_k);      // some PCG ran out of launch groups
+        if (more) return ChainStep{ChainStep::RESUME, kmax, 0, 0};
+        if (!any_run) return ChainStep{ChainStep::DONE, kmax, 0, 0};
+        if (adaptive) kmax = chain_kmax_for_vote(rules, vote);
         return ChainStep{ChainStep::BATCH, kmax, chain_batch_iters(rules, remaining), 0};
     }
 };

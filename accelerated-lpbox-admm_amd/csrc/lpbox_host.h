@@ -1,6 +1,6 @@
 // lpbox_host.h -- the HIP-side plumbing every host file (*_capi.hip) shares: the error-check macros, use_device, the owning device
-// buffer, the stream timer, the cache of captured graphs and the driver of a single-problem launch chain (its decisions are those of
-// lpbox_chain.h).  Not part of the C-ABI.
+// buffer, the stream timer, the cache of captured graphs and the drivers of a single-problem launch chain and of the lockstep chain of
+// a batch (their decisions are those of lpbox_chain.h).  Not part of the C-ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -136,6 +136,26 @@ struct GraphCache {
     }
 };
 
+// `batch` outer iterations at kmax: replays of the graph of per_graph iterations while that many are left, the rest eagerly;
+// enqueue(n) issues n iterations.  A capture that fails makes the chain go on with eager launches for good.
+template <class Enqueue>
+int chain_enqueue_batch(GraphCache &graphs, ChainIo &io, int per_graph, int kmax, int batch, Enqueue &&enqueue) {
+    if (io.use_graph && io.can_capture && batch >= per_graph) {
+        const GraphCache::Entry *g = nullptr;
+        if (graphs.get(kmax, io, [&] { return enqueue(per_graph); }, &g) < 0) {
+            io.use_graph = false;
+            (void)hipGetLastError();
+        } else {
+            for (; batch >= per_graph; batch -= per_graph) {
+                HIPCHK(hipGraphLaunch(g->exec, io.stream));
+                io.launches += g->launches; io.collectives += g->collectives;
+            }
+        }
+    }
+    if (batch > 0) CHK(enqueue(batch));
+    return LPBOX_OK;
+}
+
 // The host loop of a single-problem chain up to iter_end: read the control state, resume a PCG that ran out of launch groups, re-pick
 // kmax, enqueue a batch as graph replays plus an eager tail, finalise.  Ops supplies the front end's launches:
 //   int read_state(ChainView &v)   copy the control state back (synchronises)
@@ -155,21 +175,36 @@ int chain_run(ChainController &ctl, GraphCache &graphs, ChainIo io, int iter_end
             return lpbox_fail(LPBOX_E_STATE, "iteration %d: the PCG is still halted at k = %d after %d resumes in a row", v.iter, v.pcg_k, step.resumes);
         if (step.kind == ChainStep::RESUME) { CHK(ops.resume_pcg()); continue; }
         CHK(ops.batch_head());
-        int batch = step.iters;
-        const int per_graph = ctl.rules.iters_per_graph;
-        if (io.use_graph && io.can_capture && batch >= per_graph) {
-            const GraphCache::Entry *g = nullptr;
-            if (graphs.get(step.kmax, io, [&] { return ops.enqueue(per_graph); }, &g) < 0) {     // go on with eager launches for good
-                io.use_graph = false;
-                (void)hipGetLastError();
-            } else {
-                for (; batch >= per_graph; batch -= per_graph) {
-                    HIPCHK(hipGraphLaunch(g->exec, io.stream));
-                    io.launches += g->launches; io.collectives += g->collectives;
-                }
-            }
-        }
-        if (batch > 0) CHK(ops.enqueue(batch));
+        CHK(chain_enqueue_batch(graphs, io, ctl.rules.iters_per_graph, step.kmax, step.iters, [&](int n) { return ops.enqueue(n); }));
         CHK(ops.finalize());
     }
+}
+
+// The host loop of the ONE chain A members of a batch share, up to iter_end (decisions: ChainLockstep).  resumes[A] is raised for every
+// member whose own state showed the halt at a resume; act[k] is the batch index of the member in slot k (nullptr: k) for the error text.
+// A front end that launches eagerly passes use_graph = false and an empty cache.  Ops as for chain_run, but collect(ChainView *v) reads
+// the A control states, and batch_head(iters, kmax) and enqueue(n, kmax) are told the step: a count that must be the same for a replay
+// and for eager launches is made by formula in batch_head (enqueue runs once, inside a capture).
+template <class Ops>
+int chain_run_lockstep(ChainLockstep &ctl, int A, const int *act, GraphCache &graphs, ChainIo io, int iter_end, long long *resumes, Ops &&ops) {
+    std::vector<ChainView> v((size_t)A);
+    ctl.begin(A);
+    for (;;) {
+        CHK(ops.collect(v.data()));
+        const ChainStep step = ctl.next(v.data(), iter_end, resumes);
+        if (step.kind == ChainStep::DONE) return LPBOX_OK;
+        if (step.kind == ChainStep::STUCK)
+            return lpbox_fail(LPBOX_E_STATE, "problem %d of the batch, iteration %d: the PCG is still halted at k = %d after %d resumes in a row", act ? act[ctl.stuck_slot] : ctl.stuck_slot, ctl.stuck_iter, ctl.stuck_pcg_k, step.resumes);
+        if (step.kind == ChainStep::RESUME) { CHK(ops.resume_pcg()); continue; }
+        CHK(ops.batch_head(step.iters, step.kmax));
+        CHK(chain_enqueue_batch(graphs, io, ctl.rules.iters_per_graph, step.kmax, step.iters, [&](int n) { return ops.enqueue(n, step.kmax); }));
+        CHK(ops.finalize());
+    }
+}
+
+// the indices of the members a batch's mask leaves active, ascending
+inline std::vector<int> active_members(const std::vector<uint8_t> &active) {
+    std::vector<int> act;
+    for (size_t i = 0; i < active.size(); i++) if (active[i]) act.push_back((int)i);
+    return act;
 }

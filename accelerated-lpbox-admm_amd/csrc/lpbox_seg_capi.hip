@@ -1,8 +1,8 @@
 // lpbox_seg_capi.hip -- host side of the SEGMENTATION flavour behind the C-ABI: image -> (A, b, c) cost construction
 // (SEGcpp:46-248, :705-756), device buffers, the graph-replayed iteration driver, early-fix index bookkeeping and getters.
 // All solver arithmetic runs in lpbox_seg_kernels.hip; there is no CPU fallback.  What the launch chains decide (kmax, batches, the resume
-// limit) is in lpbox_chain.h; the driver of the single-problem chain, the graph cache, the device buffer, the timer and the error-check
-// macros are in lpbox_host.h.  The lockstep chain of a batch (batch_run_chain) keeps its own loop and takes its rules from lpbox_chain.h.
+// limit) is in lpbox_chain.h; the drivers of the single-problem chain and of the lockstep chain of a batch, the graph cache, the device
+// buffer, the timer and the error-check macros are in lpbox_host.h.  This file supplies their launches (SegChainOps, SegBatchOps).
 #include "../../include/lpbox_hip.h"
 #include "lpbox_capi_internal.h"
 #include "lpbox_host.h"
@@ -328,50 +328,31 @@ int batch_reset_handle(SegSolver *s) {
     return LPBOX_OK;
 }
 
-// The lockstep chain of a batch (devs = device array of B descriptors, the window already set): iterations up to iter_end for every
-// problem, each on its own control state -- one that has stopped, is all fixed or whose PCG has converged falls through, a
-// SEG_HALT_PCG_MORE on any problem resumes the chain.  hs[B] receives the final states; *kmax carries the adaptive launch count;
-// resumes[B] is raised for every problem whose own state showed the halt at a resume.
-int batch_run_chain(const ChainRules &rules, const SegDev *devs, SegState *dstates, int B, int Gmax, int iter_end, int *parity, int *kmax,
-                    bool adaptive, SegState *hs, long long *launches, long long *resumes, hipStream_t st) {
-    std::vector<int> resumed(B, 0);                                 // per problem: resumes since one of its outer iterations last completed
-    for (;;) {
-        HIPCHK(segb_collect_states(devs, B, *parity, dstates, st));
-        HIPCHK(hipMemcpyAsync(hs, dstates, sizeof(SegState) * (size_t)B, hipMemcpyDeviceToHost, st));
+// The launches of the lockstep chain of a batch (chain_run_lockstep; devs = device array of A descriptors, the window already set): each
+// problem on its own control state -- one that has stopped, is all fixed or whose PCG has converged falls through, a SEG_HALT_PCG_MORE on
+// any problem resumes the chain.  hs[A] receives the final states.  The launches are eager and counted by formula.
+struct SegBatchOps {
+    const SegDev *devs; SegState *dstates; int A, Gmax; SegState *hs; int &parity; long long &launches; hipStream_t st;
+    int collect(ChainView *v) {
+        HIPCHK(segb_collect_states(devs, A, parity, dstates, st));
+        HIPCHK(hipMemcpyAsync(hs, dstates, sizeof(SegState) * (size_t)A, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
-        bool more = false, any_run = false;
-        int remaining = 0, vote = 0, pcg_k = 0;
-        for (int i = 0; i < B; i++) {
-            const SegState &h = hs[i];
-            if (h.halt == SEG_HALT_PCG_MORE) {
-                if (++resumed[i] > rules.resume_limit())
-                    return lpbox_fail(LPBOX_E_STATE, "problem %d of the batch, iteration %d: the PCG is still halted at k = %d after %d resumes in a row", i, h.iter, h.pcg_k, resumed[i] - 1);
-                resumes[i]++; more = true; pcg_k = std::max(pcg_k, h.pcg_k);
-                continue;
-            }
-            resumed[i] = 0;
-            if (h.halt != SEG_HALT_NONE) continue;
-            const int rem = iter_end - h.iter;
-            if (rem <= 0 && !h.have_prev) continue;
-            // (a problem that completed no PCG in the previous batch -- which only finalised a resumed iteration or was not its own --
-            //  votes for the kmax in use: chain_pcg_vote)
-            any_run = true; remaining = std::max(remaining, rem);
-            vote = std::max(vote, chain_pcg_vote(rules, *kmax, chain_view(h)));
-        }
-        if (more) {                                                 // some PCG ran out of launches: resume it (the others fall through)
-            HIPCHK(segb_enqueue_pcg_more(devs, B, Gmax, CHAIN_PAIRS_PER_RESUME, parity, st));
-            *launches += 2 + 2 * CHAIN_PAIRS_PER_RESUME;
-            if (adaptive) *kmax = chain_kmax_after_halt(rules, *kmax, pcg_k);
-            continue;
-        }
-        if (!any_run) break;
-        if (adaptive) *kmax = chain_kmax_for_vote(rules, vote);
-        HIPCHK(segb_launch_copy(devs, B, 1, parity, st));
-        const int batch = chain_batch_iters(rules, remaining);
-        if (batch > 0) HIPCHK(segb_enqueue_iterations(devs, B, Gmax, batch, *kmax, parity, st));
-        HIPCHK(segb_enqueue_finalize(devs, B, Gmax, parity, st));
-        *launches += 2 + (long long)batch * (4 + 2 * *kmax);
+        for (int i = 0; i < A; i++) v[i] = chain_view(hs[i]);
+        return LPBOX_OK;
     }
+    int resume_pcg() { HIPCHK(segb_enqueue_pcg_more(devs, A, Gmax, CHAIN_PAIRS_PER_RESUME, &parity, st)); launches += 2 + 2 * CHAIN_PAIRS_PER_RESUME; return LPBOX_OK; }
+    // (counts the whole batch: copy, iterations, finalize)
+    int batch_head(int iters, int kmax) { HIPCHK(segb_launch_copy(devs, A, 1, &parity, st)); launches += 2 + (long long)iters * (4 + 2 * kmax); return LPBOX_OK; }
+    int enqueue(int n, int kmax) { HIPCHK(segb_enqueue_iterations(devs, A, Gmax, n, kmax, &parity, st)); return LPBOX_OK; }
+    int finalize() { HIPCHK(segb_enqueue_finalize(devs, A, Gmax, &parity, st)); return LPBOX_OK; }
+};
+
+// iterations up to iter_end for the A problems behind `ops`, from *kmax on (written back after a chain that completed); act: see chain_run_lockstep
+int segb_run_chain(const ChainRules &rules, int *kmax, bool adaptive, const int *act, int iter_end, long long *resumes, SegBatchOps ops) {
+    ChainLockstep ctl(rules, *kmax, adaptive);
+    GraphCache none; long long collectives = 0; bool use_graph = false;          // the batch launches eagerly
+    CHK(chain_run_lockstep(ctl, ops.A, act, none, ChainIo{ops.st, ops.parity, ops.launches, collectives, use_graph, false}, iter_end, resumes, ops));
+    *kmax = ctl.kmax;
     return LPBOX_OK;
 }
 
@@ -516,7 +497,8 @@ int segc_legacy_batch(SegSolver **ss, int B, int *energies) {
     HIPCHK(segb_launch_init(devs.p, B, Gmax, st));
     HIPCHK(segb_launch_set_window(devs.p, B, 0, SEG_MAX_ITERS, 0, &parity, st));
     launches += 2;
-    if ((rc = batch_run_chain(s0->chain.rules, devs.p, dstates.p, B, Gmax, SEG_MAX_ITERS, &parity, &kmax, s0->chain.adaptive, hs.data(), &launches, resumes.data(), st))) return rc;
+    if ((rc = segb_run_chain(s0->chain.rules, &kmax, s0->chain.adaptive, nullptr, SEG_MAX_ITERS, resumes.data(),
+                             SegBatchOps{devs.p, dstates.p, B, Gmax, hs.data(), parity, launches, st}))) return rc;
     double ms = 0.0;
     HIPCHK(s0->timer.stop_sync(st, &ms));
     for (int i = 0; i < B; i++) {
@@ -775,19 +757,13 @@ int segb_describe(lpbox_seg_batch *b, const std::vector<int> &act, const std::ve
     return LPBOX_OK;
 }
 
-std::vector<int> segb_active(const lpbox_seg_batch *b) {
-    std::vector<int> act;
-    for (int i = 0; i < b->B; i++) if (b->active[i]) act.push_back(i);
-    return act;
-}
-
 // one window.  Host-vector form: vecs / nums (deter_fix_2 done by the caller); score form: scores (device, float32, one per packed row of
 // the last pack) or NULL, the rule runs on the device.  `score_form` selects which.
 int segb_window(lpbox_seg_batch *b, int iter_start, int iter_end, bool score_form, const double *vecs, long vec_stride, const int *nums,
                 const float *scores, double hi, double lo, int min_fix, int *rets, int *fixed) {
     const int ws = iter_end - iter_start;
     if (ws > SEG_XITERS_COLS) return lpbox_fail(LPBOX_E_BADARG, "window of %d iterations exceeds the %d columns of x_iters (SEGcpp:924)", ws, SEG_XITERS_COLS);
-    const std::vector<int> act = segb_active(b);
+    const std::vector<int> act = active_members(b->active);
     const int A = (int)act.size();
     std::vector<int> live(A), num(A, 0);
     for (int k = 0; k < A; k++) { SegSolver *s = b->ss[act[k]]; live[k] = s->inited ? s->hst.n_live : s->n; }
@@ -886,9 +862,8 @@ int segb_window(lpbox_seg_batch *b, int iter_start, int iter_end, bool score_for
 
     std::vector<SegState> hs(A);
     std::vector<long long> resumes(A, 0);
-    int kmax = b->kmax;
-    if ((rc = batch_run_chain(b->rules, b->devs.p, b->dstates.p, A, Gmax, iter_end, &parity, &kmax, b->ss[0]->chain.adaptive, hs.data(), &launches, resumes.data(), st))) return rc;
-    b->kmax = kmax;
+    if ((rc = segb_run_chain(b->rules, &b->kmax, b->ss[0]->chain.adaptive, act.data(), iter_end, resumes.data(),
+                             SegBatchOps{b->devs.p, b->dstates.p, A, Gmax, hs.data(), parity, launches, st}))) return rc;
     double ms = 0.0;
     HIPCHK(b->timer.stop_sync(st, &ms));
     for (int k = 0; k < A; k++) {
@@ -979,7 +954,7 @@ int segbc_l2f_scores(lpbox_seg_batch *b, int iter_start, int iter_end, const flo
 // the (n_live x ws) windows of all active handles, one after the other, in ONE buffer of the batch (one launch)
 int segbc_get_x_iters_device(lpbox_seg_batch *b, int ws, void **dev_ptr, long *row_off) {
     if (ws <= 0 || ws > SEG_XITERS_COLS) return lpbox_fail(LPBOX_E_BADARG, "ws = %d outside (0,%d]", ws, SEG_XITERS_COLS);
-    const std::vector<int> act = segb_active(b);
+    const std::vector<int> act = active_members(b->active);
     const int A = (int)act.size();
     for (int k = 0; k < A; k++)
         if (!b->ss[act[k]]->xi_valid) return lpbox_fail(LPBOX_E_STATE, "problem %d of the batch: solve_iter_l2f has not been called", act[k]);

@@ -98,6 +98,29 @@ def test_resumed_pcg_in_lockstep(monkeypatch):
     B.close()
 
 
+def test_captured_batch_chain(monkeypatch):
+    """LPBOX_BIG_BATCH_GRAPH=1: the iterations of a batch are replays of captured graphs (two iterations each) plus an eager tail, and a
+    second window comes back to the cache at another kmax.  Same bits as eager launches; the batch must not have fallen back to them."""
+    monkeypatch.setenv("LPBOX_BIG_BATCH_GRAPH", "1")
+    cases = [(300, 0), (1100, 4)]
+    windows = ((0, 7), (7, 40))
+    B = make_batch(cases)
+    assert B.scalar("graph") == 1.0
+    twins = [solo(n, s) for (n, s) in cases]
+    for w, (a, b) in enumerate(windows):
+        rets = B.solve_iter(a, b)
+        for k, (n, s) in enumerate(cases):
+            tag = f"captured, n={n} seed={s} [{a},{b})"
+            snap = BC.oracle_windows(n, s, windows)[w]
+            assert rets[k] == snap["ret"] == twins[k].solve_iter(a, b), tag
+            BC.same_as_snapshot(B[k], snap, tag)
+            BC.same_as_twin(B[k], twins[k], tag)
+    assert B.scalar("graph") == 1.0 and B.scalar("launches") > 0
+    for t in twins:
+        t.close()
+    B.close()
+
+
 def test_batch_of_one_equals_the_solo_handle():
     (n, s) = BC.MIXED[2]
     B, t = make_batch([(n, s)]), solo(n, s)

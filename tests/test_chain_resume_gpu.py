@@ -1,5 +1,5 @@
 """GPU tests of the PCG halt-and-resume path of the segmentation and generic-BQP launch chains (chain_run in csrc/lpbox_host.h with the
-operations of csrc/lpbox_seg_capi.hip and csrc/lpbox_gen_capi.hip, batch_run_chain in csrc/lpbox_seg_capi.hip): an outer iteration
+operations of csrc/lpbox_seg_capi.hip and csrc/lpbox_gen_capi.hip, chain_run_lockstep with SegBatchOps for a batch): an outer iteration
 enqueues kmax (matvec, update) pairs; a PCG that needs more halts the chain from `post`, every launch behind the halt falls through, and the host enqueues
 resume + 16 pairs + post.  The problems (tests/chain_cases.py, pinned on the CPU by tests/test_chain_resume_cases.py) need up to 44 and
 1000 PCG iterations, and LPBOX_SEG_KMAX / LPBOX_BQP_KMAX force the launch count down to 1.

@@ -1311,6 +1311,8 @@ int lpbox_debug_get_scalar(lpbox_t *h, int idx, const char *name, double *out) {
 
 int lpbox_debug_block_sum(int threads, int nv, int stage, int groups, int rounds, const double *in, double *out) {
     if (!in || !out || groups <= 0 || groups > 1024 || rounds <= 0 || rounds > 1024) return lpbox_fail(LPBOX_E_BADARG, "lpbox_debug_block_sum: bad argument");
+    if (threads <= 0 || threads > 1024 || nv <= 0 || nv > 6 || stage < 0 || stage > 5 || (stage != 0 && threads != 512))    // stages 1..5 are built for 512 threads
+        return lpbox_fail(LPBOX_E_BADARG, "lpbox_debug_block_sum: no kernel for %d threads, %d values, stage %d", threads, nv, stage);
     if (lpbox_device_count() < 1) return lpbox_fail(LPBOX_E_NODEVICE, "no HIP device");
     HIPCHK(hipSetDevice(g_device));
     const size_t per = (size_t)rounds * threads * nv;

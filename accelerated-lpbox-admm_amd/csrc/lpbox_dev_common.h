@@ -58,6 +58,36 @@ __device__ __forceinline__ double row_allreduce(double v) {      // inside each 
     return v;
 }
 
+// row_newbcast:N, the one DPP control gfx950 applies to a 64-bit operand: every lane of a row of 16 receives lane N of its row.
+// Preconditions of what is built on it (row_reduce_lane0): all 64 lanes of the wave are active -- a DPP read of an inactive lane is
+// not the value the sums need -- and the call stands in wave-uniform control flow.
+// The f64 arithmetic that takes such an operand is v_fmac_f64 (v_add_f64 has no DPP form on gfx950: the assembler rejects it), so an
+// addition of a broadcast value is written  acc += bcast(x) * 1.0.  The product with 1.0 is exact, so the one rounding of the fused
+// operation is the rounding of the addition acc + bcast(x): the same bits for every non-NaN operand, +-0 and infinities included.
+// The compiler does not select this form, hence the asm statements; each carries its own wait states (two between a VALU write of a
+// register and a DPP read of it).
+
+// row_allreduce for a caller that reads lane 0 of each row only (the owner lanes of wave_partials_store): the two quad steps, then with
+// the four quads of a row holding Q0..Q3   a = Q0 + Q1 (right in lanes 0-3),  b = Q2 + Q3 (right in lanes 8-11),  lane 0 = a + b:
+// three v_fmac_f64 with a row_newbcast operand, two of them independent, where row_half_mirror and row_mirror cost two moves, a wait and
+// an addition each.  Lane 0 receives (Q0 + Q1) + (Q2 + Q3), row_allreduce's association.  Every other lane of the row holds garbage.
+// Wait states: in front, where the compiler's quad step has just written v, and between the write of b and its DPP read (the
+// independent a += and s_nop 0).
+__device__ __forceinline__ double row_reduce_lane0(double v) {
+    v = v + dpp_mov<0xB1>(v);    // quad_perm [1,0,3,2]
+    v = v + dpp_mov<0x4E>(v);    // quad_perm [2,3,0,1]
+    double a = v, b = v;
+    asm("s_nop 1\n\t"
+        "v_fmac_f64_dpp %1, %0, %2 row_newbcast:12 row_mask:0xf bank_mask:0xf\n\t"      // b = Q + Q3: Q2 + Q3 in lanes 8-11
+        "v_fmac_f64_dpp %0, %0, %2 row_newbcast:4 row_mask:0xf bank_mask:0xf\n\t"       // a = Q + Q1: Q0 + Q1 in lanes 0-3
+        "s_nop 0\n\t"
+        "v_fmac_f64_dpp %0, %1, %2 row_newbcast:8 row_mask:0xf bank_mask:0xf"           // lane 0: (Q0 + Q1) + (Q2 + Q3)
+        : "+v"(a), "+v"(b) : "v"(1.0));
+    return a;
+}
+template <bool LANE0>
+__device__ __forceinline__ double row_finish(double v) { if constexpr (LANE0) return row_reduce_lane0(v); else return row_allreduce(v); }
+
 // 64-lane all-reduce of one value (every lane receives the sum).
 __device__ __forceinline__ double wave_allreduce_sum(double v) {
 #ifdef LPBOX_REDUCE_SHFL
@@ -74,7 +104,7 @@ __device__ __forceinline__ double wave_allreduce_sum(double v) {
 // NV <= 4 values through ONE narrow butterfly: on return the total of value k sits in every lane of row ROW_OF[k]
 // (rows of 16 lanes: value 0 -> row 0, 1 -> row 2, 2 -> row 1, 3 -> row 3); the result is returned in `out`, to be read
 // only in those rows.  Same per-value tree as wave_allreduce_sum.
-template <int NV>
+template <int NV, bool LANE0 = false>                                  // LANE0: valid in the first lane of each of those rows only (row_reduce_lane0)
 __device__ __forceinline__ double wave_reduce_scatter(const double *v) {
     static_assert(NV >= 2 && NV <= 4, "2..4 values");
     const double x = pair_step<HalfSwap>(v[0], v[1]);                                   // lower half: value 0, upper half: value 1
@@ -84,7 +114,7 @@ __device__ __forceinline__ double wave_reduce_scatter(const double *v) {
         const double y = NV == 4 ? pair_step<HalfSwap>(v[2], v[3]) : pair_step<HalfSwap>(v[2], v[2]);
         s = pair_step<RowSwap>(x, y);                                                   // rows: [v0, v2, v1, v3 (or v2 again)]
     }
-    return row_allreduce(s);
+    return row_finish<LANE0>(s);
 }
 // lane that owns value k after wave_reduce_scatter<NV>
 __device__ __forceinline__ constexpr int scatter_lane(int nv, int k) { return nv == 2 ? 32 * k : (k == 0 ? 0 : k == 1 ? 32 : k == 2 ? 16 : 48); }
@@ -132,6 +162,15 @@ constexpr int RED_STAGE_BCAST = 0;   // every lane reads all W partials (broadca
 constexpr int RED_STAGE_PAIRS = 1;   // W = 8: lane reads the pair (p[2j], p[2j+1]), j = lane & 3, with one ds_read_b128 per value
                                      // and adds it (the tree's "pairs" level); two quad_perm steps finish the tree
 constexpr int RED_STAGE_PAIRS_LOW = 2;   // RED_STAGE_PAIRS whose first stage runs the wide steps of 1, 2 and 3 values without register copies
+constexpr int RED_STAGE_PAIRS_BC = 3;    // RED_STAGE_PAIRS_LOW whose first stage finishes each row for its first lane only (row_reduce_lane0)
+// the second stage that reads four partials per lane (h = lane & 1 reads 4h .. 4h + 3 with two ds_read_b128 per value and adds
+// (p0 + p1) + (p2 + p3), the tree's pairs and quads of waves; ONE quad_perm level finishes), on either first stage
+constexpr int RED_STAGE_FOUR_BC = 4;     // first stage of RED_STAGE_PAIRS_BC: what the 512 x 1 window kernel runs
+constexpr int RED_STAGE_FOUR_LOW = 5;    // first stage of RED_STAGE_PAIRS_LOW
+constexpr int RED_STAGE_LAST = RED_STAGE_FOUR_LOW;
+__host__ __device__ constexpr bool red_first_low(int stage) { return stage >= RED_STAGE_PAIRS_LOW; }
+__host__ __device__ constexpr bool red_first_lane0(int stage) { return stage == RED_STAGE_PAIRS_BC || stage == RED_STAGE_FOUR_BC; }
+__host__ __device__ constexpr bool red_second_four(int stage) { return stage == RED_STAGE_FOUR_BC || stage == RED_STAGE_FOUR_LOW; }
 
 // First stage of RED_STAGE_PAIRS: the wave butterflies of block_sum, then ONE predicated store per butterfly -- the first lane
 // of every row of 16 lanes writes what its row holds (rows [v0, v2, v1, v3]; with fewer than four values a row that repeats a value
@@ -141,30 +180,33 @@ constexpr int RED_STAGE_PAIRS_LOW = 2;   // RED_STAGE_PAIRS whose first stage ru
 // three -- swaps it against an undefined register instead (pair_step_low): no v_mov copies in front of the swap.  The stored lanes
 // receive the same sums in the same association; the other owner lanes write garbage to the slots nobody reads (values >= NV of the
 // same parity half, as before).  Six values keep the copies: the rows of their second butterfly share two slots.
-template <int NV, bool LOW = false>
+// LANE0 (RED_STAGE_PAIRS_BC): the owner lanes are the only ones stored, for every number of values, so each butterfly finishes its rows
+// with row_reduce_lane0 -- the lanes it leaves with garbage are exactly the lanes that do not store.  All 64 lanes must be active.
+template <int NV, bool LOW = false, bool LANE0 = false>
 __device__ __forceinline__ void wave_partials_store(const double *v, double *buf, int lane, int w) {
+    static_assert(LOW || !LANE0, "the lane-0 row finish goes with the LOW wide steps");
     const int row = lane >> 4, k = ((row & 1) << 1) | (row >> 1);    // value index of this lane's row after wave_reduce_scatter<3 or 4>;
     const bool owner = (lane & 15) == 0;                              // after <2> rows 0, 1 hold value 0 and rows 2, 3 value 1: slots 0, 2, 1, 3
     double *at = buf + k * RED_MAXW + w;                         // loop-invariant up to the parity offset
     if constexpr (NV == 1) {
         double t0;
-        if constexpr (LOW) t0 = row_allreduce(pair_step_low<RowSwap>(pair_step_low<HalfSwap>(v[0])));   // row 0 holds it
+        if constexpr (LOW) t0 = row_finish<LANE0>(pair_step_low<RowSwap>(pair_step_low<HalfSwap>(v[0])));   // row 0 holds it
         else t0 = wave_allreduce_sum(v[0]);                           // every lane holds it: the slots of k = 1..3 get copies
         if (owner) *at = t0;
     } else if constexpr (LOW && NV == 2) {
         const double x = pair_step<HalfSwap>(v[0], v[1]);
-        const double sc = row_allreduce(pair_step_low<RowSwap>(x));   // rows 0 and 2 hold values 0 and 1: slots 0 and 1
+        const double sc = row_finish<LANE0>(pair_step_low<RowSwap>(x));   // rows 0 and 2 hold values 0 and 1: slots 0 and 1
         if (owner) *at = sc;
     } else if constexpr (LOW && NV == 3) {
         const double x = pair_step<HalfSwap>(v[0], v[1]);
         const double y = pair_step_low<HalfSwap>(v[2]);               // rows 0, 1 hold the halves of value 2
-        const double sc = row_allreduce(pair_step<RowSwap>(x, y));    // rows [v0, v2, v1, garbage]
+        const double sc = row_finish<LANE0>(pair_step<RowSwap>(x, y));    // rows [v0, v2, v1, garbage]
         if (owner) *at = sc;
     } else {
         constexpr int NS4 = NV > 4 ? 4 : NV;
-        const double sc = wave_reduce_scatter<NS4>(v);
+        const double sc = wave_reduce_scatter<NS4, LANE0>(v);
         if constexpr (NV == 6) {                                      // values 4 and 5 share a second butterfly: halves [v4, v5]
-            const double sc2 = wave_reduce_scatter<2>(v + 4);
+            const double sc2 = wave_reduce_scatter<2, LANE0>(v + 4);
             if (owner) { *at = sc; buf[(4 + (k & 1)) * RED_MAXW + w] = sc2; }
         } else {
             static_assert(NV <= 4, "1, 2, 3, 4 or 6 values");
@@ -189,9 +231,25 @@ __device__ __forceinline__ void block_sum(double (&v)[NV], double *red, int &par
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     double *buf = red + parity * (RED_MAXV * RED_MAXW);
     if constexpr (STAGE != RED_STAGE_BCAST) {
-        static_assert(W == 8 && (STAGE == RED_STAGE_PAIRS || STAGE == RED_STAGE_PAIRS_LOW), "built for eight waves");
-        wave_partials_store<NV, STAGE == RED_STAGE_PAIRS_LOW>(v, buf, lane, w);
+        static_assert(W == 8 && STAGE >= RED_STAGE_PAIRS && STAGE <= RED_STAGE_LAST, "built for eight waves");
+        wave_partials_store<NV, red_first_low(STAGE), red_first_lane0(STAGE)>(v, buf, lane, w);
         wg_barrier<BAR>();
+        if constexpr (red_second_four(STAGE)) {
+            // the tree's pairs and quads of waves in registers, its eight on one quad_perm level
+            double2 t0[NV], t1[NV];
+#pragma unroll
+            for (int k = 0; k < NV; k++) {
+                const double2 *q = (const double2 *)(buf + k * RED_MAXW + 4 * (lane & 1));
+                t0[k] = q[0]; t1[k] = q[1];
+            }
+#pragma unroll
+            for (int k = 0; k < NV; k++) {
+                const double u = (t0[k].x + t0[k].y) + (t1[k].x + t1[k].y);      // waves ((0,1) (2,3)) resp. ((4,5) (6,7))
+                v[k] = u + dpp_mov<0xB1>(u);                                     // eight
+            }
+            parity ^= 1;
+            return;
+        }
         double2 t[NV];
 #pragma unroll
         for (int k = 0; k < NV; k++) t[k] = *(const double2 *)(buf + k * RED_MAXW + 2 * (lane & 3));

@@ -93,6 +93,16 @@ namespace {
 #ifndef LPBOX_LP_MPDIRECT
 #define LPBOX_LP_MPDIRECT 1
 #endif
+// Reduction steps on f64 additions with a row-broadcast operand ("Row-broadcast reduction steps"), on top of REDLOW:
+//   REDBCAST1  first stage: each row of a wave is finished for its first lane only (row_reduce_lane0, RED_STAGE_PAIRS_BC)
+//   REDBCAST2  second stage: 0 the pair read with two quad_perm levels, 2 the four-partial read with one (RED_STAGE_FOUR_*; the
+//              candidate 1, row-broadcast additions behind the pair read, lost and is gone)
+#ifndef LPBOX_LP_REDBCAST1
+#define LPBOX_LP_REDBCAST1 1
+#endif
+#ifndef LPBOX_LP_REDBCAST2
+#define LPBOX_LP_REDBCAST2 2
+#endif
 // LDS hand-overs without a drain of the LDS counter in front of the barrier (lds_handover, lpbox_dev_common.h; DESIGN.md section 5, "LDS
 // hand-overs"), in the same kernel only and switched the same way (make variant NAME=x EXTRA=-DLPBOX_LP_HANDOVER_PCG=0 restores the
 // parent's text): the four barriers of a PCG iteration -- behind p, behind r4 q, inside block_sum<1> and block_sum<2>.  Between them the
@@ -139,6 +149,10 @@ __host__ __device__ constexpr bool lp_is_lean(int T, int EPT) { return EPT >= 4 
 // second stage of block_sum per geometry of lp_window_kernel (each measured on its own)
 __host__ __device__ constexpr int lp_red_stage(int T, int EPT) {
     return T == 512 && EPT == 1 ? RED_STAGE_PAIRS : RED_STAGE_BCAST;     // (512 x 4: 81.5 vs 77.4 us per iteration with PAIRS, it keeps the default)
+}
+// the stage on top of REDLOW, by the two row-broadcast steps
+__host__ __device__ constexpr int lp_red_stage_low(int bc1, int bc2) {
+    return bc1 ? (bc2 ? RED_STAGE_FOUR_BC : RED_STAGE_PAIRS_BC) : (bc2 ? RED_STAGE_FOUR_LOW : RED_STAGE_PAIRS_LOW);
 }
 // the leaner instruction stream, per step: the kernel with the fused outer iteration only
 __host__ __device__ constexpr bool lp_lean_stream(int T, int EPT, bool direct, bool log, int step_on) {
@@ -581,7 +595,7 @@ __global__ void __launch_bounds__(T) lp_window_kernel(LpBatchDev bd, int iter_st
     constexpr bool LAZY = lp_lean_stream(T, EPT, DIRECT, LOG, LPBOX_LP_LAZYSTOP), DEADZ = lp_lean_stream(T, EPT, DIRECT, LOG, LPBOX_LP_DEADZERO);
     constexpr bool MPDIR = lp_lean_stream(T, EPT, DIRECT, LOG, LPBOX_LP_MPDIRECT), MEANPRE = lp_lean_stream(T, EPT, DIRECT, LOG, LPBOX_LP_MEANPREFIX);
     constexpr int RS = (DIRECT || LOG) ? RED_STAGE_BCAST                            // second stage of every block_sum of this kernel
-                     : lp_lean_stream(T, EPT, DIRECT, LOG, LPBOX_LP_REDLOW) ? RED_STAGE_PAIRS_LOW : lp_red_stage(T, EPT);
+                     : lp_lean_stream(T, EPT, DIRECT, LOG, LPBOX_LP_REDLOW) ? lp_red_stage_low(LPBOX_LP_REDBCAST1, LPBOX_LP_REDBCAST2) : lp_red_stage(T, EPT);
     constexpr bool SCALAR_LOOP = lp_pcg_scalar_loop(T, EPT, DIRECT, LOG), SPEC = lp_pcg_spec_geometry(T, EPT, DIRECT, LOG);
     constexpr bool FUSED = lp_outer_fused(T, EPT, DIRECT, LOG);
     // barrier form of the PCG iteration's four hand-overs: between them the kernel touches LDS only
@@ -1735,7 +1749,8 @@ hipError_t lp_launch_debug_block_sum(int T, int NV, int stage, int groups, int r
     }
 #define CALL_DBG_NV(TT, SS) CALL_DBG(TT, 1, SS) CALL_DBG(TT, 2, SS) CALL_DBG(TT, 3, SS) CALL_DBG(TT, 6, SS)
     CALL_DBG_NV(256, RED_STAGE_BCAST) CALL_DBG_NV(512, RED_STAGE_BCAST) CALL_DBG_NV(1024, RED_STAGE_BCAST)
-    CALL_DBG_NV(512, RED_STAGE_PAIRS) CALL_DBG_NV(512, RED_STAGE_PAIRS_LOW)
+    CALL_DBG_NV(512, RED_STAGE_PAIRS) CALL_DBG_NV(512, RED_STAGE_PAIRS_LOW) CALL_DBG_NV(512, RED_STAGE_PAIRS_BC)
+    CALL_DBG_NV(512, RED_STAGE_FOUR_BC) CALL_DBG_NV(512, RED_STAGE_FOUR_LOW)
 #undef CALL_DBG_NV
 #undef CALL_DBG
     return hipErrorInvalidConfiguration;

@@ -310,7 +310,10 @@ int lpbox_debug_get_lp_table(lpbox_t *h, int idx, const char *name, int *out, in
  * threads each call the reduction `rounds` times back to back on one scratch area.  in[(r * threads + t) * nv + k] is thread t's
  * partial of value k in round r (the same for every workgroup); out[((g * rounds + r) * threads + t) * nv + k] is what thread t of
  * workgroup g received.  stage: 0 = the default second stage (threads 256 / 512 / 1024), 1 = the one the 512-thread window kernel
- * runs (threads 512); nv = 1, 2, 3 or 6.  Anything else: LPBOX_E_BADARG. */
+ * ran first (threads 512: pair reads), 2 = stage 1 with wide butterfly steps free of register copies; 3 = stage 2 whose rows of 16 lanes
+ * are finished for their first lane only, by additions of a row-broadcast operand; 4 = stage 3 with the second stage that reads four
+ * partials per lane (what the 512-thread window kernel runs); 5 = stage 2 with that second stage (threads 512 for 1..5); nv = 1, 2, 3
+ * or 6.  Anything else: LPBOX_E_BADARG. */
 int lpbox_debug_block_sum(int threads, int nv, int stage, int groups, int rounds, const double *in, double *out);
 /* Test entry for the LDS hand-over of the 512-thread window kernel (no solver state, used by no product path): `groups` workgroups of 512
  * threads run `rounds` rounds on ONE 512-vector in LDS.  A round: thread t writes v to element t; barrier; s = the sum, in order, of the

@@ -99,7 +99,103 @@ __global__ void __launch_bounds__(512) kh(double *out, unsigned long long *cyc, 
     if (tid == 0) cyc[blockIdx.x] = t1 - t0;
 }
 
-#define RUNH(KIND, BARE, name)                                                                                          \
+// Reduction steps on f64 arithmetic with a row_newbcast operand ("Row-broadcast reduction steps"), each as a
+// dependent chain per round, all 64 lanes active.  gfx950 has no v_add_f64_dpp; the addition of a broadcast value is
+// v_fmac_f64_dpp acc, bcast(x), 1.0 (exact product, one rounding: the addition's bits).
+//   KIND 0 / 1  the row finish of block_sum's first stage: two quad_perm levels, then row_half_mirror + row_mirror (0) or three
+//               v_fmac_f64_dpp (1, right in lane 0 of a row only; the other lanes carry finite garbage along the chain)
+//   KIND 2 / 3 / 4  the second stage behind a bare-barrier hand-over: pair read + two quad_perm levels (2), pair read + two broadcast
+//               moves + two v_fmac_f64_dpp + add (3, S2a), two ds_read_b128 + three adds + one quad_perm level (4, S2b)
+//   KIND 5 .. 8  16 dependent operations: plain v_add_f64 (5), v_add_f64 behind the two wait states a DPP read needs (6), v_fmac_f64
+//               behind them (7), v_fmac_f64_dpp row_newbcast:0 behind them (8) -- 8 minus 7 is the cost of the DPP operand itself
+template <int N> __device__ __forceinline__ double row_bcast(double v) { return __builtin_amdgcn_update_dpp(v, v, 0x150 + N, 0xf, 0xf, false); }
+__device__ __forceinline__ double row_finish_mirror(double v) {
+    v = v + dpp_mov<0xB1>(v); v = v + dpp_mov<0x4E>(v); v = v + dpp_mov<0x141>(v); v = v + dpp_mov<0x140>(v);
+    return v;
+}
+__device__ __forceinline__ double row_finish_lane0(double v) {
+    v = v + dpp_mov<0xB1>(v); v = v + dpp_mov<0x4E>(v);
+    double a = v, b = v;
+    asm("s_nop 1\n\t"
+        "v_fmac_f64_dpp %1, %0, %2 row_newbcast:12 row_mask:0xf bank_mask:0xf\n\t"
+        "v_fmac_f64_dpp %0, %0, %2 row_newbcast:4 row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 0\n\t"
+        "v_fmac_f64_dpp %0, %1, %2 row_newbcast:8 row_mask:0xf bank_mask:0xf"
+        : "+v"(a), "+v"(b) : "v"(1.0));
+    return a;
+}
+template <int KIND>
+__global__ void __launch_bounds__(512) kr(double *out, unsigned long long *cyc, const unsigned short *, int iters, double seed) {
+    __shared__ __attribute__((aligned(16))) double buf[2][16];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    double v = seed + tid * 1e-3;
+    const double c = seed * 1e-3;
+    if (tid < 16) { buf[0][tid] = 0.0; buf[1][tid] = 0.0; }
+    __syncthreads();
+    unsigned long long t0 = __builtin_amdgcn_s_memtime();
+    for (int it = 0; it < iters; it++) {
+        if (KIND == 0) v = row_finish_mirror(v) * 0.0625;
+        if (KIND == 1) v = row_finish_lane0(v) * 0.0625;
+        if (KIND >= 2 && KIND <= 4) {
+            double *b = buf[it & 1];
+            if (lane == 0) b[w] = v;
+            bar<true>();
+            double tot;
+            if (KIND == 4) {
+                const double2 *q = (const double2 *)(b + 4 * (lane & 1));
+                const double2 p0 = q[0], p1 = q[1];
+                const double u = (p0.x + p0.y) + (p1.x + p1.y);
+                tot = u + dpp_mov<0xB1>(u);
+            } else {
+                const double2 t = *(const double2 *)(b + 2 * (lane & 3));
+                double u = t.x + t.y;
+                if (KIND == 2) { u = u + dpp_mov<0xB1>(u); tot = u + dpp_mov<0x4E>(u); }
+                else {
+                    double a = row_bcast<0>(u), bb = row_bcast<2>(u);
+                    asm("s_nop 1\n\t"
+                        "v_fmac_f64_dpp %0, %2, %3 row_newbcast:1 row_mask:0xf bank_mask:0xf\n\t"
+                        "v_fmac_f64_dpp %1, %2, %3 row_newbcast:3 row_mask:0xf bank_mask:0xf"
+                        : "+v"(a), "+v"(bb) : "v"(u), "v"(1.0));
+                    tot = a + bb;
+                }
+            }
+            v = tot * 0.125 + 1e-3;
+        }
+        if (KIND == 5) {
+#pragma unroll
+            for (int q = 0; q < 16; q++) asm volatile("v_add_f64 %0, %0, %1" : "+v"(v) : "v"(c));
+        }
+        if (KIND == 6) {
+#pragma unroll
+            for (int q = 0; q < 16; q++) asm volatile("s_nop 1\n\tv_add_f64 %0, %0, %1" : "+v"(v) : "v"(c));
+        }
+        if (KIND == 7) {
+#pragma unroll
+            for (int q = 0; q < 16; q++) asm volatile("s_nop 1\n\tv_fmac_f64 %0, %1, %2" : "+v"(v) : "v"(c), "v"(1.0));
+        }
+        if (KIND == 8) {
+#pragma unroll
+            for (int q = 0; q < 16; q++) asm volatile("s_nop 1\n\tv_fmac_f64_dpp %0, %0, %1 row_newbcast:0 row_mask:0xf bank_mask:0xf" : "+v"(v) : "v"(c));
+        }
+    }
+    unsigned long long t1 = __builtin_amdgcn_s_memtime();
+    out[blockIdx.x * 512 + tid] = v;
+    if (tid == 0) cyc[blockIdx.x] = t1 - t0;
+}
+
+#define RUNR(KIND, name, per)                                                                                           \
+    {                                                                                                                   \
+        hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);                                                    \
+        kr<KIND><<<256, 512>>>(out, cyc, idx, 100, 1.25);                                                               \
+        hipEventRecord(e0); kr<KIND><<<256, 512>>>(out, cyc, idx, iters, 1.25); hipEventRecord(e1);                     \
+        hipDeviceSynchronize(); float ms; hipEventElapsedTime(&ms, e0, e1);                                             \
+        unsigned long long h[256]; hipMemcpy(h, cyc, sizeof(h), hipMemcpyDeviceToHost);                                 \
+        double s = 0; for (int i = 0; i < 256; i++) s += h[i];                                                          \
+        printf("%-46s %8.1f cycles  %7.1f ns  (clock %.2f GHz)\n", name, s / 256 / iters / per, 1e6 * ms / iters / per, \
+               s / 256 / (ms * 1e6));                                                                                   \
+    }
+
+#define RUNH(KIND, BARE, name)                                                                                         \
     {                                                                                                                   \
         hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);                                                    \
         kh<KIND, BARE><<<256, 512>>>(out, cyc, idx, 100, 1.25);                                                         \
@@ -147,6 +243,18 @@ int main() {
         RUNH(0, true, "vector hand-over L=8, bare s_barrier")
         RUNH(1, false, "block_sum hand-over b128, __syncthreads()")
         RUNH(1, true, "block_sum hand-over b128, bare s_barrier")
+    }
+    // row-broadcast reduction steps, each form twice in alternation
+    for (int rep = 0; rep < 2; rep++) {
+        RUNR(0, "row finish: 2 quad + half_mirror + mirror", 1)
+        RUNR(1, "row finish: 2 quad + 3 v_fmac_f64_dpp", 1)
+        RUNR(2, "second stage: pair read + 2 quad levels", 1)
+        RUNR(3, "second stage S2a: pair read + bcast fmacs", 1)
+        RUNR(4, "second stage S2b: 2 b128 reads + 1 quad level", 1)
+        RUNR(5, "dependent v_add_f64", 16)
+        RUNR(6, "dependent s_nop 1 + v_add_f64", 16)
+        RUNR(7, "dependent s_nop 1 + v_fmac_f64", 16)
+        RUNR(8, "dependent s_nop 1 + v_fmac_f64_dpp", 16)
     }
     return 0;
 }

@@ -1372,6 +1372,12 @@ int lpbox_seg_set_image(lpbox_t *h, const unsigned char *gray, int rows, int col
     return segc_set_image(h->seg, gray, rows, cols, num_nodes);
 }
 
+int lpbox_seg_set_order(lpbox_t *h, int mode) {
+    int rc = seg_handle(h);
+    if (rc) return rc;
+    return segc_set_order(h->seg, mode);
+}
+
 int lpbox_seg_legacy(lpbox_t *h, int *energy) {
     int rc = seg_handle(h);
     if (rc) return rc;

@@ -10,6 +10,7 @@ SegSolver *segc_create(int print_info, int device);
 void segc_destroy(SegSolver *s);
 int segc_set_problem(SegSolver *s, int n, int nnz, const int *rowptr, const int *colidx, const double *vals, const double *b,
                      double c, int rows, int cols, bool from_image = false);
+int segc_set_order(SegSolver *s, int mode);
 int segc_set_image(SegSolver *s, const unsigned char *gray, int rows, int cols, int num_nodes);
 int segc_init(SegSolver *s);
 int segc_legacy(SegSolver *s, int *energy);

@@ -107,3 +107,30 @@ hipError_t segb_launch_decide(const SegDev *devs, const SegBatchAux *aux, int B,
 hipError_t segb_launch_fix(const SegDev *devs, const SegFixPar *par, int B, int Gmax, int *parity, hipStream_t s);
 hipError_t segb_launch_compact(const SegDev *devs, const SegBatchAux *aux, const SegFixPar *par, int B, hipStream_t s);
 hipError_t segb_launch_pack_xiters(const SegDev *devs, const SegBatchAux *aux, int B, int max_rows, int ws, double *out, hipStream_t s);
+
+// ---- the reference's summation order (lpbox_seg_set_order(LPBOX_ORDER_REFERENCE); lpbox_seg_ref_kernels.hip) ----
+// A producer writes one term per live variable to stage[row][rank[i]] (row pitch n); one workgroup per problem walks the rows in
+// Eigen's redux association and leaves the totals in red[row].  Rows: resid's three, matvec's one, update's two, post's seven and,
+// directly behind them, the sphere-norm row (prep's, and post's for the next iteration) -- so that one walk takes post's eight.
+#define SEG_REF_MAXV 8
+enum { SEG_REF_B = 0, SEG_REF_C = 3, SEG_REF_D = 4, SEG_REF_E = 6, SEG_REF_A = 13, SEG_REF_ROWS = 14 };
+struct SegRef {
+    int *rank;              // [n] position of a live variable among the live ones (-1: fixed); SegBatchAux::left is its inverse
+    int *cnt;               // [1] live count
+    double *stage;          // [SEG_REF_ROWS][n]
+    double *red;            // [SEG_REF_ROWS] totals
+};
+hipError_t segr_launch_rank(const SegDev &d, const SegRef &rf, hipStream_t s);             // behind init and behind every fix
+// the launches of the default order's helpers of the same names, a walk behind every producer (a walk flips no parity):
+// prep + walk / per iteration yrhs, resid + walk, kmax x (matvec + walk, update + walk), post + walk  (5 + 4 kmax launches)
+hipError_t segr_enqueue_prep(const SegDev &d, const SegRef &rf, int *parity, hipStream_t s);
+hipError_t segr_enqueue_iterations(const SegDev &d, const SegRef &rf, int iters, int kmax, int *parity, hipStream_t s);
+hipError_t segr_enqueue_pcg_more(const SegDev &d, const SegRef &rf, int pairs, int *parity, hipStream_t s);   // 3 + 4 pairs launches
+hipError_t segr_enqueue_finalize(const SegDev &d, const SegRef &rf, int *parity, hipStream_t s);
+// a batch in lockstep: grid (Gmax, B) for the producers, (1, B) for the walks and the rank pass.  Unlike the default order's batch the
+// iterations carry no prep launch: the finalisation inside yrhs is a few scalar operations per workgroup here.
+hipError_t segrb_launch_rank(const SegDev *devs, const SegRef *refs, int B, hipStream_t s);
+hipError_t segrb_enqueue_prep(const SegDev *devs, const SegRef *refs, int B, int Gmax, int *parity, hipStream_t s);
+hipError_t segrb_enqueue_iterations(const SegDev *devs, const SegRef *refs, int B, int Gmax, int iters, int kmax, int *parity, hipStream_t s);
+hipError_t segrb_enqueue_pcg_more(const SegDev *devs, const SegRef *refs, int B, int Gmax, int pairs, int *parity, hipStream_t s);
+hipError_t segrb_enqueue_finalize(const SegDev *devs, const SegRef *refs, int B, int Gmax, int *parity, hipStream_t s);

@@ -28,6 +28,14 @@ ChainRules seg_rules() {
     if (const char *e = getenv("LPBOX_SEG_KMARGIN")) r.margin = std::max(0, atoi(e));
     return r;
 }
+
+// c1 = pow(n_live, 1/p), p = 2 (SEGcpp:557,670) through libm's pow, as the reference and the oracle call it: with the literal exponent
+// the compiler turns the call into sqrt, and glibc's pow is not correctly rounded (n = 2921: one ulp apart).  Reference order only; the
+// default order keeps the expressions it has always had.
+double ref_c1(int n) {
+    volatile double e = 1.0 / 2;
+    return std::pow((double)n, e);
+}
 }  // namespace
 
 struct SegSolver {
@@ -61,6 +69,14 @@ struct SegSolver {
     int record = 0;        // legacy loop keeps x of up to `record` iterations (lpbox_set_record; print_info 1, SEGcpp:1209-1213,1270-1277)
     int rec_cols = 0;      // iterations the last legacy solve recorded
     SegState hst;
+    // the reference's summation order (lpbox_seg_set_order; lpbox_seg_ref_kernels.hip): chosen before the problem, so the handle's
+    // buffers, launch chain and captured graphs belong to one order for good
+    int order = LPBOX_ORDER_DEFAULT;
+    DevBuf<int> d_rank, d_cnt;
+    DevBuf<double> d_stage, d_red;
+    bool ref() const { return order == LPBOX_ORDER_REFERENCE; }
+    SegRef rf() const { SegRef r; r.rank = d_rank.p; r.cnt = d_cnt.p; r.stage = d_stage.p; r.red = d_red.p; return r; }
+    double c1_of(int n_live) const { return ref() ? ref_c1(n_live) : std::pow((double)n_live, 1.0 / 2); }
 
     SegDev dev() const {
         SegDev d;
@@ -71,7 +87,7 @@ struct SegSolver {
         d.x = x.p; d.y1 = y1.p; d.y2 = y2.p; d.z1 = z1.p; d.z2 = z2.p; d.b = b.p; d.rhs = rhs.p; d.r = r.p; d.z = z.p;
         d.tmp = tmp.p; d.dinv = dinv.p; d.td = td.p; d.p0 = p0.p; d.p1 = p1.p; d.live = live.p; d.fixval = fixval.p;
         d.newfix = newfix.p; d.part = part.p; d.xhist = xhist.p; d.ws_cap = ws_cap; d.st = st.p;
-        d.c1_init = std::pow((double)n, 1.0 / 2);      // pow(n, 1/p), p = 2 (SEGcpp:557,670)
+        d.c1_init = ref() ? ref_c1(n) : std::pow((double)n, 1.0 / 2);      // pow(n, 1/p), p = 2 (SEGcpp:557,670)
         return d;
     }
 };
@@ -260,6 +276,11 @@ int upload(SegSolver *s) {
     }
     HIPCHK(hipMemset(s->part.p, 0, sizeof(double) * (size_t)5 * SEG_NPART * s->G));
     HIPCHK(hipMemset(s->newfix.p, 0, n));
+    if (s->ref()) {
+        HIPCHK(s->d_rank.alloc(n)); HIPCHK(s->d_cnt.alloc(1)); HIPCHK(s->d_stage.alloc((size_t)SEG_REF_ROWS * n)); HIPCHK(s->d_red.alloc(SEG_REF_ROWS));
+        HIPCHK(hipMemset(s->d_red.p, 0, sizeof(double) * SEG_REF_ROWS));
+        HIPCHK(hipMemset(s->d_cnt.p, 0, sizeof(int)));
+    }
     s->uploaded = true;
     return LPBOX_OK;
 }
@@ -279,22 +300,42 @@ struct SegChainOps {
     SegSolver *s;
     int read_state(ChainView &v) { CHK(::read_state(s)); v = chain_view(s->hst); return LPBOX_OK; }
     int resume_pcg() {
+        if (s->ref()) {
+            HIPCHK(segr_enqueue_pcg_more(s->dev(), s->rf(), CHAIN_PAIRS_PER_RESUME, &s->parity, s->stream));
+            s->launches += 3 + 4 * CHAIN_PAIRS_PER_RESUME;
+            return LPBOX_OK;
+        }
         HIPCHK(seg_enqueue_pcg_more(s->dev(), CHAIN_PAIRS_PER_RESUME, &s->parity, s->stream));
         s->launches += 2 + 2 * CHAIN_PAIRS_PER_RESUME;
         return LPBOX_OK;
     }
     int batch_head() {
         HIPCHK(seg_launch_copy(s->dev(), 1, &s->parity, s->stream));       // pcg_max = 0 for the coming batch
+        if (s->ref()) {
+            HIPCHK(segr_enqueue_prep(s->dev(), s->rf(), &s->parity, s->stream));
+            s->launches += 3;
+            return LPBOX_OK;
+        }
         HIPCHK(seg_enqueue_prep(s->dev(), &s->parity, s->stream));         // head of the batch (inside it post + yrhs do prep's work)
         s->launches += 2;
         return LPBOX_OK;
     }
     int enqueue(int n) {
+        if (s->ref()) {
+            HIPCHK(segr_enqueue_iterations(s->dev(), s->rf(), n, s->chain.kmax, &s->parity, s->stream));
+            s->launches += (long long)n * (5 + 4 * s->chain.kmax);
+            return LPBOX_OK;
+        }
         HIPCHK(seg_enqueue_iterations(s->dev(), n, s->chain.kmax, &s->parity, s->stream));
         s->launches += (long long)n * (3 + 2 * s->chain.kmax);
         return LPBOX_OK;
     }
-    int finalize() { HIPCHK(seg_enqueue_finalize(s->dev(), &s->parity, s->stream)); s->launches += 1; return LPBOX_OK; }
+    int finalize() {
+        if (s->ref()) HIPCHK(segr_enqueue_finalize(s->dev(), s->rf(), &s->parity, s->stream));
+        else HIPCHK(seg_enqueue_finalize(s->dev(), &s->parity, s->stream));
+        s->launches += 1;
+        return LPBOX_OK;
+    }
 };
 
 int run_window(SegSolver *s, int iter_end) {
@@ -333,6 +374,7 @@ int batch_reset_handle(SegSolver *s) {
 // any problem resumes the chain.  hs[A] receives the final states.  The launches are eager and counted by formula.
 struct SegBatchOps {
     const SegDev *devs; SegState *dstates; int A, Gmax; SegState *hs; int &parity; long long &launches; hipStream_t st;
+    const SegRef *refs = nullptr;                // the members' staging descriptors: a batch in the reference's summation order
     int collect(ChainView *v) {
         HIPCHK(segb_collect_states(devs, A, parity, dstates, st));
         HIPCHK(hipMemcpyAsync(hs, dstates, sizeof(SegState) * (size_t)A, hipMemcpyDeviceToHost, st));
@@ -340,12 +382,36 @@ struct SegBatchOps {
         for (int i = 0; i < A; i++) v[i] = chain_view(hs[i]);
         return LPBOX_OK;
     }
-    int resume_pcg() { HIPCHK(segb_enqueue_pcg_more(devs, A, Gmax, CHAIN_PAIRS_PER_RESUME, &parity, st)); launches += 2 + 2 * CHAIN_PAIRS_PER_RESUME; return LPBOX_OK; }
-    // (counts the whole batch: copy, iterations, finalize)
-    int batch_head(int iters, int kmax) { HIPCHK(segb_launch_copy(devs, A, 1, &parity, st)); launches += 2 + (long long)iters * (4 + 2 * kmax); return LPBOX_OK; }
-    int enqueue(int n, int kmax) { HIPCHK(segb_enqueue_iterations(devs, A, Gmax, n, kmax, &parity, st)); return LPBOX_OK; }
-    int finalize() { HIPCHK(segb_enqueue_finalize(devs, A, Gmax, &parity, st)); return LPBOX_OK; }
+    int resume_pcg() {
+        if (refs) { HIPCHK(segrb_enqueue_pcg_more(devs, refs, A, Gmax, CHAIN_PAIRS_PER_RESUME, &parity, st)); launches += 3 + 4 * CHAIN_PAIRS_PER_RESUME; return LPBOX_OK; }
+        HIPCHK(segb_enqueue_pcg_more(devs, A, Gmax, CHAIN_PAIRS_PER_RESUME, &parity, st)); launches += 2 + 2 * CHAIN_PAIRS_PER_RESUME; return LPBOX_OK;
+    }
+    // (counts the whole batch: copy, iterations, finalize; reference order: copy, prep, walk, iterations, finalize)
+    int batch_head(int iters, int kmax) {
+        HIPCHK(segb_launch_copy(devs, A, 1, &parity, st));
+        if (refs) { HIPCHK(segrb_enqueue_prep(devs, refs, A, Gmax, &parity, st)); launches += 4 + (long long)iters * (5 + 4 * kmax); return LPBOX_OK; }
+        launches += 2 + (long long)iters * (4 + 2 * kmax); return LPBOX_OK;
+    }
+    int enqueue(int n, int kmax) {
+        if (refs) HIPCHK(segrb_enqueue_iterations(devs, refs, A, Gmax, n, kmax, &parity, st));
+        else HIPCHK(segb_enqueue_iterations(devs, A, Gmax, n, kmax, &parity, st));
+        return LPBOX_OK;
+    }
+    int finalize() {
+        if (refs) HIPCHK(segrb_enqueue_finalize(devs, refs, A, Gmax, &parity, st));
+        else HIPCHK(segb_enqueue_finalize(devs, A, Gmax, &parity, st));
+        return LPBOX_OK;
+    }
 };
+
+// all members of a batch run in ONE summation order, member 0's; a member in the other order is refused by name
+int batch_order_ok(SegSolver *const *ss, int B) {
+    for (int i = 1; i < B; i++) {
+        if (ss[i]->ref() && !ss[0]->ref()) return lpbox_fail(LPBOX_E_UNSUPPORTED, "problem %d of the batch runs in the reference summation order; the batch runs the default order (problem 0's)", i);
+        if (!ss[i]->ref() && ss[0]->ref()) return lpbox_fail(LPBOX_E_UNSUPPORTED, "problem %d of the batch runs in the default order; the batch runs the reference summation order (problem 0's)", i);
+    }
+    return LPBOX_OK;
+}
 
 // iterations up to iter_end for the A problems behind `ops`, from *kmax on (written back after a chain that completed); act: see chain_run_lockstep
 int segb_run_chain(const ChainRules &rules, int *kmax, bool adaptive, const int *act, int iter_end, long long *resumes, SegBatchOps ops) {
@@ -413,6 +479,14 @@ int segc_set_problem(SegSolver *s, int n, int nnz, const int *rowptr, const int 
     return LPBOX_OK;
 }
 
+// Opt-in: the reference's summation order.  Before the problem: the staging buffers are allocated with it.
+int segc_set_order(SegSolver *s, int mode) {
+    if (mode != LPBOX_ORDER_DEFAULT && mode != LPBOX_ORDER_REFERENCE) return lpbox_fail(LPBOX_E_BADARG, "unknown summation order %d", mode);
+    if (s->has_problem || s->uploaded || s->inited) return lpbox_fail(LPBOX_E_STATE, "set the summation order before lpbox_seg_set_image / lpbox_set_problem_bqp");
+    s->order = mode;
+    return LPBOX_OK;
+}
+
 int segc_set_image(SegSolver *s, const unsigned char *gray, int rows, int cols, int num_nodes) {
     if (!gray || rows <= 0 || cols <= 0 || num_nodes <= 0) return lpbox_fail(LPBOX_E_BADARG, "bad image arguments");
     const double scale = std::sqrt(num_nodes / (double)((long)rows * cols));     // SEGcpp:707
@@ -435,7 +509,8 @@ int segc_init(SegSolver *s) {
     for (int i = 0; i < s->n; i++) s->left_idx[i] = i;
     s->left_stale = false; s->dleft_valid = false; s->win_serial++;
     s->xi_valid = false; s->parity = 0; s->chain.pcg_resumes = 0;
-    HIPCHK(seg_launch_init(s->dev(), std::pow((double)s->n, 1.0 / 2), s->stream));    // pow(n, 1/p), p = 2 (SEGcpp:557,670)
+    HIPCHK(seg_launch_init(s->dev(), s->ref() ? ref_c1(s->n) : std::pow((double)s->n, 1.0 / 2), s->stream));    // pow(n, 1/p), p = 2 (SEGcpp:557,670)
+    if (s->ref()) { HIPCHK(segr_launch_rank(s->dev(), s->rf(), s->stream)); s->launches++; }      // the identity: every variable is live
     rc = read_state(s);
     if (rc) return rc;
     s->inited = true;
@@ -473,6 +548,7 @@ int segc_legacy_batch(SegSolver **ss, int B, int *energies) {
         for (int k = 0; k < i; k++)                                 // one handle twice = every launch advancing the same buffers twice
             if (ss[k] == ss[i]) return lpbox_fail(LPBOX_E_BADARG, "problem %d and problem %d of the batch are the same handle", k, i);
     }
+    if (int orc = batch_order_ok(ss, B)) return orc;
     // a solver counts as initialised only once the whole chain has completed: an early error return leaves every member of the
     // batch in the "solve_init has not been called" state instead of flagged ready with half-written device state
     for (int i = 0; i < B; i++) { ss[i]->inited = false; ss[i]->xi_valid = false; }
@@ -486,19 +562,27 @@ int segc_legacy_batch(SegSolver **ss, int B, int *energies) {
     hipStream_t st = s0->stream;
     std::vector<SegDev> hd(B);
     for (int i = 0; i < B; i++) hd[i] = ss[i]->dev();
-    DevBuf<SegDev> devs; DevBuf<SegState> dstates;
+    DevBuf<SegDev> devs; DevBuf<SegState> dstates; DevBuf<SegRef> refs;
     HIPCHK(devs.alloc(B)); HIPCHK(dstates.alloc(B));
     HIPCHK(hipMemcpyAsync(devs.p, hd.data(), sizeof(SegDev) * (size_t)B, hipMemcpyHostToDevice, st));
+    std::vector<SegRef> hr;
+    if (s0->ref()) {
+        hr.resize(B);
+        for (int i = 0; i < B; i++) hr[i] = ss[i]->rf();
+        HIPCHK(refs.alloc(B));
+        HIPCHK(hipMemcpyAsync(refs.p, hr.data(), sizeof(SegRef) * (size_t)B, hipMemcpyHostToDevice, st));
+    }
     std::vector<SegState> hs(B);
     int parity = 0, kmax = s0->chain.kmax;
     long long launches = 0;
     std::vector<long long> resumes(B, 0);
     HIPCHK(s0->timer.start(st));
     HIPCHK(segb_launch_init(devs.p, B, Gmax, st));
+    if (refs.p) { HIPCHK(segrb_launch_rank(devs.p, refs.p, B, st)); launches++; }
     HIPCHK(segb_launch_set_window(devs.p, B, 0, SEG_MAX_ITERS, 0, &parity, st));
     launches += 2;
     if ((rc = segb_run_chain(s0->chain.rules, &kmax, s0->chain.adaptive, nullptr, SEG_MAX_ITERS, resumes.data(),
-                             SegBatchOps{devs.p, dstates.p, B, Gmax, hs.data(), parity, launches, st}))) return rc;
+                             SegBatchOps{devs.p, dstates.p, B, Gmax, hs.data(), parity, launches, st, refs.p}))) return rc;
     double ms = 0.0;
     HIPCHK(s0->timer.stop_sync(st, &ms));
     for (int i = 0; i < B; i++) {
@@ -536,7 +620,8 @@ int segc_l2f(SegSolver *s, int iter_start, int iter_end, const double *vec, int 
         }
         s->left_idx.swap(keep);
         HIPCHK(hipMemcpy(s->newfix.p, nf.data(), nf.size(), hipMemcpyHostToDevice));
-        HIPCHK(seg_launch_fix(s->dev(), n_live - num, std::pow((double)(n_live - num), 1.0 / 2), &s->parity, s->stream));
+        HIPCHK(seg_launch_fix(s->dev(), n_live - num, s->ref() ? ref_c1(n_live - num) : std::pow((double)(n_live - num), 1.0 / 2), &s->parity, s->stream));
+        if (s->ref()) { HIPCHK(segr_launch_rank(s->dev(), s->rf(), s->stream)); s->launches++; }   // the live set has changed
         HIPCHK(hipMemsetAsync(s->newfix.p, 0, s->n, s->stream));
     }
     s->xi_rows = n_live - num; s->xi_left_idx = s->left_idx;
@@ -630,6 +715,20 @@ int segc_get_obj(SegSolver *s, double *out) {                                 //
     if (rc) return rc;
     std::vector<double> xx;
     if ((rc = fetch_solution(s, xx))) return rc;
+    if (s->ref()) {
+        // reference order: x.dot(A x) and b.dot(x) over the full-length vectors in Eigen's redux association (SEGcpp:868-893); the
+        // problem need not be an image's, so the terms need not be integers
+        std::vector<double> t1((size_t)s->n), t2((size_t)s->n);
+        for (int i = 0; i < s->n; i++) {
+            double t = 0;
+            for (int k = s->rowptr[i]; k < s->rowptr[i + 1]; k++) t += s->vals[k] * xx[s->colidx[k]];
+            double r = 0.0;
+            r += 1.0 * t;
+            t1[i] = xx[i] * r; t2[i] = s->orgb[i] * xx[i];
+        }
+        *out = (eigen_sum(t1) + eigen_sum(t2)) + s->c;
+        return LPBOX_OK;
+    }
     // compute_cost(xx, org_A, org_b) = xx.(A xx) + b.xx; every term is an integer, so the summation order is immaterial
     double val = 0.0, val2 = 0.0;
     for (int i = 0; i < s->n; i++) {
@@ -689,7 +788,7 @@ int segc_debug_scalar(SegSolver *s, const char *name, double *out) {
         {"rho1", h.rho1}, {"gamma", h.gamma_val}, {"cur_obj", h.cur_obj}, {"std_obj", h.std_obj}, {"cvg1", h.cvg1}, {"cvg2", h.cvg2},
         {"obj_val", h.obj_val}, {"best_bin_obj", h.best_bin_obj}, {"c", s->c}, {"last_pcg", (double)h.last_pcg}, {"iter", (double)h.iter},
         {"matrix_as_diagonals", s->dia ? 1.0 : 0.0}, {"ell_width", (double)s->ell_w},
-        {"pcg_resumes", (double)s->chain.pcg_resumes}, {"kmax", (double)s->chain.kmax},
+        {"pcg_resumes", (double)s->chain.pcg_resumes}, {"kmax", (double)s->chain.kmax}, {"order", (double)s->order},
     };
     for (auto &e : tab) if (!strcmp(e.n, name)) { *out = e.v; return LPBOX_OK; }
     return lpbox_fail(LPBOX_E_BADARG, "unknown scalar '%s'", name);
@@ -720,6 +819,8 @@ struct lpbox_seg_batch {
     hipStream_t stream = nullptr;
     StreamTimer timer;
     DevBuf<SegDev> devs; DevBuf<SegBatchAux> aux; DevBuf<SegFixPar> par; DevBuf<SegState> dstates; DevBuf<int> counts; DevBuf<double> pack;
+    bool ref = false;                            // every member runs in the reference's summation order (checked at create)
+    DevBuf<SegRef> refs; std::vector<SegRef> h_refs;   // ... then the staging descriptors of the handles behind devs, in that order
     uint8_t *h_newfix = nullptr;                 // pinned staging of the host-vector form, problem i at nf_off[i]
     std::vector<size_t> nf_off;
     std::vector<SegDev> h_devs; std::vector<SegBatchAux> h_aux;   // host side of devs / aux (alive until the stream has taken them)
@@ -736,6 +837,7 @@ int segb_ensure(lpbox_seg_batch *b) {
     HIPCHK(hipStreamCreate(&b->stream));
     HIPCHK(b->timer.create());
     HIPCHK(b->devs.alloc(B)); HIPCHK(b->aux.alloc(B)); HIPCHK(b->par.alloc(B)); HIPCHK(b->dstates.alloc(B)); HIPCHK(b->counts.alloc(2 * (size_t)B));
+    if (b->ref) HIPCHK(b->refs.alloc(B));
     size_t tot = 0;
     b->nf_off.assign(B, 0);
     for (int i = 0; i < B; i++) { b->nf_off[i] = tot; tot += (size_t)b->ss[i]->n; }
@@ -754,6 +856,11 @@ int segb_describe(lpbox_seg_batch *b, const std::vector<int> &act, const std::ve
     }
     HIPCHK(hipMemcpyAsync(b->devs.p, hd.data(), sizeof(SegDev) * hd.size(), hipMemcpyHostToDevice, b->stream));
     HIPCHK(hipMemcpyAsync(b->aux.p, ha.data(), sizeof(SegBatchAux) * ha.size(), hipMemcpyHostToDevice, b->stream));
+    if (b->ref) {
+        b->h_refs.resize(act.size());
+        for (size_t k = 0; k < act.size(); k++) b->h_refs[k] = b->ss[act[k]]->rf();
+        HIPCHK(hipMemcpyAsync(b->refs.p, b->h_refs.data(), sizeof(SegRef) * act.size(), hipMemcpyHostToDevice, b->stream));
+    }
     return LPBOX_OK;
 }
 
@@ -851,7 +958,7 @@ int segb_window(lpbox_seg_batch *b, int iter_start, int iter_end, bool score_for
     for (int k = 0; k < A; k++) {
         const int nl = live[k] - applied[k];
         hp[k].apply = applied[k] > 0 ? 1 : 0; hp[k].n_live_new = nl;
-        hp[k].c1_new = std::pow((double)nl, 1.0 / 2);             // on the host, as segc_l2f: pow and a device sqrt differ by an ulp now and then
+        hp[k].c1_new = b->ref ? ref_c1(nl) : std::pow((double)nl, 1.0 / 2);             // on the host, as segc_l2f: pow and a device sqrt differ by an ulp now and then
         any |= applied[k] > 0;
     }
     HIPCHK(hipMemcpyAsync(b->par.p, hp.data(), sizeof(SegFixPar) * (size_t)A, hipMemcpyHostToDevice, st));
@@ -859,11 +966,12 @@ int segb_window(lpbox_seg_batch *b, int iter_start, int iter_end, bool score_for
     HIPCHK(segb_launch_fix(b->devs.p, b->par.p, A, Gmax, &parity, st));          // also x_iters = Zero, all staged columns
     launches += 2;
     if (any) { HIPCHK(segb_launch_compact(b->devs.p, b->aux.p, b->par.p, A, st)); launches++; }
+    if (any && b->ref) { HIPCHK(segrb_launch_rank(b->devs.p, b->refs.p, A, st)); launches++; }      // the live sets have changed
 
     std::vector<SegState> hs(A);
     std::vector<long long> resumes(A, 0);
     if ((rc = segb_run_chain(b->rules, &b->kmax, b->ss[0]->chain.adaptive, act.data(), iter_end, resumes.data(),
-                             SegBatchOps{b->devs.p, b->dstates.p, A, Gmax, hs.data(), parity, launches, st}))) return rc;
+                             SegBatchOps{b->devs.p, b->dstates.p, A, Gmax, hs.data(), parity, launches, st, b->ref ? b->refs.p : nullptr}))) return rc;
     double ms = 0.0;
     HIPCHK(b->timer.stop_sync(st, &ms));
     for (int k = 0; k < A; k++) {
@@ -894,7 +1002,9 @@ lpbox_seg_batch *segbc_create(SegSolver **ss, int B) {
         for (int k = 0; k < i; k++)
             if (ss[k] == ss[i]) return refuse(lpbox_fail(LPBOX_E_BADARG, "problem %d and problem %d of the batch are the same handle", k, i));
     }
+    if (int orc = batch_order_ok(ss, B)) return refuse(orc);
     lpbox_seg_batch *b = new lpbox_seg_batch();
+    b->ref = ss[0]->ref();
     b->ss.assign(ss, ss + B); b->B = B; b->active.assign(B, 1); b->kmax = ss[0]->chain.kmax;
     b->row_off.assign((size_t)B + 1, 0); b->pack_serial.assign(B, -1);
     return b;
@@ -933,6 +1043,7 @@ int segbc_init(lpbox_seg_batch *b) {
     for (int i = 0; i < B; i++) all[i] = i;
     if ((rc = segb_describe(b, all, zero, zero))) return rc;
     HIPCHK(segb_launch_init(b->devs.p, B, Gmax, b->stream));
+    if (b->ref) { HIPCHK(segrb_launch_rank(b->devs.p, b->refs.p, B, b->stream)); b->ss[0]->launches += 1; }
     std::vector<SegState> hs(B);
     HIPCHK(segb_collect_states(b->devs.p, B, 0, b->dstates.p, b->stream));
     HIPCHK(hipMemcpyAsync(hs.data(), b->dstates.p, sizeof(SegState) * (size_t)B, hipMemcpyDeviceToHost, b->stream));

@@ -168,6 +168,7 @@ inline double *LPboxADMMsolver::get_x_sol() {
     return s_->xsol.data();
 }
 inline double LPboxADMMsolver::get_final_obj() { double v = 0; seg_ok(lpbox_seg_get_obj(s_->h, &v), "lpbox_seg_get_obj"); return v; }
+inline void LPboxADMMsolver::set_order(int mode) { seg_ok(lpbox_seg_set_order(s_->h, mode), "lpbox_seg_set_order"); }
 inline long long LPboxADMMsolver::outer_iterations() { long long o = 0, p = 0; seg_ok(lpbox_get_counters(s_->h, 0, &o, &p), "lpbox_get_counters"); return o; }
 
 inline void LPboxADMMsolver::save_img() {                      // white where x >= 0.5; x is the scaled image column by column (SEGcpp:822-826)

@@ -30,6 +30,7 @@ public:
     void save_img();                                          // lpbox_seg_get_shape + get_x_sol -> <result>/output_<problem>.png   SEGcpp:812-837
 
     // ---- not in the reference ----
+    void set_order(int mode);                                 // lpbox_seg_set_order: LPBOX_ORDER_REFERENCE = the reference's summation order; before _init
     long long outer_iterations();                             // lpbox_get_counters
     std::string output_path() const;
 

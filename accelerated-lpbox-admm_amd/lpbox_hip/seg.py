@@ -61,6 +61,7 @@ class PyLPboxADMMsolver:
             check(-2, "lpbox_create")
         self._h = C.c_void_p(h)
         self._have_problem = False
+        self.order = "default"
 
     def close(self):
         if getattr(self, "_h", None):
@@ -72,6 +73,20 @@ class PyLPboxADMMsolver:
             self.close()
         except Exception:
             pass
+
+    # ---- extension: the reference's summation order (C-ABI lpbox_seg_set_order) ----
+    _ORDERS = {"default": 0, "reference": 1}
+
+    def set_order(self, order):
+        """"reference": every sum over the live variables in the association of the reference's Eigen redux -- the bits of the
+        reference's own arithmetic (oracle/seg_oracle.c in its Eigen order); "default": the tuned kernels.  Call it before set_image /
+        set_problem (a late call raises RuntimeError).  solve_batch and SegBatch run in the order of their members and refuse a mix."""
+        if order not in self._ORDERS:
+            raise ValueError("order must be 'default' or 'reference', not %r" % (order,))
+        if self._have_problem:
+            raise RuntimeError("set_order must be called before set_image / set_problem")
+        check(self._L.lpbox_seg_set_order(self._h, self._ORDERS[order]), "lpbox_seg_set_order")
+        self.order = order
 
     # ---- extensions: hand the image / the problem over in memory ----
     def set_image(self, gray, numNodes=None):

@@ -208,6 +208,19 @@ int lpbox_set_problem_bqp(lpbox_t *h, int n, int nnz, const int *rowptr, const i
 /* The image part of ADMM_bqp_unconstrained_init (SEGcpp:702-756): grayscale pixels (rows x cols, row-major, what
  * cv::imread(path, 0) yields), scaled to ~num_nodes pixels (cv::resize INTER_LINEAR), costs per SEGcpp:46-248. */
 int lpbox_seg_set_image(lpbox_t *h, const unsigned char *gray, int rows, int cols, int num_nodes);
+/* OPT-IN: the reference's summation order for this flavour, LPBOX_ORDER_DEFAULT / LPBOX_ORDER_REFERENCE as for
+ * lpbox_set_order.  REFERENCE = every sum over a problem's live variables (the PCG dot products, the norms of the stop test and of the
+ * sphere projection, both compute_cost calls) associated as Eigen 3.3.8's SSE2 redux associates it over the reference's COMPACTED
+ * vector, c1 through libm's pow, lpbox_seg_get_obj in the same association: bit for bit oracle/seg_oracle.c in its Eigen order on every
+ * vector and scalar, except std_obj (sqrt for pow(v, 1/2): within 2 ulps).  The sparse products and the fix step are the reference's
+ * order in both modes.  Call it BEFORE lpbox_seg_set_image / lpbox_set_problem_bqp (the staging rows are allocated with the problem);
+ * afterwards -> LPBOX_E_STATE.  Unknown mode -> LPBOX_E_BADARG; an LP-flavour handle -> LPBOX_E_STATE (and lpbox_set_order on a
+ * segmentation handle keeps answering LPBOX_E_STATE).  lpbox_debug_get_scalar(h, 0, "order") reports the mode.  Everything else works
+ * as in the default order: windows, recording, the launch-chain controls (LPBOX_SEG_KMAX, _KMARGIN, _NOGRAPH, _EPT, _NODIA).
+ * lpbox_seg_legacy_batch and lpbox_seg_batch_create take handles that are all in ONE order, problem 0's: a member in the other order
+ * -> LPBOX_E_UNSUPPORTED, naming its index.  What it costs: every reduction becomes a walk of n_live / 4 dependent additions by one
+ * workgroup per problem; a batch runs its members' walks side by side. */
+int lpbox_seg_set_order(lpbox_t *h, int mode);
 /* `cv::imread(imagePath, 0)` (SEGcpp:705) without an image library: the luminance plane of a baseline / extended-sequential 8-bit
  * Huffman JPEG, reconstructed with libjpeg's default ISLOW inverse DCT -- bit for bit what libjpeg yields for JCS_GRAYSCALE output,
  * which is what OpenCV's grayscale imread and PIL's draft("L") hand out (csrc/lpbox_jpeg_host.cpp; pinned against PIL in the tests).

@@ -66,6 +66,22 @@ hipError_t gen_launch_post(const GenDev &d, int *parity, hipStream_t s);
 hipError_t gen_launch_dual(const GenDev &d, int init_only, int *parity, hipStream_t s);
 hipError_t gen_launch_resume(const GenDev &d, int reset_pcg_max, int *parity, hipStream_t s);
 
+// ---- a BATCH of problems through one chain in lockstep (lpbox_bqp_lockstep_*): grid (X, B) per launch, row
+// blockIdx.y = problem blockIdx.y of the device array devs[B]; X = the largest extent of that kernel over the batch ----
+#define GEN_BATCH_MAX 65535   // members: blockIdx.y
+struct GenBatchGrid {
+    int B;
+    int cols;      // max G: prep, rhs_cols, resid, pcg_cols, pcg_upd, post
+    int y;         // max of max(G, Gl, 1)
+    int rows;      // max of max(Gm, Gl, 1): rows, dual
+};
+hipError_t genb_launch_resume(const GenDev *devs, const GenBatchGrid &g, int reset_pcg_max, int *parity, hipStream_t s);
+hipError_t genb_launch_prep(const GenDev *devs, const GenBatchGrid &g, int do_prep, int *parity, hipStream_t s);            // with do_prep = 0: the finalising launch
+hipError_t genb_enqueue_pcg(const GenDev *devs, const GenBatchGrid &g, int pairs, int *parity, hipStream_t s);             // pairs x (rows(1), pcg_cols, fin, pcg_upd, fin)
+hipError_t genb_enqueue_tail(const GenDev *devs, const GenBatchGrid &g, int *parity, hipStream_t s);                       // post, fin, rows(0), dual
+hipError_t genb_enqueue_iterations(const GenDev *devs, const GenBatchGrid &g, int iters, int kmax, int *parity, hipStream_t s);   // 16 + 5 kmax launches each
+hipError_t genb_collect_states(const GenDev *devs, const GenBatchGrid &g, int parity, GenState *out, hipStream_t s);       // out[i] = st[parity] of problem i
+
 // ---- the reference's summation order (lpbox_bqp_set_order(LPBOX_ORDER_REFERENCE), lpbox_gen_ref_kernels.hip) ----
 #define GEN_REF_NSTAGE 7   // staging rows of n doubles, numbered as the slots of GenDev::part (post fills all seven)
 struct GenRef {

@@ -3,6 +3,7 @@
 // _linear_eq_and_uneq (SEGcpp:1834-2109).  The kernels are in lpbox_gen_kernels.hip (and, for the opt-in reference summation order of
 // lpbox_bqp_set_order, lpbox_gen_ref_kernels.hip); the host loop of the launch chain is chain_run of
 // lpbox_host.h with the rules of lpbox_chain.h (CHAIN_RULES_GEN), which also holds the graph cache, the device buffer and the macros.
+// At the end of the file: a batch of handles through one chain in lockstep (lpbox_bqp_lockstep_*, chain_run_lockstep).
 #include "lpbox_gen_host.h"
 #include "lpbox_host.h"
 
@@ -182,10 +183,9 @@ int lpbox_bqp_set_problem(lpbox_bqp_t *h, int n, const int *Ap, const int *Ai, c
     return LPBOX_OK;
 }
 
-int lpbox_bqp_solve(lpbox_bqp_t *h, int *iterations) {                              // ADMM_bqp SEGcpp:1384-1832
-    if (!h) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
-    if (!h->has_problem) return lpbox_fail(LPBOX_E_STATE, "no problem set");
-    CHK(use_device(h->device));
+// What precedes the chain of a solve, on the handle's own stream (the device is the current one): the upload at the first solve, the
+// counters and the timer started, the init launches.  lpbox_bqp_solve goes on with chain_run, a lockstep batch with the chain it shares.
+static int gen_begin_solve(lpbox_bqp *h) {
     const int n = h->n, m = h->m, l = h->l;
     if (!h->uploaded) {
         auto groups = [](int len, int &ept) { ept = 2; while ((len + GEN_T * ept - 1) / (GEN_T * ept) > 4096 && ept < 64) ept *= 2; return len > 0 ? (len + GEN_T * ept - 1) / (GEN_T * ept) : 0; };
@@ -217,6 +217,16 @@ int lpbox_bqp_solve(lpbox_bqp_t *h, int *iterations) {                          
     HIPCHK(gen_launch_init2(d, h->stream));
     ROWS(0);                                                                        // E x0 for the first y3
     HIPCHK(gen_launch_dual(d, 1, &h->parity, h->stream));
+    return LPBOX_OK;
+}
+
+int lpbox_bqp_solve(lpbox_bqp_t *h, int *iterations) {                              // ADMM_bqp SEGcpp:1384-1832
+    if (!h) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
+    if (!h->has_problem) return lpbox_fail(LPBOX_E_STATE, "no problem set");
+    CHK(use_device(h->device));
+    CHK(gen_begin_solve(h));
+    const GenDev d = h->dev();
+    const int n = h->n;
     CHK(chain_run(h->chain, h->graphs, ChainIo{h->stream, h->parity, h->launches, h->collectives, h->use_graph, true}, h->prm.max_iters,
                   GenChainOps{h, d}));
     // best_sol = x_sol of the last improving iteration (:1792) is copied by the NEXT iteration's y kernel; if the loop ended right after an
@@ -256,6 +266,179 @@ int lpbox_bqp_get_scalar(lpbox_bqp_t *h, const char *name, double *out) {
         {"graph_revisits", (double)h->graphs.revisits}, {"order", h->ref ? (double)LPBOX_ORDER_REFERENCE : (double)LPBOX_ORDER_DEFAULT},
     };
     for (auto &e : tab) if (!strcmp(e.n, name)) { *out = e.v; return LPBOX_OK; }
+    return lpbox_fail(LPBOX_E_BADARG, "unknown scalar '%s'", name);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------
+// A BATCH of handles through ONE launch chain in lockstep: ADMM_bqp of every member at once, grid (X, B) per
+// launch, each member on its own control state -- one that has stopped, reached its own max_iters or whose PCG has converged falls
+// through; a GEN_HALT_PCG_MORE on any member resumes the chain for all.  The handles are borrowed and stay ordinary handles: per member
+// the arithmetic is that of lpbox_bqp_solve on its own, bit for bit.  Default summation order only.
+struct lpbox_bqp_lockstep {
+    std::vector<lpbox_bqp *> hs;
+    int B = 0, device = 0;
+    ChainLockstep chain{CHAIN_RULES_GEN, CHAIN_RULES_GEN.kmax_start};
+    int kmax_forced = 0;                            // LPBOX_BQP_KMAX at create (0: adaptive, every solve starts at the rules' kmax)
+    bool use_graph = false;                         // LPBOX_BQP_LOCKSTEP_GRAPH
+    hipStream_t stream = nullptr;
+    StreamTimer timer;
+    GraphCache graphs;                              // two iterations per (kmax, start parity), for the member count and extents of `grid`
+    GenBatchGrid grid{0, 0, 0, 0};
+    DevBuf<GenDev> devs; DevBuf<GenState> dstates;
+    std::vector<GenDev> h_devs; std::vector<GenState> h_states;
+    std::vector<long long> resumes;                 // per member, of the last solve
+    double kernel_ms = 0.0; long long launches = 0, collectives = 0;
+    bool solved = false;
+};
+
+namespace {
+
+// what a member must be for the lockstep chain; `i` names it in the message.  Checked at create and at every solve: a handle can be
+// changed between the calls (lpbox_bqp_set_order).
+int genl_member_ok(const lpbox_bqp *h, int i) {
+    if (!h || !h->has_problem) return lpbox_fail(LPBOX_E_STATE, "problem %d of the batch has no problem", i);
+    if (h->ref) return lpbox_fail(LPBOX_E_UNSUPPORTED, "problem %d of the batch runs in the reference summation order; the batch runs the default order (lpbox_bqp_solve per handle)", i);
+    return LPBOX_OK;
+}
+
+// The launches of the lockstep chain (chain_run_lockstep) over the members whose descriptors stand in devs: the solo chain's launches,
+// launch for launch, so the counts are those of enqueue_iteration / enqueue_pcg / enqueue_tail.  b->h_states[k]: the final states.
+struct GenLockstepOps {
+    lpbox_bqp_lockstep *b; const GenDev *devs; hipStream_t st; GenBatchGrid g; int &parity;
+    int collect(ChainView *v) {
+        HIPCHK(genb_collect_states(devs, g, parity, b->dstates.p, st));
+        HIPCHK(hipMemcpyAsync(b->h_states.data(), b->dstates.p, sizeof(GenState) * (size_t)g.B, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (int i = 0; i < g.B; i++) v[i] = chain_view(b->h_states[i]);
+        return LPBOX_OK;
+    }
+    int resume_pcg() {
+        HIPCHK(genb_launch_resume(devs, g, 0, &parity, st));
+        HIPCHK(genb_enqueue_pcg(devs, g, CHAIN_PAIRS_PER_RESUME, &parity, st));
+        HIPCHK(genb_enqueue_tail(devs, g, &parity, st));
+        b->launches += 5 + 5 * CHAIN_PAIRS_PER_RESUME;
+        return LPBOX_OK;
+    }
+    int batch_head(int, int) { HIPCHK(genb_launch_resume(devs, g, 1, &parity, st)); b->launches += 1; return LPBOX_OK; }
+    int enqueue(int n, int kmax) {
+        HIPCHK(genb_enqueue_iterations(devs, g, n, kmax, &parity, st));
+        b->launches += (long long)n * (16 + 5 * kmax);
+        return LPBOX_OK;
+    }
+    int finalize() { HIPCHK(genb_launch_prep(devs, g, 0, &parity, st)); b->launches += 1; return LPBOX_OK; }
+};
+
+}  // namespace
+
+extern "C" {
+
+lpbox_bqp_lockstep_t *lpbox_bqp_lockstep_create(lpbox_bqp_t **handles, int count) {
+    auto refuse = [](int) -> lpbox_bqp_lockstep * { return nullptr; };     // lpbox_fail has recorded status and text
+    if (!handles || count <= 0) return refuse(lpbox_fail(LPBOX_E_BADARG, "empty batch"));
+    if (count > GEN_BATCH_MAX) return refuse(lpbox_fail(LPBOX_E_BADARG, "%d problems: a lockstep batch takes at most %d", count, GEN_BATCH_MAX));
+    for (int i = 0; i < count; i++) {                               // no device call
+        if (genl_member_ok(handles[i], i) < 0) return nullptr;
+        if (handles[i]->device != handles[0]->device) return refuse(lpbox_fail(LPBOX_E_BADARG, "problem %d of the batch lives on another device than problem 0", i));
+        for (int k = 0; k < i; k++)
+            if (handles[k] == handles[i]) return refuse(lpbox_fail(LPBOX_E_BADARG, "problem %d and problem %d of the batch are the same handle", k, i));
+    }
+    lpbox_bqp_lockstep *b = new lpbox_bqp_lockstep();
+    b->hs.assign(handles, handles + count); b->B = count; b->device = handles[0]->device;
+    b->resumes.assign(count, 0);
+    if (const char *e = getenv("LPBOX_BQP_KMAX")) { int v = atoi(e); if (v >= 1 && v <= 1000) b->kmax_forced = v; }
+    if (const char *e = getenv("LPBOX_BQP_LOCKSTEP_GRAPH")) b->use_graph = atoi(e) != 0;   // replay captured iterations instead of eager launches
+    return b;
+}
+
+void lpbox_bqp_lockstep_destroy(lpbox_bqp_lockstep_t *b) {
+    if (!b) return;
+    if (b->stream) {
+        (void)hipSetDevice(b->device);
+        (void)hipStreamSynchronize(b->stream);
+        b->graphs.clear();
+        b->timer.destroy();
+        (void)hipStreamDestroy(b->stream);
+    }
+    delete b;
+}
+
+// ADMM_bqp (SEGcpp:1384-1832) of every member, each to its own stop; iterations[i] = member i's iteration count
+int lpbox_bqp_lockstep_solve(lpbox_bqp_lockstep_t *b, int *iterations) {
+    if (!b) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
+    for (int i = 0; i < b->B; i++) CHK(genl_member_ok(b->hs[i], i));
+    CHK(use_device(b->device));
+    b->solved = false;
+    // per member, on its own stream: the upload at its first solve and the init launches of lpbox_bqp_solve (a handful, once per solve)
+    for (int i = 0; i < b->B; i++) { b->hs[i]->solved = false; CHK(gen_begin_solve(b->hs[i])); }
+    for (int i = 0; i < b->B; i++) HIPCHK(hipStreamSynchronize(b->hs[i]->stream));
+    if (!b->stream) {
+        HIPCHK(hipStreamCreate(&b->stream));
+        HIPCHK(b->timer.create());
+        HIPCHK(b->devs.alloc(b->B)); HIPCHK(b->dstates.alloc(b->B));
+        b->h_devs.resize(b->B); b->h_states.resize(b->B);
+    }
+    GenBatchGrid g{b->B, 0, 1, 1};
+    int iter_end = 0, pcg_cap = 1;
+    for (int i = 0; i < b->B; i++) {
+        const lpbox_bqp *h = b->hs[i];
+        g.cols = std::max(g.cols, h->G); g.y = std::max(g.y, std::max(h->G, h->Gl)); g.rows = std::max(g.rows, std::max(h->Gm, h->Gl));
+        iter_end = std::max(iter_end, h->prm.max_iters); pcg_cap = std::max(pcg_cap, h->prm.pcg_maxiters);
+        b->h_devs[i] = h->dev();
+    }
+    if (g.cols != b->grid.cols || g.y != b->grid.y || g.rows != b->grid.rows || g.B != b->grid.B) b->graphs.clear();   // the captured launches carry the grid
+    b->grid = g;
+    hipStream_t st = b->stream;
+    HIPCHK(hipMemcpyAsync(b->devs.p, b->h_devs.data(), sizeof(GenDev) * (size_t)b->B, hipMemcpyHostToDevice, st));
+    b->chain.rules = CHAIN_RULES_GEN; b->chain.rules.pcg_cap = pcg_cap;
+    b->chain.kmax = b->kmax_forced ? b->kmax_forced : CHAIN_RULES_GEN.kmax_start;       // every solve starts where a fresh handle starts
+    b->chain.adaptive = !b->kmax_forced;
+    b->launches = 0; b->kernel_ms = 0.0;
+    std::fill(b->resumes.begin(), b->resumes.end(), 0);
+    int parity = 0;                                 // where gen_begin_solve leaves every member (two flips after the init)
+    for (int i = 0; i < b->B; i++)
+        if (b->hs[i]->parity != parity) return lpbox_fail(LPBOX_E_STATE, "problem %d of the batch: unexpected state parity after its init", i);
+    HIPCHK(b->timer.start(st));
+    const int rc = chain_run_lockstep(b->chain, b->B, nullptr, b->graphs, ChainIo{st, parity, b->launches, b->collectives, b->use_graph, true}, iter_end,
+                                      b->resumes.data(), GenLockstepOps{b, b->devs.p, st, g, parity});
+    if (rc >= 0)
+        // best_sol of a member whose loop ended right after an improvement: as lpbox_bqp_solve does behind its loop
+        for (int i = 0; i < b->B; i++) {
+            const lpbox_bqp *h = b->hs[i];
+            if (b->h_states[i].copy_best) HIPCHK(hipMemcpyAsync(h->best.p, h->x.p, sizeof(double) * (size_t)h->n, hipMemcpyDeviceToDevice, st));
+        }
+    double ms = 0.0;
+    const hipError_t e = b->timer.stop_sync(st, &ms);
+    if (rc < 0) return rc;
+    HIPCHK(e);
+    b->kernel_ms = ms;
+    for (int i = 0; i < b->B; i++) {
+        lpbox_bqp *h = b->hs[i];
+        double own = 0.0;
+        HIPCHK(h->timer.stop_sync(h->stream, &own));                // (started by gen_begin_solve; the chain's time and launches are the batch's)
+        h->hst = b->h_states[i]; h->parity = parity; h->solved = true;
+        h->chain.pcg_resumes = b->resumes[i]; h->kernel_ms = 0.0; h->launches = 0;
+        if (iterations) iterations[i] = h->hst.iter;
+    }
+    b->solved = true;
+    return LPBOX_OK;
+}
+
+int lpbox_bqp_lockstep_get_scalar(lpbox_bqp_lockstep_t *b, const char *name, double *out) {
+    if (!b || !name || !out) return lpbox_fail(LPBOX_E_BADHANDLE, "bad handle");
+    struct { const char *n; double v; } tab[] = {
+        {"count", (double)b->B}, {"launches", (double)b->launches}, {"kernel_ms", b->kernel_ms},
+        {"kmax", (double)(b->solved || b->kmax_forced ? b->chain.kmax : CHAIN_RULES_GEN.kmax_start)}, {"graph", b->use_graph ? 1.0 : 0.0},
+        {"graph_entries", (double)b->graphs.entries.size()},
+        {"grid_cols", (double)b->grid.cols}, {"grid_y", (double)b->grid.y}, {"grid_rows", (double)b->grid.rows},
+    };
+    for (auto &e : tab) if (!strcmp(e.n, name)) { *out = e.v; return LPBOX_OK; }
+    if (!strncmp(name, "pcg_resumes_", 12)) {
+        char *end = nullptr;
+        const long i = strtol(name + 12, &end, 10);
+        if (end != name + 12 && !*end && i >= 0 && i < b->B) { *out = (double)b->resumes[(size_t)i]; return LPBOX_OK; }
+    }
     return lpbox_fail(LPBOX_E_BADARG, "unknown scalar '%s'", name);
 }
 

@@ -29,7 +29,9 @@ __device__ __forceinline__ void store_partials(const GenDev &d, int slot0, doubl
     }
 }
 
-__global__ void __launch_bounds__(T) gen_k_fin(GenDev d, int nv) {
+// ---- bodies.  One per phase, shared by the entry of one problem (gen_k_*) and the entry of a batch in lockstep (gen_kb_*); the entries
+// are at the end of this namespace.
+__device__ __forceinline__ void gen_b_fin(const GenDev &d, int nv) {
     __shared__ double red[2 * RED_MAXV * RED_MAXW];
     int parity = 0;
     fin_reduce<T>(d.part, d.G, nv, d.red, red, parity);
@@ -96,7 +98,7 @@ __global__ void gen_k_init2(GenDev d) {
     d.st[0].best_bin_obj = v; d.st[1].best_bin_obj = v;
 }
 
-__global__ void gen_k_resume(GenDev d, int in, int out, int reset_pcg_max) {
+__device__ __forceinline__ void gen_b_resume(const GenDev &d, int in, int out, int reset_pcg_max) {
     d.st[out] = d.st[in];
     if (d.st[out].halt == GEN_HALT_PCG_MORE) d.st[out].halt = GEN_HALT_NONE;
     if (reset_pcg_max) d.st[out].pcg_max = 0;
@@ -104,7 +106,7 @@ __global__ void gen_k_resume(GenDev d, int in, int out, int reset_pcg_max) {
 
 // finalise the previous iteration from red[0..7) = x.x, |x-y1|^2, |x-y2|^2, x.Ax, b.x, xb.A xb, b.xb (SEGcpp:1742-1794), then the
 // partial of ||x + z2/rho2 - 1/2||^2 for the next one
-__global__ void __launch_bounds__(T) gen_k_prep(GenDev d, int in, int out, int do_prep) {
+__device__ __forceinline__ void gen_b_prep(const GenDev &d, int in, int out, int do_prep) {
     __shared__ double red[2 * RED_MAXV * RED_MAXW];
     int parity = 0;
     const GenState *si = d.st + in;
@@ -142,8 +144,9 @@ __global__ void __launch_bounds__(T) gen_k_prep(GenDev d, int in, int out, int d
     store_partials<1>(d, 0, pa, red, parity);
 }
 
-// y1, y2, y3, matrix / preconditioner refresh (:1619-1650), rhs base (:1656), preconditioner (:1711-1718), best_sol copy (:1792)
-__global__ void __launch_bounds__(T) gen_k_y(GenDev d, int in, int out) {
+// y1, y2, y3, matrix / preconditioner refresh (:1619-1650), rhs base (:1656), preconditioner (:1711-1718), best_sol copy (:1792).
+// nblk: the workgroups that run this problem's body (its own extent max(G, Gl, 1), not the grid of a batch)
+__device__ __forceinline__ void gen_b_y(const GenDev &d, int in, int out, int nblk) {
     const GenState *si = d.st + in;
     if (si->halt || si->phase != 1) { forward_state(d, in, out); return; }
     const GenParams &P = d.prm;
@@ -178,7 +181,7 @@ __global__ void __launch_bounds__(T) gen_k_y(GenDev d, int in, int out) {
             d.gsrc[j] = y1;                                                       // x_sol = y1 (:1721)
         }
     if (refresh) {                                                                // the scaled transposes (:1643, :1648)
-        const long stride = (long)gridDim.x * T;
+        const long stride = (long)nblk * T;
         if (d.eq && d.ineq) for (long k = (long)blockIdx.x * T + threadIdx.x; k < d.Cnnz; k += stride) d.Cc_sv[k] = P.learning_fact * d.Cc_sv[k];
         if (d.ineq) for (long k = (long)blockIdx.x * T + threadIdx.x; k < d.Ennz; k += stride) d.Ec_sv[k] = P.learning_fact * d.Ec_sv[k];
     }
@@ -193,7 +196,7 @@ __global__ void __launch_bounds__(T) gen_k_y(GenDev d, int in, int out) {
     if (LEADER) { d.st[out] = *si; d.st[out].rhoUpdated = 0; d.st[out].copy_best = 0; }
 }
 
-__global__ void __launch_bounds__(T) gen_k_rhs_cols(GenDev d, int in, int out) {   // :1663-1706
+__device__ __forceinline__ void gen_b_rhs_cols(const GenDev &d, int in, int out) {   // :1663-1706
     const GenState *si = d.st + in;
     if (si->halt || si->phase != 1) { forward_state(d, in, out); return; }
     for (int q = 0; q < d.EPT; q++) {
@@ -209,7 +212,7 @@ __global__ void __launch_bounds__(T) gen_k_rhs_cols(GenDev d, int in, int out) {
 
 // qC = C v, qE = E v.  mode 0: v = gsrc.  mode 1: v = the PCG search direction; the exit test / beta of the previous PCG iteration is
 // evaluated here (SEGcpp:445-467) -- this launch exists (one workgroup) even without constraints.
-__global__ void __launch_bounds__(T) gen_k_rows(GenDev d, int in, int out, int mode) {
+__device__ __forceinline__ void gen_b_rows(const GenDev &d, int in, int out, int mode) {
     const GenState *si = d.st + in;
     if (si->halt) { forward_state(d, in, out); return; }
     const GenParams &P = d.prm;
@@ -271,7 +274,7 @@ __global__ void __launch_bounds__(T) gen_k_rows(GenDev d, int in, int out, int m
         for (int s = 0; s < d.EPTl; s++) { const int i = blockIdx.x * (T * d.EPTl) + s * T + threadIdx.x; if (i < d.l) d.qE[i] = row(d.Er, i); }
 }
 
-__global__ void __launch_bounds__(T) gen_k_resid(GenDev d, int in, int out) {       // :419-441
+__device__ __forceinline__ void gen_b_resid(const GenDev &d, int in, int out) {       // :419-441
     __shared__ double red[2 * RED_MAXV * RED_MAXW];
     int parity = 0;
     const GenState *si = d.st + in;
@@ -297,7 +300,7 @@ __global__ void __launch_bounds__(T) gen_k_resid(GenDev d, int in, int out) {   
     if (LEADER) { d.st[out] = *si; d.st[out].pcg_k = 0; d.st[out].pcg_done = 0; d.st[out].pcg_first = 0; d.st[out].phase = 2; }
 }
 
-__global__ void __launch_bounds__(T) gen_k_pcg_cols(GenDev d, int in, int out) {    // tmp = M p, partial p.tmp (:447-448)
+__device__ __forceinline__ void gen_b_pcg_cols(const GenDev &d, int in, int out) {    // tmp = M p, partial p.tmp (:447-448)
     __shared__ double red[2 * RED_MAXV * RED_MAXW];
     int parity = 0;
     const GenState *si = d.st + in;
@@ -338,7 +341,7 @@ __global__ void __launch_bounds__(T) gen_k_pcg_cols(GenDev d, int in, int out) {
     forward_state(d, in, out);
 }
 
-__global__ void __launch_bounds__(T) gen_k_pcg_upd(GenDev d, int in, int out) {     // :448-462
+__device__ __forceinline__ void gen_b_pcg_upd(const GenDev &d, int in, int out) {     // :448-462
     __shared__ double red[2 * RED_MAXV * RED_MAXW];
     int parity = 0;
     const GenState *si = d.st + in;
@@ -367,7 +370,7 @@ __global__ void __launch_bounds__(T) gen_k_pcg_upd(GenDev d, int in, int out) { 
 }
 
 // after the PCG: commit x, duals z1 z2 (:1733-1734), the seven partials (:1742-1793; A x and A round(x) gathered from the final iterate)
-__global__ void __launch_bounds__(T) gen_k_post(GenDev d, int in, int out) {
+__device__ __forceinline__ void gen_b_post(const GenDev &d, int in, int out) {
     __shared__ double red[2 * RED_MAXV * RED_MAXW];
     int parity = 0;
     const GenState *si = d.st + in;
@@ -412,7 +415,7 @@ __global__ void __launch_bounds__(T) gen_k_post(GenDev d, int in, int out) {
 }
 
 // z3 += gamma rho3 (C x - d) (:1736), z4 += gamma rho4 (E x + y3 - f) (:1739); Ex = E x for the next y3
-__global__ void __launch_bounds__(T) gen_k_dual(GenDev d, int in, int out, int init_only) {
+__device__ __forceinline__ void gen_b_dual(const GenDev &d, int in, int out, int init_only) {
     const GenState *si = d.st + in;
     if (init_only) {
         if (d.ineq && blockIdx.x < d.Gl)
@@ -437,6 +440,40 @@ __global__ void __launch_bounds__(T) gen_k_dual(GenDev d, int in, int out, int i
         }
     if (LEADER) { d.st[out] = *si; d.st[out].have_prev = 1; d.st[out].phase = 0; }
 }
+
+// ---- entries.  gen_k_*: one problem, the descriptor in the kernel arguments.  gen_kb_*: a BATCH of problems in lockstep (DESIGN.md
+// section 34), grid (X, B): row blockIdx.y of the grid runs problem blockIdx.y through the same body on its own descriptor, control
+// state, partials and vectors.  X is the largest extent of that kernel over the batch; a workgroup at or beyond its own problem's extent
+// leaves before it touches anything (the bodies index partials and vectors by blockIdx.x without a bound of their own: the solo grid is
+// exactly the extent).  A problem that has halted, or whose PCG is done, forwards its state inside the body as its solo launch does.
+__device__ __forceinline__ int ext_cols(const GenDev &d) { return d.G; }
+__device__ __forceinline__ int ext_y(const GenDev &d) { const int a = d.G > d.Gl ? d.G : d.Gl; return a > 1 ? a : 1; }
+__device__ __forceinline__ int ext_rows(const GenDev &d) { const int a = d.Gm > d.Gl ? d.Gm : d.Gl; return a > 1 ? a : 1; }
+
+__global__ void __launch_bounds__(T) gen_k_fin(GenDev d, int nv) { gen_b_fin(d, nv); }
+__global__ void gen_k_resume(GenDev d, int in, int out, int reset_pcg_max) { gen_b_resume(d, in, out, reset_pcg_max); }
+__global__ void __launch_bounds__(T) gen_k_prep(GenDev d, int in, int out, int do_prep) { gen_b_prep(d, in, out, do_prep); }
+__global__ void __launch_bounds__(T) gen_k_y(GenDev d, int in, int out) { gen_b_y(d, in, out, (int)gridDim.x); }
+__global__ void __launch_bounds__(T) gen_k_rhs_cols(GenDev d, int in, int out) { gen_b_rhs_cols(d, in, out); }
+__global__ void __launch_bounds__(T) gen_k_rows(GenDev d, int in, int out, int mode) { gen_b_rows(d, in, out, mode); }
+__global__ void __launch_bounds__(T) gen_k_resid(GenDev d, int in, int out) { gen_b_resid(d, in, out); }
+__global__ void __launch_bounds__(T) gen_k_pcg_cols(GenDev d, int in, int out) { gen_b_pcg_cols(d, in, out); }
+__global__ void __launch_bounds__(T) gen_k_pcg_upd(GenDev d, int in, int out) { gen_b_pcg_upd(d, in, out); }
+__global__ void __launch_bounds__(T) gen_k_post(GenDev d, int in, int out) { gen_b_post(d, in, out); }
+__global__ void __launch_bounds__(T) gen_k_dual(GenDev d, int in, int out, int init_only) { gen_b_dual(d, in, out, init_only); }
+
+__global__ void __launch_bounds__(T) gen_kb_fin(const GenDev *__restrict__ devs, int nv) { gen_b_fin(devs[blockIdx.y], nv); }
+__global__ void gen_kb_resume(const GenDev *__restrict__ devs, int in, int out, int reset_pcg_max) { gen_b_resume(devs[blockIdx.y], in, out, reset_pcg_max); }
+__global__ void __launch_bounds__(T) gen_kb_prep(const GenDev *__restrict__ devs, int in, int out, int do_prep) { const GenDev &d = devs[blockIdx.y]; if ((int)blockIdx.x >= ext_cols(d)) return; gen_b_prep(d, in, out, do_prep); }
+__global__ void __launch_bounds__(T) gen_kb_y(const GenDev *__restrict__ devs, int in, int out) { const GenDev &d = devs[blockIdx.y]; if ((int)blockIdx.x >= ext_y(d)) return; gen_b_y(d, in, out, ext_y(d)); }
+__global__ void __launch_bounds__(T) gen_kb_rhs_cols(const GenDev *__restrict__ devs, int in, int out) { const GenDev &d = devs[blockIdx.y]; if ((int)blockIdx.x >= ext_cols(d)) return; gen_b_rhs_cols(d, in, out); }
+__global__ void __launch_bounds__(T) gen_kb_rows(const GenDev *__restrict__ devs, int in, int out, int mode) { const GenDev &d = devs[blockIdx.y]; if ((int)blockIdx.x >= ext_rows(d)) return; gen_b_rows(d, in, out, mode); }
+__global__ void __launch_bounds__(T) gen_kb_resid(const GenDev *__restrict__ devs, int in, int out) { const GenDev &d = devs[blockIdx.y]; if ((int)blockIdx.x >= ext_cols(d)) return; gen_b_resid(d, in, out); }
+__global__ void __launch_bounds__(T) gen_kb_pcg_cols(const GenDev *__restrict__ devs, int in, int out) { const GenDev &d = devs[blockIdx.y]; if ((int)blockIdx.x >= ext_cols(d)) return; gen_b_pcg_cols(d, in, out); }
+__global__ void __launch_bounds__(T) gen_kb_pcg_upd(const GenDev *__restrict__ devs, int in, int out) { const GenDev &d = devs[blockIdx.y]; if ((int)blockIdx.x >= ext_cols(d)) return; gen_b_pcg_upd(d, in, out); }
+__global__ void __launch_bounds__(T) gen_kb_post(const GenDev *__restrict__ devs, int in, int out) { const GenDev &d = devs[blockIdx.y]; if ((int)blockIdx.x >= ext_cols(d)) return; gen_b_post(d, in, out); }
+__global__ void __launch_bounds__(T) gen_kb_dual(const GenDev *__restrict__ devs, int in, int out, int init_only) { const GenDev &d = devs[blockIdx.y]; if ((int)blockIdx.x >= ext_rows(d)) return; gen_b_dual(d, in, out, init_only); }
+__global__ void gen_kb_collect(const GenDev *__restrict__ devs, int parity, GenState *out) { out[blockIdx.x] = devs[blockIdx.x].st[parity]; }
 
 }  // namespace
 
@@ -478,3 +515,55 @@ hipError_t gen_launch_pcg_cols(const GenDev &d, int *parity, hipStream_t s) { GE
 hipError_t gen_launch_pcg_upd(const GenDev &d, int *parity, hipStream_t s) { GEN_LAUNCH(gen_k_pcg_upd, d.G); return hipGetLastError(); }
 hipError_t gen_launch_post(const GenDev &d, int *parity, hipStream_t s) { GEN_LAUNCH(gen_k_post, d.G); return hipGetLastError(); }
 hipError_t gen_launch_dual(const GenDev &d, int init_only, int *parity, hipStream_t s) { GEN_LAUNCH(gen_k_dual, gmax3(d.Gm, d.Gl, 1), init_only); return hipGetLastError(); }
+
+// ---- a batch in lockstep: the launches of enqueue_iteration / enqueue_pcg / enqueue_tail of lpbox_gen_capi.hip, launch for launch,
+// over (extent, members).  The reductions are launches of their own here too (one workgroup per member): 16 + 5 kmax per iteration.
+#define GENB_LAUNCH(kernel, X, ...)                                                                              \
+    do {                                                                                                         \
+        hipLaunchKernelGGL(kernel, dim3(X, g.B), dim3(T), 0, s, devs, *parity, *parity ^ 1, ##__VA_ARGS__);      \
+        *parity ^= 1;                                                                                            \
+    } while (0)
+#define GENB_FIN(nv) hipLaunchKernelGGL(gen_kb_fin, dim3(1, g.B), dim3(T), 0, s, devs, nv)
+
+hipError_t genb_launch_resume(const GenDev *devs, const GenBatchGrid &g, int reset_pcg_max, int *parity, hipStream_t s) {
+    hipLaunchKernelGGL(gen_kb_resume, dim3(1, g.B), dim3(1), 0, s, devs, *parity, *parity ^ 1, reset_pcg_max);
+    *parity ^= 1;
+    return hipGetLastError();
+}
+hipError_t genb_launch_prep(const GenDev *devs, const GenBatchGrid &g, int do_prep, int *parity, hipStream_t s) { GENB_LAUNCH(gen_kb_prep, g.cols, do_prep); return hipGetLastError(); }
+hipError_t genb_enqueue_pcg(const GenDev *devs, const GenBatchGrid &g, int pairs, int *parity, hipStream_t s) {
+    for (int k = 0; k < pairs; k++) {
+        GENB_LAUNCH(gen_kb_rows, g.rows, 1);
+        GENB_LAUNCH(gen_kb_pcg_cols, g.cols);
+        GENB_FIN(1);
+        GENB_LAUNCH(gen_kb_pcg_upd, g.cols);
+        GENB_FIN(2);
+    }
+    return hipGetLastError();
+}
+hipError_t genb_enqueue_tail(const GenDev *devs, const GenBatchGrid &g, int *parity, hipStream_t s) {
+    GENB_LAUNCH(gen_kb_post, g.cols);
+    GENB_FIN(7);
+    GENB_LAUNCH(gen_kb_rows, g.rows, 0);
+    GENB_LAUNCH(gen_kb_dual, g.rows, 0);
+    return hipGetLastError();
+}
+hipError_t genb_enqueue_iterations(const GenDev *devs, const GenBatchGrid &g, int iters, int kmax, int *parity, hipStream_t s) {
+    for (int it = 0; it < iters; it++) {
+        GENB_LAUNCH(gen_kb_prep, g.cols, 1);
+        GENB_FIN(1);
+        GENB_LAUNCH(gen_kb_y, g.y);
+        GENB_LAUNCH(gen_kb_rhs_cols, g.cols);
+        GENB_LAUNCH(gen_kb_rows, g.rows, 0);
+        GENB_LAUNCH(gen_kb_resid, g.cols);
+        GENB_FIN(3);
+        hipError_t e = genb_enqueue_pcg(devs, g, kmax, parity, s);
+        if (e == hipSuccess) e = genb_enqueue_tail(devs, g, parity, s);
+        if (e != hipSuccess) return e;
+    }
+    return hipGetLastError();
+}
+hipError_t genb_collect_states(const GenDev *devs, const GenBatchGrid &g, int parity, GenState *out, hipStream_t s) {
+    hipLaunchKernelGGL(gen_kb_collect, dim3(g.B), dim3(1), 0, s, devs, parity, out);
+    return hipGetLastError();
+}

@@ -150,6 +150,10 @@ SYMBOLS = {
     "lpbox_bqp_batch_get_vec": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, _dp, C.c_long]),
     "lpbox_bqp_batch_get_scalar": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.POINTER(C.c_double)]),
     "lpbox_bqp_batch_set_order": (C.c_int, [C.c_void_p, C.c_int]),
+    "lpbox_bqp_lockstep_create": (C.c_void_p, [C.c_void_p, C.c_int]),
+    "lpbox_bqp_lockstep_destroy": (None, [C.c_void_p]),
+    "lpbox_bqp_lockstep_solve": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "lpbox_bqp_lockstep_get_scalar": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_double)]),
 }
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p)

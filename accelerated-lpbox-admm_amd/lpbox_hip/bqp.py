@@ -308,3 +308,147 @@ def solve_many(problems, **kw):
         out.append(sol)
     s.close()
     return out
+
+
+# ---- many problems of any size at once: one launch chain in lockstep ---------------------------------------
+def _is_problem(P):
+    return isinstance(P, dict) and all(k in P for k in ("n", "A", "b", "x0"))
+
+
+def _as_problem(P):
+    """A problem dict, or the positional tuple (n, A, b, x0[, C, d[, E, f]]) of `BqpSolver`."""
+    if isinstance(P, (tuple, list)) and len(P) in (4, 6, 8):
+        return dict(zip(("n", "A", "b", "x0", "C", "d", "E", "f"), P))
+    return P
+
+
+def _dims(P):
+    return (int(P["n"]), 0 if P.get("C") is None else len(P["d"]), 0 if P.get("E") is None else len(P["f"]))
+
+
+class BqpLockstep:
+    """A batch of BQPs of any size through ONE launch chain in lockstep (lpbox_bqp_lockstep_* in include/lpbox_hip.h): every launch of
+    `BqpSolver`'s chain runs once for all members over a (workgroups, members) grid, each member on its own control state, to its own
+    stop.  Meant for many problems with a dimension above `BATCH_MAX_DIM`, where `BqpBatch` does not reach and a loop over `BqpSolver`
+    handles is bound by its launches; every member gets the bits `BqpSolver` gives it alone.
+
+    members: problem dicts as for `BqpBatch` (or the tuples (n, A, b, x0[, C, d[, E, f]])) -- a `BqpSolver` is built for each and closed
+    with the batch -- and / or `BqpSolver` objects (borrowed; default summation order only).  presets / params: None, a single value, or one
+    per member; they apply to the members built here (a borrowed solver keeps its own).  `batch[i]` is member i's
+    `BqpSolver`: its getters, and a `solve` of its own, work after the batch's solve."""
+
+    def __init__(self, members, presets=None, params=None, device=0):
+        members = [_as_problem(m) for m in members] if members is not None else []
+        if not members:
+            raise ValueError("BqpLockstep: no problems")
+        count = len(members)
+        presets = _per_problem(presets, count, "presets")
+        params = _per_problem(params, count, "params")
+        for k, m in enumerate(members):
+            if not isinstance(m, BqpSolver) and not _is_problem(m):
+                raise TypeError("member %d is neither a BqpSolver nor a problem with n, A, b, x0 (and C, d, E, f)" % k)
+        self._L = _lib.load()
+        self._h = None
+        self._own = [not isinstance(m, BqpSolver) for m in members]
+        self.solvers = []
+        try:
+            for k, m in enumerate(members):
+                if isinstance(m, BqpSolver):
+                    self.solvers.append(m)
+                    continue
+                s = BqpSolver.__new__(BqpSolver)
+                self.solvers.append(s)                       # before __init__: a handle it made is closed below when it raises
+                s.__init__(m["n"], m["A"], m["b"], m["x0"], m.get("C"), m.get("d"), m.get("E"), m.get("f"), preset=presets[k], params=params[k],
+                           device=device)
+            arr = (C.c_void_p * count)(*[s._h for s in self.solvers])
+            h = self._L.lpbox_bqp_lockstep_create(arr, count)
+            if not h:
+                rc = self._L.lpbox_last_status()
+                check(rc if rc < 0 else -2, "lpbox_bqp_lockstep_create")
+        except Exception:                                    # no handle of ours stays open
+            self._close_own()
+            raise
+        self._h = C.c_void_p(h)
+        self.count = count
+
+    def _close_own(self):
+        for s, own in zip(self.solvers, self._own):
+            if own:
+                s.close()
+
+    def __len__(self):
+        return len(self.solvers)
+
+    def __getitem__(self, i):
+        return self.solvers[i]
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.lpbox_bqp_lockstep_destroy(self._h)
+            self._h = None
+            self._close_own()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def solve(self):
+        """ADMM_bqp of every member, each to its own stop; the iteration counts as an int32 array."""
+        it = np.zeros(len(self.solvers), np.int32)
+        check(self._L.lpbox_bqp_lockstep_solve(self._h, it.ctypes.data_as(C.c_void_p)), "lpbox_bqp_lockstep_solve")
+        return it
+
+    def scalar(self, name):
+        v = C.c_double()
+        check(self._L.lpbox_bqp_lockstep_get_scalar(self._h, name.encode(), C.byref(v)), "lpbox_bqp_lockstep_get_scalar")
+        return v.value
+
+
+def _solution_of(s, iterations, kernel_ms):
+    sol = s.solution()
+    sol.update(iterations=int(iterations), stop=int(s.scalar("stop")), best_bin_obj=s.scalar("best_bin_obj"), time_elapsed_ms=kernel_ms)
+    return sol
+
+
+def solve_large_many(problems, **kw):
+    """Solve a sequence of problems of any size in one lockstep batch; a list of the dicts the ADMM_bqp_* entry points return
+    (`time_elapsed_ms` is the batch's).  Keywords are those of `BqpLockstep` (presets, params, device)."""
+    s = BqpLockstep(problems, **kw)
+    try:
+        its = s.solve()
+        ms = s.scalar("kernel_ms")
+        return [_solution_of(s[i], its[i], ms) for i in range(len(s))]
+    finally:
+        s.close()
+
+
+def split_by_size(problems):
+    """(indices for `BqpBatch`, indices for `BqpLockstep`): a problem with max(n, m, l) <= BATCH_MAX_DIM goes to the first."""
+    small, large = [], []
+    for i, P in enumerate(problems):
+        (small if max(_dims(P)) <= BATCH_MAX_DIM else large).append(i)
+    return small, large
+
+
+def solve_any(problems, presets=None, params=None, device=0):
+    """Solve a sequence of problems of any sizes: those with max(n, m, l) <= BATCH_MAX_DIM in one `BqpBatch` (`solve_many`), the rest in
+    one `BqpLockstep` (`solve_large_many`); the Solution dicts in the order of `problems`.  presets / params as for `BqpBatch`."""
+    problems = [_as_problem(P) for P in problems]
+    if not problems:
+        raise ValueError("solve_any: no problems")
+    for k, P in enumerate(problems):
+        if not _is_problem(P):
+            raise TypeError("problem %d is not a problem with n, A, b, x0 (and C, d, E, f)" % k)
+    count = len(problems)
+    presets = _per_problem(presets, count, "presets")
+    params = _per_problem(params, count, "params")
+    out = [None] * count
+    for idx, solver in zip(split_by_size(problems), (solve_many, solve_large_many)):
+        if not idx:
+            continue
+        res = solver([problems[i] for i in idx], presets=[presets[i] for i in idx], params=[params[i] for i in idx], device=device)
+        for i, sol in zip(idx, res):
+            out[i] = sol
+    return out

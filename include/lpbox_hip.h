@@ -518,6 +518,29 @@ int lpbox_bqp_batch_get_scalar(lpbox_bqp_batch_t *h, int idx, const char *name, 
  * (they describe the default order).  Unknown mode -> LPBOX_E_BADARG.  lpbox_bqp_* (one problem per handle): lpbox_bqp_set_order above. */
 int lpbox_bqp_batch_set_order(lpbox_bqp_batch_t *h, int mode);
 
+/* ---- a BATCH of generic BQPs of ANY size through ONE launch chain in lockstep ------------------------------
+ * For many problems with a dimension above 2048 (the ones lpbox_bqp_batch_* turns away).  The batch borrows lpbox_bqp_t handles that
+ * hold a problem; they stay ordinary handles (lpbox_bqp_solve, the getters) and must outlive the batch.  Every launch of the one-problem
+ * chain becomes one launch over a (workgroups, members) grid; each member runs on its own control state, with its own preset,
+ * parameters, stop tests and max_iters, and whatever the getters return for a member afterwards is bit for bit what lpbox_bqp_solve
+ * returns for it alone.  Members may differ in n, m, l and type.
+ * _create makes no device call.  It returns NULL, with status and text in lpbox_last_status / lpbox_last_error and the offending
+ * member's index in the text: empty batch or null array -> LPBOX_E_BADARG; a null member or one without a problem -> LPBOX_E_STATE; the
+ * same handle twice, or a member on another device than member 0 -> LPBOX_E_BADARG; a member in the reference summation order ->
+ * LPBOX_E_UNSUPPORTED (lpbox_bqp_solve per handle runs that order).  _solve checks the members again before anything changes.
+ * _solve: uploads (first solve) and initialises every member with the launches of lpbox_bqp_solve, runs the chain, and leaves every
+ * member solved: lpbox_bqp_get_vec / _get_scalar on a member return its result; a member's "pcg_resumes" is its own count, its
+ * "kernel_ms" and "launches" read 0 (the chain's launches belong to the batch).  iterations[count] may be NULL.
+ * LPBOX_BQP_KMAX (read at _create) forces the launch groups per iteration as it does for a handle; LPBOX_BQP_LOCKSTEP_GRAPH=1 replays
+ * captured iterations instead of eager launches.
+ * Scalars: "count", "launches", "kernel_ms", "kmax", "graph", "graph_entries", "grid_cols" / "grid_y" / "grid_rows" (the x-extents of the
+ * launches), "pcg_resumes_<i>" (member i, last solve). */
+typedef struct lpbox_bqp_lockstep lpbox_bqp_lockstep_t;
+lpbox_bqp_lockstep_t *lpbox_bqp_lockstep_create(lpbox_bqp_t **handles, int count);
+void lpbox_bqp_lockstep_destroy(lpbox_bqp_lockstep_t *b);
+int lpbox_bqp_lockstep_solve(lpbox_bqp_lockstep_t *b, int *iterations);
+int lpbox_bqp_lockstep_get_scalar(lpbox_bqp_lockstep_t *b, const char *name, double *out);
+
 #ifdef __cplusplus
 }
 #endif
